@@ -15,6 +15,12 @@ accumulators are gathered onto rank 0 with one RCCL gather per step and added in
 (the progressive merge of FullRaytracer.cs:326-344), overlapped with the next step's render.
 `--split samples` instead gives every rank the whole frame with a disjoint sample range and
 reduces the accumulators onto rank 0.
+
+A plain run sets up, warms up, times `--steps` steps and prints the result line.  `--dump-outputs
+DIR` also writes the last timed step's arrays and the frame accumulators as DIR/<name>.npy (the
+inputs are fixed by the arguments, so two builds compare output for output).  `--full` adds what
+takes runs of its own: the instrumented launch (path_stats) and the roofline from it, the CPU
+baseline and, at N > 1, the per-phase steps (multi_gpu).
 """
 from __future__ import annotations
 
@@ -216,6 +222,30 @@ def cpu_baseline(cfg_name: str, threads: int = 0):
     }
 
 
+DUMP_BUDGET_BYTES = 60 * 10 ** 6  # --dump-outputs: the arrays of one run together (under 64 MB with headers)
+DUMP_SAMPLE_SEED = 0x5EED
+
+
+def dump_outputs(out_dir: str, per_pixel: dict, scalars: dict) -> None:
+    """--dump-outputs: writes every array as out_dir/<name>.npy in float64.  `per_pixel` arrays run
+    over the frame's pixels along their last axis; where they exceed the budget together, the same
+    fixed, seeded sample of pixels (ascending, listed in pixel_index.npy) is kept of each."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    npix = next(iter(per_pixel.values())).shape[-1]
+    per = 8 * (1 + sum(a.size // npix for a in per_pixel.values()))  # bytes per pixel, the index included
+    index = np.arange(npix)
+    if npix * per > DUMP_BUDGET_BYTES:
+        keep = DUMP_BUDGET_BYTES // per
+        index = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(npix, size=keep, replace=False))
+    np.save(os.path.join(out_dir, "pixel_index.npy"), index.astype(np.float64))
+    for name, a in per_pixel.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a[..., index], dtype=np.float64))
+    for name, v in scalars.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray([v], dtype=np.float64))
+
+
 def frame_split(args) -> int:
     """--split frame: the product's multi-GPU path, timed.  One process, rt_frame over devices
     0..N-1 (rtcore_api.hip rt_frame_render: every device renders its interleaved 8-row band set with
@@ -260,6 +290,10 @@ def frame_split(args) -> int:
     tot = acc[1].astype(np.int64) + acc[2].astype(np.int64)
     if not np.all(tot == expect):
         raise SystemExit(f"sample bookkeeping mismatch: {np.unique(tot)} != {expect}")
+    if args.dump_outputs:  # the host SampleSet buffers a caller of rt_frame holds after the last step
+        dump_outputs(args.dump_outputs,
+                     {"frame_sum": np.moveaxis(acc[0], 2, 0).reshape(3, W * H), "frame_samples": acc[1].reshape(W * H),
+                      "frame_misses": acc[2].reshape(W * H)}, {"rays": rays})
     frame.close()
     out = {
         "metric": "Mrays/sec (primary+secondary), multi-GPU product path (rt_frame, host buffers)",
@@ -335,6 +369,15 @@ def main() -> int:
                          "ncclGather to device 0, merge into host SampleSet buffers)")
     ap.add_argument("--dump", default="", help="rank 0 writes the frame accumulators of the warm-up and timed "
                                                "steps (sum, samples, misses) to this .npz (tests)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps rank 0 writes what the last timed step computed (step_sum, "
+                         "step_samples, step_misses), the frame accumulators after it (frame_*) and the timed "
+                         "steps' ray count as DIR/<name>.npy (float64; a fixed seeded sample of the pixels, "
+                         "pixel_index.npy, where the frame is larger than 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the instrumented launch (path_stats) "
+                         "and the roofline from it, the CPU baseline (unless --no-cpu-baseline) and, at N > 1, "
+                         "the untimed per-phase steps (multi_gpu)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
@@ -406,10 +449,10 @@ def main() -> int:
         def start_merge(k: int):
             return k, sharding.gather_slots(slots[k % 2], glists[k % 2], dist, async_op=True)
 
-        def apply_merge(k: int) -> None:
+        def apply_merge(k: int, into=None) -> None:
             if rank == 0:
                 got = glists[k % 2] if world > 1 else [slots[k % 2]]
-                sharding.scatter_slots(f_sum, f_n, f_m, got, rows, W, plane)
+                sharding.scatter_slots(*(into or (f_sum, f_n, f_m)), got, rows, W, plane)
         expect_per_step = frame_spp
         parallelism = (f"row bands x{world} (interleaved {band}-row bands, {frame_spp} spp per frame), "
                        + ("RCCL gather per step" if world > 1 else "one GPU, no collective"))
@@ -430,12 +473,13 @@ def main() -> int:
         def start_merge(k: int):
             return k, sharding.merge_accumulators(sets[k % 2], dist, async_op=True)
 
-        def apply_merge(k: int) -> None:
+        def apply_merge(k: int, into=None) -> None:
             if rank == 0:
+                t_sum, t_n, t_m = into or (f_sum, f_n, f_m)
                 d_sum, d_n, d_m = sets[k % 2]
-                f_sum.add_(d_sum)
-                f_n.add_(d_n)
-                f_m.add_(d_m)
+                t_sum.add_(d_sum)
+                t_n.add_(d_n)
+                t_m.add_(d_m)
         expect_per_step = spp * world
         parallelism = f"sample-sharded x{world}, " + ("RCCL reduce per step" if world > 1 else "one GPU, no collective")
 
@@ -498,9 +542,18 @@ def main() -> int:
         if args.dump:
             np.savez(args.dump, sum=f_sum.cpu().numpy().reshape(3, H, W), samples=n_all.reshape(H, W),
                      misses=m_all.reshape(H, W))
+        if args.dump_outputs and args.steps > 0:
+            # the last timed step alone: its merge (apply_merge) repeated into zeroed accumulators
+            last = (torch.zeros_like(f_sum), torch.zeros_like(f_n), torch.zeros_like(f_m))
+            apply_merge(args.warmup + args.steps - 1, into=last)
+            dump_outputs(args.dump_outputs,
+                         {"step_sum": last[0].cpu().numpy().reshape(3, npix), "step_samples": last[1].cpu().numpy(),
+                          "step_misses": last[2].cpu().numpy(), "frame_sum": f_sum.cpu().numpy().reshape(3, npix),
+                          "frame_samples": n_all, "frame_misses": m_all}, {"rays": total_rays})
+            del last
 
     multi = None
-    if world > 1:
+    if world > 1 and args.full:
         # where an N-GPU step's time goes, from untimed steps after the timed region: every rank's
         # path-kernel time, and the render, collective and merge phases run one at a time
         ks = [torch.zeros(1, dtype=torch.float64, device=dev) for _ in range(world)]
@@ -541,16 +594,6 @@ def main() -> int:
     if rank == 0:
         my_rays_per_step = total_rays / (args.steps * world)  # the average rank's launch
         build = gpu.build_stats()  # of the timed launches (before the instrumented one below)
-        # the BVH kernels' lane-slot split depends on the launch's length (its tail), so they are
-        # instrumented at the timed launch's spp; the brute-force kernels at 1/16 of it
-        st = path_stats(gpu, W, H, spp if info.traversal in (2, 3) else max(1, spp // 16), args.seed, d_rays)
-        fpr = flops_per_ray(st)
-        bpr = bytes_per_ray(st, scene)
-        counters = None
-        traffic_file = os.path.join(ROOT, "profiles", "traffic", f"{args.config}.json")
-        # PMC figures of this launch shape (tools/profile.sh); the profiles are of the 1-GPU launch
-        if os.path.exists(traffic_file) and args.spp == 0 and world == 1:
-            counters = json.load(open(traffic_file))
         metric = BASELINE_METRIC if args.config == "bounce1080" else \
             f"Mrays/sec (primary+secondary) and samples/sec, {scene_file} {W}x{H}"
         out = {
@@ -577,17 +620,29 @@ def main() -> int:
             "published_reference": {"samples_per_s": 3.0576e6, "source": "Screenshots/app.png status bar"},
             "rays_per_sample": round(total_rays / total_samples, 4),
             "kernel_ms": round(avg_ms, 3),
-            "roofline": roofline(args.config, fpr, bpr, my_rays_per_step, avg_ms, counters),
-            "path_stats": {"per_ray": {k: round(st[k], 3) for k in ("nodes", "tris", "sphs", "outer")},
-                           "flop_per_ray": round(fpr, 1), "bytes_per_ray": round(bpr, 1),
-                           "rays_per_launch": round(my_rays_per_step),
-                           "lane_slots_per_ray": st["wave_iters_per_ray"],
-                           **({"lane_slots": st["lane_slots"]} if st["lane_slots"] else {}),
-                           **({"stack": st["stack"]} if "stack" in st else {})},
+            "roofline": None,  # --full
             "multi_gpu": multi,
             "scene_build": {"builder": ["auto", "host", "gpu"][info.bvh_builder],
                             **{k: round(v, 2) for k, v in build.items()}},
         }
+        counters = None
+        if args.full:
+            # the BVH kernels' lane-slot split depends on the launch's length (its tail), so they are
+            # instrumented at the timed launch's spp; the brute-force kernels at 1/16 of it
+            st = path_stats(gpu, W, H, spp if info.traversal in (2, 3) else max(1, spp // 16), args.seed, d_rays)
+            fpr = flops_per_ray(st)
+            bpr = bytes_per_ray(st, scene)
+            traffic_file = os.path.join(ROOT, "profiles", "traffic", f"{args.config}.json")
+            # PMC figures of this launch shape (tools/profile.sh); the profiles are of the 1-GPU launch
+            if os.path.exists(traffic_file) and args.spp == 0 and world == 1:
+                counters = json.load(open(traffic_file))
+            out["roofline"] = roofline(args.config, fpr, bpr, my_rays_per_step, avg_ms, counters)
+            out["path_stats"] = {"per_ray": {k: round(st[k], 3) for k in ("nodes", "tris", "sphs", "outer")},
+                                 "flop_per_ray": round(fpr, 1), "bytes_per_ray": round(bpr, 1),
+                                 "rays_per_launch": round(my_rays_per_step),
+                                 "lane_slots_per_ray": st["wave_iters_per_ray"],
+                                 **({"lane_slots": st["lane_slots"]} if st["lane_slots"] else {}),
+                                 **({"stack": st["stack"]} if "stack" in st else {})}
         if counters is not None:
             rf = out["roofline"]
             rf["traffic"] = counters["traffic_bytes"]
@@ -599,7 +654,7 @@ def main() -> int:
                 rf["measured"] = {"achieved": round(gbs, 1), "frac": round(gbs / HBM_PEAK_GBS, 4), "unit": "GB/s",
                                   "basis": "PMC 2 x FETCH_SIZE + WRITE_SIZE per launch (L2 -> fabric, includes "
                                            "Infinity Cache hits) / path-kernel time"}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.config, args.cpu_threads)
         print(json.dumps(out), flush=True)
     gpu.close()

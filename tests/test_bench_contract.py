@@ -23,8 +23,8 @@ def _last_json(out: str) -> dict:
 
 
 def test_bench_line_single_gpu():
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--spp", "16"], cwd=ROOT,
-                       capture_output=True, text=True, timeout=240)
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--spp", "16"],
+                       cwd=ROOT, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _last_json(r.stdout)
     assert KEYS <= set(d)
@@ -44,11 +44,43 @@ def test_bench_line_single_gpu():
     assert d["kernel_ms"] <= d["ms_per_step"] * 1.001
 
 
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """Without --full the run is the timed steps alone: the driver's keys without the roofline, the
+    instrumented launch and the CPU baseline.  --dump-outputs writes float64 arrays: the frame
+    accumulators (equal to --dump's) and the last timed step alone."""
+    out, npz = tmp_path / "out", tmp_path / "frame.npz"
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--spp", "4",
+                        "--config", "bounce256", "--dump-outputs", str(out), "--dump", str(npz)], cwd=ROOT,
+                       capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _last_json(r.stdout)
+    assert KEYS - {"cpu_baseline"} <= set(d) and d["roofline"] is None
+    assert "cpu_baseline" not in d and "path_stats" not in d
+    assert d["steps"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0 and d["dtype"] == "f32"
+    assert d["kernel_ms"] <= d["ms_per_step"] * 1.001
+    got = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    assert set(got) == {"pixel_index", "step_sum", "step_samples", "step_misses", "frame_sum", "frame_samples",
+                        "frame_misses", "rays"}
+    assert all(a.dtype == np.float64 for a in got.values())
+    npix = 256 * 256
+    assert np.array_equal(got["pixel_index"], np.arange(npix))  # a small frame is written whole
+    ref = np.load(npz)
+    assert np.array_equal(got["frame_sum"], ref["sum"].reshape(3, npix))
+    assert np.array_equal(got["frame_samples"], ref["samples"].reshape(npix))
+    assert np.array_equal(got["frame_misses"], ref["misses"].reshape(npix))
+    assert np.all(got["step_samples"] + got["step_misses"] == 4)
+    assert np.all(got["frame_samples"] + got["frame_misses"] == 12)
+    assert got["step_sum"].shape == (3, npix) and np.all(got["step_sum"] <= got["frame_sum"])
+    assert 0 < got["step_sum"].sum() < got["frame_sum"].sum()
+    # the timed steps' rays are the line's (rays_per_sample is rounded to 4 places, at least 1 ray per sample)
+    assert got["rays"][0] == pytest.approx(d["rays_per_sample"] * 2 * 4 * npix, rel=1e-4)
+
+
 def test_bench_two_ranks_one_device():
     env = dict(os.environ, RTCORE_BENCH_SAME_DEVICE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", "29561", "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--spp", "8", "--no-cpu-baseline"]
+           "--spp", "8", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _last_json(r.stdout)
@@ -76,7 +108,7 @@ def test_bench_gpus2_without_launcher_starts_its_ranks(tmp_path):
     band sets (gloo, both on device 0) equals, bit for bit, one rank rendering the same frame."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["RTCORE_BENCH_SAME_DEVICE"] = "1"
-    common = ["--config", "bounce256", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    common = ["--config", "bounce256", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     two, one = tmp_path / "two.npz", tmp_path / "one.npz"
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--spp", "4", "--dump", str(two)] + common,
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)

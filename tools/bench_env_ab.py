@@ -20,7 +20,7 @@ def main():
             if kv.strip():
                 k, v = kv.strip().split("=", 1)
                 env[k] = v
-        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline"] + bench_args,
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--no-cpu-baseline"] + bench_args,
                            env=env, capture_output=True, text=True, timeout=600)
         lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
         if r.returncode != 0 or not lines:

@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 out=gpurun_out/prof_$tag
 mkdir -p "$out"
 set -e
-rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o run -- python3 bench.py --no-cpu-baseline --steps 20 --warmup 5 "$@" > "$out/trace.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o run -- python3 bench.py --full --no-cpu-baseline --steps 20 --warmup 5 "$@" > "$out/trace.log" 2>&1
 P="python3 bench.py --no-cpu-baseline --steps 5 --warmup 1 $*"
 timeout -s KILL 150 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY --output-format csv -d "$out/pmc1" -o pmc -- $P > "$out/pmc1.log" 2>&1
 timeout -s KILL 150 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out/pmc2" -o pmc -- $P > "$out/pmc2.log" 2>&1

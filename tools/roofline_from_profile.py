@@ -2,7 +2,7 @@
 """Recomputes bench.py's roofline fraction from a rocprofv3 kernel-trace summary: the dominant path
 kernel's average duration (kernel_stats.csv) with the per-launch work of the same run's bench line
 (path_stats: FLOP or bytes per ray segment, rays per launch).
-usage: tools/roofline_from_profile.py KERNEL_STATS.csv BENCH_LINE.json"""
+usage: tools/roofline_from_profile.py KERNEL_STATS.csv BENCH_LINE.json   (the line of a `bench.py --full` run)"""
 import csv
 import json
 import sys
