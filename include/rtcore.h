@@ -38,10 +38,11 @@
 extern "C" {
 #endif
 
-#define RTCORE_ABI_VERSION 5 /* 2: rt_frame_*, rt_render_bands, sample_base in rt_render_frame_multi;
+#define RTCORE_ABI_VERSION 6 /* 2: rt_frame_*, rt_render_bands, sample_base in rt_render_frame_multi;
                                 3: rt_set_jit, rt_scene_get_jit_error, build stats [15..17];
                                 4: rt_kernel_times;
-                                5: rt_frame_submit / rt_frame_collect / rt_frame_inject_fault */
+                                5: rt_frame_submit / rt_frame_collect / rt_frame_inject_fault;
+                                6: rt_trace_paths, rt_debug_ray, rt_bounce_type */
 
 typedef enum rt_status {
     RT_OK = 0,
@@ -288,6 +289,83 @@ int rt_primary_ids(rt_scene* scene, int32_t x0, int32_t y0, int32_t w, int32_t h
  * only through those.  counts_out[x*h + y]; 0 where the root is missed.
  */
 int rt_bvh_counts(rt_scene* scene, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t* counts_out);
+
+/* ------------------------------------------------------------ path inspection --- */
+/* Raytracer.BounceType (Raytracer.cs:14-26), same values. */
+typedef enum rt_bounce_type {
+    RT_BOUNCE_SKIPPED = 0,            /* no record (past the end of the path)                  */
+    RT_BOUNCE_DIFFUSE = 1,
+    RT_BOUNCE_SPECULAR = 2,
+    RT_BOUNCE_SPECULAR_FAIL = 3,      /* a specular direction into the surface ends the path   */
+    RT_BOUNCE_TRANSMITTED = 4,
+    RT_BOUNCE_EMISSION = 5,           /* no event chosen: the path ends on the emission        */
+    RT_BOUNCE_PURE_BLACK = 6,         /* a primitive of no luminance at all                    */
+    RT_BOUNCE_RECURSION_COMPLETE = 7, /* the hit at bounce index Scene.Recursion               */
+    RT_BOUNCE_MISSED = 8,
+    RT_BOUNCE_DEBUG = 9               /* Scene.DebugGeom                                       */
+} rt_bounce_type;
+
+/*
+ * Raytracer.DebugRay (Raytracer.cs:28-33) with its Hit, one per bounce: 96 B, six 16-byte rows,
+ * no pointers.  The floats are the kernel's own fp32 values, not widened.
+ *   offset  0  prim_id       Primitive.ID (insertion order), -1 on a miss
+ *           4  type          rt_bounce_type
+ *           8  inside        Hit.Inside after Primitive.Invert (0 / 1; 0 on a miss)
+ *          12  distance      Hit.Distance along `direction` (0 on a miss, and on the re-hit of a
+ *                            vertex-normal triangle the ray leaves)
+ *          16  fresnel       DebugRay.FresnelRatio: NaN where GetColor does not reach the Fresnel block
+ *                            (Raytracer.cs:120), exactly 1 on total internal reflection (:144)
+ *          20  cos_in        the `cos` of Raytracer.cs:115, -roughNormal . direction; NaN on the types
+ *                            MISSED, DEBUG and RECURSION_COMPLETE, which end before it
+ *          24  bounce        the record's index in its path, 0 = the camera ray
+ *          28  reserved0     0
+ *          32  position[3]   Hit.Position as the shading uses it (0 on a miss)
+ *          44  normal[3]     Hit.Normal, facing the incoming ray (0 on a miss; NaN inside a
+ *                            vertex-normal triangle, Triangle.GetNormal's quirk)
+ *          56  origin[3]     the ray traced at this bounce
+ *          68  direction[3]
+ *          80  tint[3]       the path's tint before this bounce
+ *          92  reserved1     0
+ */
+typedef struct rt_debug_ray {
+    int32_t prim_id;
+    int32_t type;
+    int32_t inside;
+    float distance;
+    float fresnel;
+    float cos_in;
+    int32_t bounce;
+    int32_t reserved0;
+    float position[3];
+    float normal[3];
+    float origin[3];
+    float direction[3];
+    float tint[3];
+    int32_t reserved1;
+} rt_debug_ray;
+
+/* Most records (w * h * spp * (Scene.Recursion + 1)) of one rt_trace_paths call: 96 MB of them. */
+#define RT_TRACE_MAX_RECORDS (1 << 20)
+
+/*
+ * Raytracer.GetDebugTrace (Raytracer.cs:254-260, 289-292; RayInspector.RunTraces) for the
+ * library's own samples: the samples sample_base .. sample_base+spp-1 of every pixel of the tile,
+ * exactly as a render with this seed traces them (the same kernels in the scene's traversal mode;
+ * always the generic ones, whatever rt_set_jit says), with one record per bounce.
+ *   sample k of pixel (x, y) of the tile is s = (x*h + y)*spp + k
+ *   rays_out[s*(recursion+1) + i]   bounce i of the sample; the records past n_rays_out[s] are all
+ *                                   zero (type RT_BOUNCE_SKIPPED)
+ *   n_rays_out[s]  (may be NULL)    records of the sample, 1 .. recursion+1
+ *   colors_out[s]  (may be NULL)    the sample's value as rt_render_tile_1spp returns it for
+ *                                   sample_index = sample_base + k, (-1,-1,-1) on a primary miss
+ * RT_ERR_ARG, before anything is launched, for a null rays_out, spp <= 0, a tile outside the frame
+ * or more than RT_TRACE_MAX_RECORDS records.  Synchronous, on the scene's own stream; the counters
+ * of rt_scene_get_stats, an armed rt_debug_ray_log, rt_kernel_times and the scene-specialised
+ * kernels are left as they were.
+ */
+int rt_trace_paths(rt_scene* scene, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t spp,
+                   uint64_t seed, uint64_t sample_base, rt_debug_ray* rays_out, int32_t* n_rays_out,
+                   rt_color* colors_out);
 
 /* -------------------------------------------------- device-resident renders --- */
 /*

@@ -23,12 +23,18 @@ LIB_PATH = os.path.join(_HERE, "librtcore_hip.so")
 REPO_ROOT = os.path.dirname(_HERE)
 
 RT_OK = 0
-ABI_VERSION = 5  # RTCORE_ABI_VERSION of include/rtcore.h
+ABI_VERSION = 6  # RTCORE_ABI_VERSION of include/rtcore.h
 RT_PRIM_TRIANGLE, RT_PRIM_SPHERE, RT_PRIM_PLANE = 0, 1, 2
 RT_FLAG_MIRROR, RT_FLAG_TWOSIDED, RT_FLAG_INVERT, RT_FLAG_HASNORMALS, RT_FLAG_TRANSFORMED = 1, 2, 4, 8, 16
 RT_CAMERA_FRUSTUM, RT_CAMERA_ORTHO = 0, 1
 RT_TRAVERSAL_AUTO, RT_TRAVERSAL_BRUTE, RT_TRAVERSAL_BVH, RT_TRAVERSAL_BVH2, RT_TRAVERSAL_GROUPED = 0, 1, 2, 3, 4
 RT_BVH_BUILDER_AUTO, RT_BVH_BUILDER_HOST, RT_BVH_BUILDER_GPU = 0, 1, 2
+# rt_bounce_type = Raytracer.BounceType (Raytracer.cs:14-26)
+(RT_BOUNCE_SKIPPED, RT_BOUNCE_DIFFUSE, RT_BOUNCE_SPECULAR, RT_BOUNCE_SPECULAR_FAIL, RT_BOUNCE_TRANSMITTED,
+ RT_BOUNCE_EMISSION, RT_BOUNCE_PURE_BLACK, RT_BOUNCE_RECURSION_COMPLETE, RT_BOUNCE_MISSED, RT_BOUNCE_DEBUG) = range(10)
+BOUNCE_TYPE_NAMES = ("Skipped", "Diffuse", "Specular", "SpecularFail", "Transmitted", "Emission", "PureBlack",
+                     "RecursionComplete", "Missed", "Debug")
+RT_TRACE_MAX_RECORDS = 1 << 20  # records of one rt_trace_paths call
 BUILD_STAT_NAMES = ("prepare_ms", "bvh_ms", "upload_ms", "gpu_build_ms", "ploc_rounds", "wide_nodes", "stack_need",
                     "flat_rects", "flat_boxes", "flat_frames", "flat_frame_boxes", "flat_frame_rects", "flat_tris",
                     "flat_spheres", "hot_nodes", "jit_status", "jit_compile_ms", "jit_cached", "group_max",
@@ -97,6 +103,25 @@ class rt_scene_info(C.Structure):
     ]
 
 
+class rt_debug_ray(C.Structure):
+    """One bounce of rt_trace_paths (Raytracer.DebugRay + its Hit): 96 B, offsets in include/rtcore.h."""
+    _fields_ = [
+        ("prim_id", C.c_int32), ("type", C.c_int32), ("inside", C.c_int32), ("distance", C.c_float),
+        ("fresnel", C.c_float), ("cos_in", C.c_float), ("bounce", C.c_int32), ("reserved0", C.c_int32),
+        ("position", C.c_float * 3), ("normal", C.c_float * 3), ("origin", C.c_float * 3),
+        ("direction", C.c_float * 3), ("tint", C.c_float * 3), ("reserved1", C.c_int32),
+    ]
+
+
+# the same record as a numpy structured dtype (the element type of GpuRaytracer.trace_paths' records)
+DEBUG_RAY_DTYPE = np.dtype([
+    ("prim_id", np.int32), ("type", np.int32), ("inside", np.int32), ("distance", np.float32),
+    ("fresnel", np.float32), ("cos_in", np.float32), ("bounce", np.int32), ("reserved0", np.int32),
+    ("position", np.float32, (3,)), ("normal", np.float32, (3,)), ("origin", np.float32, (3,)),
+    ("direction", np.float32, (3,)), ("tint", np.float32, (3,)), ("reserved1", np.int32),
+])
+
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -140,6 +165,8 @@ def load_library(path: str = "") -> C.CDLL:
         "rt_render_tile": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_uint64, C.c_uint64,
                                      P(rt_color), P(C.c_uint32), P(C.c_uint32), P(C.c_uint64)]),
         "rt_render_tile_1spp": (C.c_int, [C.c_void_p] + [C.c_int32] * 4 + [C.c_uint64, C.c_uint64, P(rt_color)]),
+        "rt_trace_paths": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_uint64, C.c_uint64, P(rt_debug_ray),
+                                     P(C.c_int32), P(rt_color)]),
         "rt_primary_ids": (C.c_int, [C.c_void_p] + [C.c_int32] * 4 + [P(C.c_int32)]),
         "rt_bvh_counts": (C.c_int, [C.c_void_p] + [C.c_int32] * 4 + [P(C.c_int32)]),
         "rt_render_device": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_uint64, C.c_uint64] +
@@ -425,6 +452,25 @@ class GpuRaytracer:
         _check(self.lib.rt_render_tile_1spp(self.handle, x0, y0, w, h, seed, sample_index,
                                             out.ctypes.data_as(C.POINTER(rt_color))))
         return out
+
+    def trace_paths(self, x0: int, y0: int, w: int, h: int, spp: int, seed: int = 0, sample_base: int = 0):
+        """rt_trace_paths (Raytracer.GetDebugTrace for the library's own samples): the samples
+        sample_base .. sample_base+spp-1 of every pixel of the tile as a render with this seed traces
+        them.  Returns (records [w, h, spp, recursion+1] of DEBUG_RAY_DTYPE, zero past a path's end;
+        n_rays int32 [w, h, spp]; colors float64 [w, h, spp, 3], each as render_tile_1spp returns it)."""
+        per = self.params.recursion + 1
+        if w <= 0 or h <= 0 or spp <= 0:
+            raise ValueError("trace_paths: w, h and spp must be positive")
+        if w * h * spp * per > RT_TRACE_MAX_RECORDS:
+            raise ValueError(f"trace_paths: more than {RT_TRACE_MAX_RECORDS} records; trace fewer pixels or samples")
+        records = np.zeros((w, h, spp, per), DEBUG_RAY_DTYPE)
+        n_rays = np.zeros((w, h, spp), np.int32)
+        colors = np.zeros((w, h, spp, 3), np.float64)
+        _check(self.lib.rt_trace_paths(self.handle, x0, y0, w, h, spp, seed, sample_base,
+                                       records.ctypes.data_as(C.POINTER(rt_debug_ray)),
+                                       n_rays.ctypes.data_as(C.POINTER(C.c_int32)),
+                                       colors.ctypes.data_as(C.POINTER(rt_color))))
+        return records, n_rays, colors
 
     def render_device(self, x0, y0, w, h, spp, seed, sample_base, d_sum, d_samples, d_misses, d_rays,
                       stream: int = 0) -> None:

@@ -784,13 +784,37 @@ __device__ __forceinline__ Best query_start(const SceneT& s, int prev)
     return Best{__builtin_huge_valf(), -1};
 }
 
+// What rt_trace_paths records of one bounce (rt_debug_ray, rtcore.h) beyond the ray and the tint,
+// which bounce() holds: filled by shade<..., REC = true> where GetColor sets debugRay.Type and
+// FresnelRatio (Raytracer.cs:79-223).
+struct BounceRec {
+    int prim_id, type, inside;
+    float distance, fresnel, cos_in;
+    V3 pos, nrm;
+};
+// bounce() writes the record as kRecRows float4 rows: the offsets rtcore.h documents
+static_assert(sizeof(rt_debug_ray) == 16 * kRecRows && __builtin_offsetof(rt_debug_ray, distance) == 12 &&
+                  __builtin_offsetof(rt_debug_ray, fresnel) == 16 && __builtin_offsetof(rt_debug_ray, bounce) == 24 &&
+                  __builtin_offsetof(rt_debug_ray, position) == 32 && __builtin_offsetof(rt_debug_ray, normal) == 44 &&
+                  __builtin_offsetof(rt_debug_ray, origin) == 56 && __builtin_offsetof(rt_debug_ray, direction) == 68 &&
+                  __builtin_offsetof(rt_debug_ray, tint) == 80,
+              "rt_debug_ray layout");
+
 // One bounce of Raytracer.GetColor after the closest-hit query.  Returns 0 to continue the
 // path, 1 if the sample ended with colour `col`, 2 if it ended as a miss (Placeholder).
-template <bool VN, bool PIN = false, bool SLOT = false, class SceneT, class VnP, class TestP>
+// REC (the instrumented instances, for rt_trace_paths): *rec receives the bounce's record.  The
+// two returns of GetColor that come before the hit's position and normal are needed (DebugGeom,
+// the recursion limit) are then taken after them, so that the record holds both; nothing in
+// between draws a number or changes the sample.
+template <bool VN, bool PIN = false, bool SLOT = false, bool REC = false, class SceneT, class VnP, class TestP>
 __device__ __forceinline__ int shade(const SceneT& s, const PrimF* __restrict__ prims, const MatF* __restrict__ mats,
                                      const XformF* __restrict__ xfs, VnP vnormals, TestP tests, const PrimD* prims_d,
-                                     const Best& b, Sample& S, V3& col)
+                                     const Best& b, Sample& S, V3& col, [[maybe_unused]] BounceRec* rec = nullptr)
 {
+    if constexpr (REC) {
+        const float nan = __builtin_nanf("");
+        *rec = BounceRec{-1, RT_BOUNCE_MISSED, 0, 0.0f, nan, nan, v3(0.0f, 0.0f, 0.0f), v3(0.0f, 0.0f, 0.0f)};
+    }
     if (b.sg < 0) {
         if (S.bounce == 0 || s.ambient_miss) return 2;
         col = v3(s.ambient_r, s.ambient_g, s.ambient_b);
@@ -808,13 +832,15 @@ __device__ __forceinline__ int shade(const SceneT& s, const PrimF* __restrict__ 
     const MatF& M = mats[__float_as_int(P.d.w)]; // the primitive's material (deduplicated table)
     const uint32_t kind = fl & KIND_MASK;
     const V3 emis = xyz(M.emission);
-    if (s.debug_geom) { // Raytracer.cs:93-98
-        col = xyz(M.specular) + xyz(M.diffuse) + emis;
-        return 1;
-    }
-    if (S.bounce >= s.recursion) {
-        col = S.tint * emis;
-        return 1;
+    if constexpr (!REC) {
+        if (s.debug_geom) { // Raytracer.cs:93-98
+            col = xyz(M.specular) + xyz(M.diffuse) + emis;
+            return 1;
+        }
+        if (S.bounce >= s.recursion) {
+            col = S.tint * emis;
+            return 1;
+        }
     }
     // hit position and normal facing the incoming ray: one straight-line form for every kind
     // (world point o + t d), with transformed spheres and vertex-normal triangles on a separate
@@ -855,6 +881,23 @@ __device__ __forceinline__ int shade(const SceneT& s, const PrimF* __restrict__ 
     }
     const V3 nrm = gin ? -n : n;
     const bool inside = gin ^ ((fl & F_INVERT) != 0);
+    if constexpr (REC) {
+        rec->prim_id = id;
+        rec->inside = inside ? 1 : 0;
+        rec->distance = b.t;
+        rec->pos = pos;
+        rec->nrm = nrm;
+        if (s.debug_geom) { // (the two returns above, see REC)
+            rec->type = RT_BOUNCE_DEBUG;
+            col = xyz(M.specular) + xyz(M.diffuse) + emis;
+            return 1;
+        }
+        if (S.bounce >= s.recursion) {
+            rec->type = RT_BOUNCE_RECURSION_COMPLETE;
+            col = S.tint * emis;
+            return 1;
+        }
+    }
 
     // RandomShine (Raytracer.cs:51-56): z = U^(1/shininess), theta = U * 2pi
     const float shin = M.shininess;
@@ -870,6 +913,7 @@ __device__ __forceinline__ int shade(const SceneT& s, const PrimF* __restrict__ 
     const float diff_lum = M.diffuse.w, emis_lum = M.emission.w;
     float spec_lum = M.specular.w, refr_lum = M.refraction.w;
     const float cs = -dot(rough, S.d);
+    if constexpr (REC) rec->cos_in = cs;
     float cos_out = 0.0f, ior_ratio = 0.0f;
     // (luminances are never NaN: for them x > 0 is the integer compare of the bits, which needs no
     // quieting of the LDS-loaded operands as the max the compiler made of the float form did)
@@ -881,6 +925,7 @@ __device__ __forceinline__ int shade(const SceneT& s, const PrimF* __restrict__ 
         const float sin_out = ior_ratio * fsqrt(1.0f - cs * cs);
         if (sin_out >= 1.0f) {
             refr_lum = 0.0f;
+            if constexpr (REC) rec->fresnel = 1.0f; // Raytracer.cs:144
         } else {
             cos_out = fsqrt(1.0f - sin_out * sin_out);
             // unpolarised Fresnel with numerator and denominator divided by iorOut:
@@ -890,12 +935,14 @@ __device__ __forceinline__ int shade(const SceneT& s, const PrimF* __restrict__ 
             const float ratio = (ra * ra * pb * pb + pa * pa * rb * rb) * rcp(rb * rb * pb * pb) * 0.5f;
             spec_lum *= ratio;
             refr_lum *= 1.0f - ratio;
+            if constexpr (REC) rec->fresnel = ratio; // Raytracer.cs:155
         }
     } else {
         refr_lum = 0.0f;
     }
     const float total = diff_lum + spec_lum + refr_lum + emis_lum;
     if (total <= 0.0f) {
+        if constexpr (REC) rec->type = RT_BOUNCE_PURE_BLACK;
         col = S.tint * emis;
         return 1;
     }
@@ -906,9 +953,11 @@ __device__ __forceinline__ int shade(const SceneT& s, const PrimF* __restrict__ 
     const bool specular = !transmit && spec_lum != 0.0f && (ray_rand -= spec_lum) <= 0.0f;
     const bool diffuse = !transmit && !specular && diff_lum != 0.0f && (ray_rand -= diff_lum) <= 0.0f;
     if (!(transmit | specular | diffuse)) { // emission
+        if constexpr (REC) rec->type = RT_BOUNCE_EMISSION;
         col = S.tint * emis;
         return 1;
     }
+    if constexpr (REC) rec->type = transmit ? RT_BOUNCE_TRANSMITTED : specular ? RT_BOUNCE_SPECULAR : RT_BOUNCE_DIFFUSE;
     V3 out_dir, new_tint;
     if (diffuse) {
         const float dz = acos_turn2(next_u(S.rng)); // 2 acos(U) / pi (Raytracer.cs:215)
@@ -921,6 +970,7 @@ __device__ __forceinline__ int shade(const SceneT& s, const PrimF* __restrict__ 
         const float be = transmit ? cs * ior_ratio - cos_out : 2.0f * cs;
         out_dir = madd(rough, be, S.d * al);
         if (specular && !(dot(out_dir, nrm) > 0.0f)) { // a specular ray into the surface ends the path
+            if constexpr (REC) rec->type = RT_BOUNCE_SPECULAR_FAIL;
             col = S.tint * emis;
             return 1;
         }
@@ -1190,12 +1240,41 @@ __device__ __forceinline__ void refill(Lane& L, Sample& S, const ParT& p, const 
 }
 
 // After a closest-hit query: one bounce of GetColor; a finished sample goes into the item's sums.
-template <bool VN, bool PIN = false, bool SLOT = false, class SceneT, class VnP, class TestP>
+// REC (the instrumented instances): a launch of rt_trace_paths (p.rec_rays set) also stores the
+// bounce's record, and the sample's own colour and record count when it ends, at the slot the lane's
+// open item names: item_pixel gives the pixel, item_sample the sample, S.bounce the bounce.
+template <bool VN, bool PIN = false, bool SLOT = false, bool REC = false, class SceneT, class VnP, class TestP, class ParT>
 __device__ __forceinline__ void bounce(Lane& L, Sample& S, const SceneT& s, const ShadeRecs& R, VnP vnormals, TestP tests,
-                                       const PrimD* prims_d, const Best& b)
+                                       const PrimD* prims_d, const Best& b, [[maybe_unused]] const ParT& p)
 {
     V3 col;
-    const int r = shade<VN, PIN, SLOT>(s, R.prims, R.mats, R.xfs, vnormals, tests, prims_d, b, S, col);
+    [[maybe_unused]] BounceRec rec;
+    [[maybe_unused]] const V3 ro = S.o, rd = S.d, rtint = S.tint; // the ray of this bounce: shade() replaces it
+    [[maybe_unused]] const int rbounce = S.bounce;
+    [[maybe_unused]] unsigned rsample = 0; // (py * w + px) * spp + sample, before the item's counts move on
+    if constexpr (REC) {
+        if (p.rec_rays) {
+            int px, py, c, fx, fy;
+            item_pixel(L.item, p, px, py, c, fx, fy);
+            rsample = ((unsigned)py * (unsigned)p.w + (unsigned)px) * (unsigned)p.spp + (unsigned)item_sample<SLOT>(L, p);
+        }
+    }
+    const int r = shade<VN, PIN, SLOT, REC>(s, R.prims, R.mats, R.xfs, vnormals, tests, prims_d, b, S, col, &rec);
+    if constexpr (REC) {
+        const unsigned slot = rsample * (unsigned)(s.recursion + 1) + (unsigned)rbounce;
+        if (p.rec_rays && slot < p.rec_max && rbounce <= s.recursion) { // whole 16-byte rows (rt_debug_ray)
+            float4* q = p.rec_rays + (size_t)kRecRows * slot;
+            q[0] = make_float4(__int_as_float(rec.prim_id), __int_as_float(rec.type), __int_as_float(rec.inside), rec.distance);
+            q[1] = make_float4(rec.fresnel, rec.cos_in, __int_as_float(rbounce), 0.0f);
+            q[2] = make_float4(rec.pos.x, rec.pos.y, rec.pos.z, rec.nrm.x);
+            q[3] = make_float4(rec.nrm.y, rec.nrm.z, ro.x, ro.y);
+            q[4] = make_float4(ro.z, rd.x, rd.y, rd.z);
+            q[5] = make_float4(rtint.x, rtint.y, rtint.z, 0.0f);
+            if (r != 0) // the sample as a 1-spp pass returns it (its item's sum from zero), and its records
+                p.rec_samples[rsample] = r == 1 ? make_float4(0.0f + col.x, 0.0f + col.y, 0.0f + col.z, __int_as_float(rbounce + 1))
+                                                : make_float4(-1.0f, -1.0f, -1.0f, __int_as_float(rbounce + 1));
+        }
+    }
     if (r != 0) {
         const bool hit = r == 1;
         L.ar += hit ? col.x : 0.0f;
@@ -1345,7 +1424,7 @@ __device__ __forceinline__ void path_body(const CameraF* __restrict__ camp, cons
             // box met its exit face.
             if (VN && __builtin_isnan(S.d.x + S.d.y + S.d.z)) b = Best{__builtin_huge_valf(), -1};
             if (STATS) t2 = __builtin_readcyclecounter();
-            bounce<VN>(L, S, sc, R, vnormals, tests, pq->prims_d, b);
+            bounce<VN, false, false, STATS>(L, S, sc, R, vnormals, tests, pq->prims_d, b, *pq);
         } else if (STATS) {
             t2 = __builtin_readcyclecounter();
         }
@@ -1533,7 +1612,7 @@ __global__ void __launch_bounds__(256, WIDTH == 4 ? RT_BVH_WAVES : RT_BVH2_WAVES
                         r[2] = make_float4(b.t, __int_as_float(b.sg), __int_as_float(S.bounce), 0.0f);
                     }
                 }
-                bounce<VN, !LDS, true>(L, S, s, R, vnormals, tests, pq->prims_d, b);
+                bounce<VN, !LDS, true, STATS>(L, S, s, R, vnormals, tests, pq->prims_d, b, p);
                 done = false;
             }
             refill<true>(L, S, p, s, *cp, lane, total);
@@ -1873,6 +1952,24 @@ __global__ void colors_1spp_kernel(PathParams p, float* __restrict__ out)
     out[3 * o + 2] = miss ? -1.0f : v.z;
 }
 
+// rt_trace_paths: the records and per-sample rows of a launch, which the path kernel wrote row-major
+// over the tile (sample (py * w + px) * spp + k), into the caller's order (x * h + y) * spp + k.
+// One thread per 16-byte row: rows = kRecRows * (recursion + 1) per sample of `rays`, 1 of `samples`.
+__global__ void trace_host_layout_kernel(int w, int h, int spp, int rows, const float4* __restrict__ rays,
+                                         const float4* __restrict__ samples, float4* __restrict__ rays_out,
+                                         float4* __restrict__ samples_out)
+{
+    const size_t n = (size_t)w * h * spp;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n * (size_t)(rows + 1)) return;
+    const size_t so = i / (size_t)(rows + 1), row = i - so * (size_t)(rows + 1); // the caller's sample, its row
+    const size_t pix = so / (size_t)spp, k = so - pix * (size_t)spp;
+    const size_t x = pix / (size_t)h, y = pix - x * (size_t)h;
+    const size_t si = (y * (size_t)w + x) * (size_t)spp + k;
+    if (row < (size_t)rows) rays_out[so * rows + row] = rays[si * rows + row];
+    else samples_out[so] = samples[si];
+}
+
 // Planar row-major tile accumulators -> the caller's SampleSet order (C# [x, y]: x * h + y), one
 // 32-B record per pixel (DoubleColor, samples, misses), so that the host-buffer entry point copies
 // one contiguous image in chunks and adds each chunk sequentially as it lands.
@@ -2136,6 +2233,17 @@ hipError_t launch_tile_host_layout(int w, int h, const double* d_sum, const uint
     if (npix == 0) return hipSuccess;
     hipLaunchKernelGGL(tile_host_layout_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, w, h, d_sum,
                        d_samples, d_misses, d_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_trace_host_layout(int w, int h, int spp, int recursion, const float4* d_rays, const float4* d_samples,
+                                    float4* d_rays_out, float4* d_samples_out, hipStream_t stream)
+{
+    const int rows = kRecRows * (recursion + 1);
+    const size_t n = (size_t)w * h * spp * (size_t)(rows + 1);
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(trace_host_layout_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, w, h, spp, rows,
+                       d_rays, d_samples, d_rays_out, d_samples_out);
     return hipGetLastError();
 }
 

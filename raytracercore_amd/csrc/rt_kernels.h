@@ -62,7 +62,15 @@ struct PathParams {
     float4* ray_log;            // BVH kernels, instrumented launch only (rt_debug_ray_log): every finished
     unsigned int* ray_log_n;    //   query as 3 float4 (o, prev | d | t, sg) appended at ray_log_n, up to
     unsigned int ray_log_cap;   //   ray_log_cap records
+    // rt_trace_paths, instrumented launch only (null on every other launch): one rt_debug_ray per
+    // bounce as kRecRows float4, record ((py * w + px) * spp + sample) * (recursion + 1) + bounce of the
+    // tile (row-major over the tile, like the other device buffers), and one float4 per sample when
+    // it ends: its colour as rt_render_tile_1spp returns it, and the number of its records
+    float4* rec_rays;
+    float4* rec_samples;
+    unsigned int rec_max;       // records in rec_rays (no store at or past it)
 };
+constexpr int kRecRows = 6;     // sizeof(rt_debug_ray) / 16
 
 // Trace-only kernel over a ray list (rt_debug_trace_rays): the wide BVH's speculative traversal
 // without the shading phase, for measuring what a wavefront split's traversal stage would take.
@@ -139,6 +147,11 @@ struct TileRec {
 // planar row-major accumulators (w*h) -> TileRec[w*h] in x*h + y order
 hipError_t launch_tile_host_layout(int w, int h, const double* d_sum, const uint32_t* d_samples,
                                   const uint32_t* d_misses, TileRec* d_out, hipStream_t stream);
+// rt_trace_paths: a launch's records (PathParams::rec_rays, kRecRows * (recursion + 1) float4 per
+// sample) and per-sample rows (rec_samples), row-major over the tile -> the caller's order
+// (x*h + y) * spp + k.
+hipError_t launch_trace_host_layout(int w, int h, int spp, int recursion, const float4* d_rays, const float4* d_samples,
+                                    float4* d_rays_out, float4* d_samples_out, hipStream_t stream);
 // partial (1 spp) -> the DoubleColor[w, h] values as fp32 rgb in x*h + y order, Placeholder(-1) on a miss.
 hipError_t launch_colors_1spp(const PathParams& p, float* d_out, hipStream_t stream);
 

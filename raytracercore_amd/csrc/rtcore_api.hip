@@ -225,6 +225,12 @@ struct rt_scene {
     unsigned int ray_log_cap = 0;
     int stats_blocks_per_cu = 1;
     DevBuf<unsigned long long> stats_buf;
+    // rt_trace_paths: its launch is the instrumented kernel's, with the counters aimed at a scratch
+    // block of its own (run_path), so stats_buf, an armed ray log and the scene-specialised kernel
+    // stay as they are
+    bool tracing = false;
+    DevBuf<unsigned long long> trace_stats;
+    DevBuf<float4> trace_rays, trace_samples, trace_out; // records and sample rows; both in the caller's order
     CameraD camd{};
     CameraF camf{};
     DevBuf<CameraF> camf_d;     // the path kernels read the camera from device memory (not kernel arguments)
@@ -1718,10 +1724,10 @@ int run_path(rt_scene* s, PathParams& p, unsigned long long* d_rays, hipStream_t
     p.partial = s->partial.p;
     p.counter = s->counter.p;
     p.rays = d_rays;
-    p.stats = s->stats_on ? s->stats_buf.p : nullptr;
+    p.stats = s->stats_on ? (s->tracing ? s->trace_stats.p : s->stats_buf.p) : nullptr;
     // rt_debug_ray_log arms the next instrumented BVH launch only, so a buffer the caller frees
-    // afterwards is never written
-    p.ray_log = (s->stats_on && s->variant >= 4) ? s->ray_log : nullptr;
+    // afterwards is never written (rt_trace_paths' launch is not one of them)
+    p.ray_log = (s->stats_on && !s->tracing && s->variant >= 4) ? s->ray_log : nullptr;
     p.ray_log_n = s->ray_log_n;
     p.ray_log_cap = s->ray_log_cap;
     if (p.ray_log) s->ray_log = nullptr;
@@ -1734,7 +1740,7 @@ int run_path(rt_scene* s, PathParams& p, unsigned long long* d_rays, hipStream_t
         HIP_TRY(s->stack_ovf.reserve((size_t)grid * 256 * kStackOverflow));
         p.stack_ovf = s->stack_ovf.p;
     }
-    const int jit = prepare_jit(s);
+    const int jit = s->tracing ? 0 : prepare_jit(s); // (rt_trace_paths: the generic kernel, the build's state untouched)
     int jit_grid = jit ? s->n_cu * s->jit.blocks_per_cu : 0;
     // A small brute-force launch runs fewer blocks per CU.  Its time is a lane's serial chain of
     // samples (each a few dependent iterations), and an iteration takes as long as the waves sharing
@@ -2847,6 +2853,75 @@ int rt_render_tile_1spp(rt_scene* s, int32_t x0, int32_t y0, int32_t w, int32_t 
     return copy_consume(s, s->colors32.p, npix, 3 * sizeof(float), [&](const unsigned char* st, size_t a, size_t b) {
         const float* f = reinterpret_cast<const float*>(st);
         for (size_t o = a; o < b; o++) out[o] = rt_color{(double)f[3 * o], (double)f[3 * o + 1], (double)f[3 * o + 2]};
+    });
+}
+
+// Raytracer.GetDebugTrace for the library's own samples: the instrumented instance of the scene's
+// path kernel (the record code is compiled into those instances only) over the tile, launched as a
+// render of the tile is (make_params: the same items), then the records in the caller's order.
+int rt_trace_paths(rt_scene* s, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t spp, uint64_t seed,
+                   uint64_t sample_base, rt_debug_ray* rays_out, int32_t* n_rays_out, rt_color* colors_out)
+{
+    static_assert(sizeof(rt_debug_ray) == kRecRows * sizeof(float4), "rt_debug_ray is kRecRows float4 rows");
+    if (!rays_out || spp <= 0 || w <= 0 || h <= 0) {
+        set_error("rt_trace_paths: bad argument (null rays_out, or spp, w or h <= 0)");
+        return RT_ERR_ARG;
+    }
+    // (a path has at least one record, so this holds whatever the scene's recursion is)
+    if ((uint64_t)w * (uint64_t)h * (uint64_t)spp > (uint64_t)RT_TRACE_MAX_RECORDS) {
+        set_error("rt_trace_paths: more than RT_TRACE_MAX_RECORDS records; trace fewer pixels or samples");
+        return RT_ERR_ARG;
+    }
+    int rc = check_tile(s, x0, y0, w, h);
+    if (rc != RT_OK) return rc;
+    const size_t n_samples = (size_t)w * h * spp;
+    const size_t per = (size_t)s->params.recursion + 1; // records of a sample (Raytracer.cs:257)
+    const size_t n_rec = n_samples * per;
+    if (s->params.recursion < 0 || n_rec > (size_t)RT_TRACE_MAX_RECORDS) {
+        set_error("rt_trace_paths: more than RT_TRACE_MAX_RECORDS records; trace fewer pixels or samples");
+        return RT_ERR_ARG;
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t rec_rows = n_rec * kRecRows;
+    HIP_TRY(s->trace_rays.reserve(rec_rows));
+    HIP_TRY(s->trace_samples.reserve(n_samples));
+    HIP_TRY(s->trace_out.reserve(rec_rows + n_samples));
+    HIP_TRY(s->trace_stats.reserve(RT_STATS_COUNT));
+    HIP_TRY(hipMemsetAsync(s->trace_rays.p, 0, rec_rows * sizeof(float4), s->stream));
+    HIP_TRY(hipMemsetAsync(s->trace_samples.p, 0, n_samples * sizeof(float4), s->stream));
+    HIP_TRY(hipMemsetAsync(s->trace_stats.p, 0, RT_STATS_COUNT * sizeof(unsigned long long), s->stream));
+    HIP_TRY(hipMemsetAsync(s->rays.p, 0, sizeof(unsigned long long), s->stream));
+    PathParams p = make_params(s, x0, y0, w, h, spp, seed, sample_base);
+    p.rec_rays = s->trace_rays.p;
+    p.rec_samples = s->trace_samples.p;
+    p.rec_max = (unsigned)n_rec;
+    // the instrumented instance for this one launch, as calibrate_grouping borrows it
+    const bool was_on = s->stats_on;
+    const int was_blocks = s->stats_blocks_per_cu;
+    s->stats_on = s->tracing = true;
+    s->stats_blocks_per_cu = path_blocks_per_cu(s->variant, path_dyn_lds(s->dev, s->variant), true, s->dev.n_vn > 0);
+    rc = run_path(s, p, s->rays.p, s->stream, false); // not one of rt_kernel_times' launches
+    s->stats_on = was_on;
+    s->tracing = false;
+    s->stats_blocks_per_cu = was_blocks;
+    if (rc != RT_OK) return rc;
+    float4* d_rays = s->trace_out.p;
+    float4* d_samples = s->trace_out.p + rec_rows;
+    HIP_TRY(launch_trace_host_layout(w, h, spp, s->params.recursion, s->trace_rays.p, s->trace_samples.p, d_rays, d_samples,
+                                     s->stream));
+    rc = end_op(s, s->stream);
+    if (rc != RT_OK) return rc;
+    rc = copy_consume(s, d_rays, n_rec, sizeof(rt_debug_ray), [&](const unsigned char* st, size_t a, size_t b) {
+        std::memcpy(rays_out + a, st + a * sizeof(rt_debug_ray), (b - a) * sizeof(rt_debug_ray));
+    });
+    if (rc != RT_OK) return rc;
+    // a sample's row: its fp32 colour (widened exactly, as rt_render_tile_1spp's) and its record count
+    return copy_consume(s, d_samples, n_samples, sizeof(float4), [&](const unsigned char* st, size_t a, size_t b) {
+        const float* f = reinterpret_cast<const float*>(st);
+        for (size_t o = a; o < b; o++) {
+            if (colors_out) colors_out[o] = rt_color{(double)f[4 * o], (double)f[4 * o + 1], (double)f[4 * o + 2]};
+            if (n_rays_out) std::memcpy(&n_rays_out[o], &f[4 * o + 3], sizeof(int32_t));
+        }
     });
 }
 

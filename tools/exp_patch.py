@@ -21,7 +21,7 @@ CSRC = os.path.join(ROOT, "raytracercore_amd", "csrc")
 
 TRACE_CALL = ("            trace_brute<CULL, STATS>(sc, groups, tests, rects, frames, boxes, xf, S.o, S.d, S.prev, b, cnt.tris,\n"
               "                                     cnt.sphs, cnt.nodes);\n")
-BOUNCE_CALL = "            bounce<VN>(L, S, sc, R, vnormals, tests, pq->prims_d, b);\n"
+BOUNCE_CALL = "            bounce<VN, false, false, STATS>(L, S, sc, R, vnormals, tests, pq->prims_d, b, *pq);\n"
 RAYS_LINE = "        wave_rays += (unsigned)__popcll(__ballot(L.live)); // one Scene.RayTrace per live lane\n"
 
 NODE_LOAD = '                    const Node4Q q = (ref & RT_HOT_BIT) ? lds_hot[ref & ~RT_HOT_BIT] : Node4Q(nodes4[ref]);\n'
