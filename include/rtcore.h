@@ -234,6 +234,19 @@ int rt_scene_check_bvh(rt_scene* scene);
    order's group count and its slot count.  Copies min(n_out, 10) values. */
 #define RT_LAYOUT_COUNT 10
 int rt_debug_brute_layout(const rt_prim* prims, int32_t n_prims, int32_t* out, int32_t n_out);
+/* Host only (no device needed): the order in which the path kernels' work dispensers deal the work
+   items of a launch over a w x h tile at spp samples per pixel, computed by the function the kernels
+   call.  chunks > 0: that many chunks per pixel (as RTCORE_PATH_CHUNKS), 0: the tuned count; pool
+   > 0: items per ticket (a multiple of 64; above 64 the grouped kernel's defaults), 0: the flat
+   kernel's; band > 0: the launch of the band set (band, band_stride, band_offset) of an h-row frame.
+   A work item is ((block << log2(n_chunks)) + chunk) * 64 + pixel of the 8x8 block.  out gets three
+   words per ticket -- item range, first item, items -- range by range, each range in the order its
+   dispenser deals; tickets past cap_words / 3 are counted but not stored.  info (optional) gets
+   {n_chunks, samples per chunk, items per full ticket, item ranges}.  Returns the number of
+   tickets or a negative rt_status.  RTCORE_ITEM_ORDER=0 in the environment gives the order that
+   also deals the empty chunk slots (A/B). */
+int rt_debug_item_order(int32_t w, int32_t h, int32_t spp, int32_t chunks, int32_t pool, int32_t band,
+                        int32_t band_stride, int32_t band_offset, uint32_t* out, int64_t cap_words, int32_t* info);
 /* Measurement of a wavefront split's traversal stage.  rt_debug_ray_log: while
    the next instrumented launch of a BVH kernel runs (rt_scene_set_stats; one launch only, then
    logging is off again), the kernel appends every finished query

@@ -203,6 +203,7 @@ def load_library(path: str = "") -> C.CDLL:
                                         C.c_double, C.c_void_p, C.c_void_p]),
         "rt_ref_bvh_export": (C.c_int, [P(rt_prim), C.c_int32, P(C.c_int32), P(C.c_double), P(C.c_int32),
                                         P(C.c_int32)]),
+        "rt_debug_item_order": (C.c_int, [C.c_int32] * 8 + [P(C.c_uint32), C.c_int64, P(C.c_int32)]),
         "rt_debug_ray_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
         "rt_debug_vn_rehit": (C.c_int, [P(C.c_double), P(C.c_double), P(C.c_double), C.c_int32, C.c_double,
                                         C.c_double, P(C.c_float), P(C.c_int32), P(C.c_double), P(C.c_double)]),
@@ -294,6 +295,26 @@ def brute_layout(prims: Sequence[rt_prim]) -> dict:
     out = (C.c_int32 * len(LAYOUT_NAMES))()
     _check(lib.rt_debug_brute_layout(arr, n, out, len(LAYOUT_NAMES)))
     return dict(zip(LAYOUT_NAMES, (int(v) for v in out)))
+
+
+def item_order(w: int, h: int, spp: int, chunks: int = 0, pool: int = 0,
+               bands: Optional[Tuple[int, int, int]] = None) -> Tuple[np.ndarray, dict]:
+    """rt_debug_item_order (host code, no GPU): the tickets the path kernels' dispensers deal for a
+    launch over a w x h tile (bands = (band, stride, offset): that band set of an h-row frame), as
+    an (n, 3) array of (item range, first item, items) in dealing order per range, and the launch's
+    n_chunks, chunk (samples per item), pool (items per full ticket) and n_split."""
+    lib = load_library()
+    b = bands or (0, 0, 0)
+    info = (C.c_int32 * 4)()
+    n = lib.rt_debug_item_order(w, h, spp, chunks, pool, b[0], b[1], b[2], None, 0, info)
+    if n < 0:
+        _check(n)
+    out = np.zeros((max(1, n), 3), np.uint32)
+    n2 = lib.rt_debug_item_order(w, h, spp, chunks, pool, b[0], b[1], b[2],
+                                 out.ctypes.data_as(C.POINTER(C.c_uint32)), 3 * n, info)
+    if n2 < 0:
+        _check(n2)
+    return out[:n], dict(zip(("n_chunks", "chunk", "pool", "n_split"), (int(v) for v in info)))
 
 
 def ref_bvh_export(prims: Sequence[rt_prim]) -> Tuple[np.ndarray, np.ndarray, int, int]:

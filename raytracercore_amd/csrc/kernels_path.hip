@@ -1167,33 +1167,58 @@ __device__ __forceinline__ void refill(Lane& L, Sample& S, const ParT& p, const 
     }
     const unsigned long long m = __ballot(need);
     if (m) {
-        const unsigned k = (unsigned)__popcll(m), avail = L.pool_end - L.pool_next;
-        unsigned fresh = 0;
-        if (k > avail) { // wave-uniform: one atomic refills the pool
+        unsigned k = (unsigned)__popcll(m);
+        const unsigned avail = L.pool_end - L.pool_next;
+        unsigned fresh = 0, fresh_len = (unsigned)p.pool;
+        // Brute-force kernels: once the pool is used up, the next ticket is drawn only when p.batch
+        // lanes wait for an item (64: the whole wave), or no lane of the wave has work left; the lanes
+        // that came early wait, and ask again in the next iteration.  A wave then opens a ticket's
+        // items together and its lanes stay in step: in most iterations no lane closes or opens an
+        // item or is alone in a shading branch, and those sections are branched over.  That saves
+        // more instructions than the waiting lanes lose (make_params has the figures).
+        bool draw = k > avail;
+        if (!NT && draw && k < (unsigned)p.batch && __ballot(L.active && !need) != 0ull) {
+            draw = false;
+            k = avail; // the pool's last items are still dealt
+        }
+        if (draw) { // wave-uniform: one atomic refills the pool
+            // lane 0 draws a ticket of a range: got = ticket | range << 28 (a launch has fewer than
+            // 2^26 tickets, run_path checks), range n_split when every range is spent; the ticket's
+            // items (ticket_items, rt_kernels.h) are then worked out once per wave, in scalar code.
+            // p.linear (ticket t of range g is the p.pool items from split_start[g] + t * pool): lane 0
+            // has the first item itself, its load of split_start[g] in flight with the atomic as before
+            // tickets (C4 draws one per two samples of a lane, and ticket_items' loads wait for it)
+            const bool linear = p.linear != 0;
+            unsigned got = linear ? total : (unsigned)p.n_split << 28;
             if (lane == 0) {
                 if (p.n_split <= 1) {
-                    fresh = atomicAdd(p.counter, (unsigned)p.pool);
+                    const unsigned f = atomicAdd(p.counter, 1u);
+                    if (f < p.split_tickets[0]) got = linear ? f * (unsigned)p.pool : f;
                 } else {
                     // the range of this workgroup's XCD first, then the others in turn (L.split_j: the
-                    // ranges this wave found spent); all spent -> total, which ends the lane
-                    fresh = total;
+                    // ranges this wave found spent)
                     const unsigned g0 = blockIdx.x & (unsigned)(p.n_split - 1);
                     for (; L.split_j < (unsigned)p.n_split; L.split_j++) {
                         const unsigned g = (g0 + L.split_j) & (unsigned)(p.n_split - 1);
-                        const unsigned f = atomicAdd(p.counter + kSplitStride * g, (unsigned)p.pool);
-                        if (f < p.split_start[g + 1] - p.split_start[g]) {
-                            fresh = p.split_start[g] + f;
+                        const unsigned f = atomicAdd(p.counter + kSplitStride * g, 1u);
+                        if (f < p.split_tickets[g]) {
+                            got = linear ? p.split_start[g] + f * (unsigned)p.pool : f | g << 28;
                             break;
                         }
                     }
                 }
             }
-            fresh = __builtin_amdgcn_readfirstlane(fresh);
+            got = __builtin_amdgcn_readfirstlane(got);
+            fresh = linear ? got : total; // all spent -> total, which ends the lane
+            if (!linear && (got >> 28) < (unsigned)p.n_split)
+                ticket_items(p, got >> 28, got & 0xFFFFFFFu, fresh, fresh_len);
         }
         if (need) {
             const unsigned r = NT ? lanes_below(m) : (unsigned)__popcll(m & ((1ull << lane) - 1ull));
             L.item = r < avail ? L.pool_next + r : fresh + (r - avail);
-            if (L.item >= total) {
+            if (r >= k) {
+                // (no ticket drawn for it yet: it asks again in the next iteration)
+            } else if (L.item >= total) {
                 L.active = false;
             } else {
                 int px, py, c, fx, fy;
@@ -1218,9 +1243,9 @@ __device__ __forceinline__ void refill(Lane& L, Sample& S, const ParT& p, const 
                 }
             }
         }
-        if (k > avail) {
+        if (draw) {
             L.pool_next = fresh + (k - avail);
-            L.pool_end = fresh + (unsigned)p.pool;
+            L.pool_end = fresh + fresh_len; // (a block's last ticket may be shorter than p.pool; never < 64)
         } else {
             L.pool_next += k;
         }

@@ -17,8 +17,8 @@ struct PathParams {
     float inv_band;             // fp32 1 / band
     int spp;                    // samples per pixel in this launch
     int chunk;                  // samples per work item (a lane owns one item at a time)
-    int n_chunks;               // ceil(spp / chunk) rounded up to a power of two (empty chunks are skipped)
-    int log2_chunks;
+    int n_chunks;               // ceil(spp / chunk) rounded up to a power of two: the chunk field of the item
+    int log2_chunks;            // index; the slots past the real chunks are never dealt (ticket_items below)
     int blocks_x;               // 8x8 pixel blocks per tile row
     int n_pad;                  // padded pixels per chunk (blocks * 64)
     int refill;                 // BVH kernel: waiting lanes (of 64) that trigger the shading phase
@@ -38,7 +38,25 @@ struct PathParams {
                                 // in item units, dealt first to the workgroups b with b % n_split == g (the
                                 // workgroups that share one XCD and its L2), then to any wave once theirs is spent
     unsigned split_start[9];
-    float4* partial;            // [block][chunk][64 pixels]: rgb sums, (samples | misses << 16)
+    // The dispensers count tickets, one per atomic (ticket_items below maps a ticket to its items).
+    // Per 8x8 block: tpb tickets of p.pool items over the block's first tpb * pool / 64 chunks, all
+    // full-length; then one ticket of tail_len items from chunk tail_first / 64 on, the rest of the
+    // block's real chunks with the short last chunk among them (tail_len 0: there is no such rest).
+    // A range deals the first kind for all its blocks (split_full[g] tickets), then the second.
+    unsigned tpb;               // tickets of the first kind per block
+    unsigned magic_tpb;         // ceil(2^32 / tpb): t / tpb = umulhi(t, magic_tpb) for every ticket of the
+                                // launch (make_params checks); 0 for tpb <= 1
+    unsigned tail_first;        // first item of a block's last ticket, relative to the block's first item
+    unsigned tail_len;          // its items (64 x its chunks, at most p.pool)
+    int linear;                 // 1: every slot is dealt and none is short (tail_len 0, tpb * pool = 64 * n_chunks),
+                                // so ticket t of range g is the p.pool items from split_start[g] + t * pool, which
+                                // the kernels then take without ticket_items
+    int batch;                  // brute-force kernels: lanes that must wait for an item before a wave whose pool
+                                // is used up draws its next ticket (0: no waiting; 64: the wave opens a ticket's
+                                // items together)
+    unsigned split_full[8];     // range g: tickets of the first kind
+    unsigned split_tickets[8];  // range g: tickets in all (the dispenser value at which it is spent)
+    float4* partial;           // [block][chunk][64 pixels]: rgb sums, (samples | misses << 16)
     unsigned long long* rays;   // Scene.RayTrace-equivalents (added to)
     int* stack_ovf;             // BVH kernels: traversal-stack overflow, RT_STACK_OVF entries per lane of the grid
     unsigned long long* stats;  // optional [7]: node visits, triangle tests, sphere tests (per lane);
@@ -71,6 +89,27 @@ struct PathParams {
     unsigned int rec_max;       // records in rec_rays (no store at or past it)
 };
 constexpr int kRecRows = 6;     // sizeof(rt_debug_ray) / 16
+
+// Ticket t of item range g -> the items it covers, [first, first + len) in the item numbering
+// ((block << log2_chunks) + chunk) * 64 + pixel: chunks of one 8x8 block next to each other, none
+// past the launch's real chunks.  t < p.split_tickets[g].  The kernels' refill and the host check
+// (rt_debug_item_order) both call this; every operand is wave-uniform in the kernels.
+template <class ParT>
+__host__ __device__ inline void ticket_items(const ParT& p, unsigned g, unsigned t, unsigned& first, unsigned& len)
+{
+    const unsigned full = p.split_full[g];
+    unsigned blk, off;
+    if (t < full) {
+        blk = p.magic_tpb ? (unsigned)(((unsigned long long)t * p.magic_tpb) >> 32) : t;
+        off = (t - blk * p.tpb) * (unsigned)p.pool;
+        len = (unsigned)p.pool;
+    } else {
+        blk = t - full;
+        off = p.tail_first;
+        len = p.tail_len;
+    }
+    first = p.split_start[g] + (blk << (p.log2_chunks + 6)) + off;
+}
 
 // Trace-only kernel over a ray list (rt_debug_trace_rays): the wide BVH's speculative traversal
 // without the shading phase, for measuring what a wavefront split's traversal stage would take.

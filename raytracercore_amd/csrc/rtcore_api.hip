@@ -1454,6 +1454,7 @@ int resolve_traversal(rt_scene* s)
 
 PathParams make_params(rt_scene* s, int x0, int y0, int w, int h, int spp, uint64_t seed, uint64_t base,
                        double chunk_npix = 0.0);
+void set_item_order(PathParams& p);
 int run_path(rt_scene* s, PathParams& p, unsigned long long* d_rays, hipStream_t stream, bool timed = true);
 int prepare_jit(rt_scene* s);
 int end_op(rt_scene* s, hipStream_t stream);
@@ -1487,6 +1488,8 @@ int calibrate_grouping(rt_scene* s)
     s->stats_blocks_per_cu = s->blocks_per_cu;
     PathParams p = make_params(s, x0, y0, w, h, 2, 0x5EEDull, 0);
     p.pool = 64; // one chunk per pool: the counts must not depend on the pool size
+    set_item_order(p);
+    p.batch = 0; // nor on which lanes share a wave: the probe deals its items as it always has
     int rc = run_path(s, p, s->rays.p, s->stream, false); // an internal probe: not in rt_kernel_times
     if (rc == RT_OK) rc = end_op(s, s->stream);
     s->stats_on = was_on;
@@ -1507,11 +1510,62 @@ int calibrate_grouping(rt_scene* s)
     return resolve_traversal(s);
 }
 
+// The order in which the dispensers deal p's work items (PathParams::tpb .. split_tickets, ticket_items
+// in rt_kernels.h), from p's chunks, pool and ranges.  Only which wave takes which item depends on it.
+// A pixel's real chunks are the first `used` of the n_chunks slots of the item index; the last of
+// them is short when chunk does not divide spp.  Per range, every block's full-length chunks are
+// dealt first, p.pool / 64 of them per ticket, then one shorter ticket per block with what is left:
+// the full chunks that do not fill a ticket and the short chunk.  The launch then ends on its
+// shortest items, and no ticket names a chunk slot past `used`.  A ticket is always adjacent chunks
+// of one block, whatever the chunks and the pool.  With every slot real and no short chunk (C1, C4
+// at 64 spp) the tickets are p.pool items each in index order: the sequence before tickets were
+// introduced.  RTCORE_ITEM_ORDER=0 deals all n_chunks slots that way (A/B), and so does a launch
+// with so many tickets that the division below would not be exact.
+// Measured, 1080p, kernel ms, one call each (profiles/r07): without the waves' batched item opening
+// (RTCORE_ITEM_BATCH=0, below) this order is the slower one, C2 16.64 -> 16.78, C3 20.80 -> 21.51:
+// a wave that drew a ticket of empty slots had its waiting lanes open the next ticket together, a
+// little of what the batching now does outright.  With the batching the empty slots only cost:
+// C2 16.07 -> 16.01, C3 20.19 -> 20.10 with this order.
+void set_item_order(PathParams& p)
+{
+    const char* e = getenv("RTCORE_ITEM_ORDER");
+    bool dense = !(e && e[0] == '0');
+    const unsigned slots = (unsigned)p.pool / 64u; // chunks per ticket: a power of two <= n_chunks
+    const unsigned used = (unsigned)((p.spp + p.chunk - 1) / p.chunk);
+    const unsigned n_blocks = (unsigned)(p.n_pad / 64);
+    for (;; dense = false) {
+        const unsigned n_real = dense ? used : (unsigned)p.n_chunks;
+        const unsigned n_full = dense && p.spp % p.chunk != 0 ? used - 1 : n_real;
+        p.tpb = n_full / slots;
+        p.tail_first = p.tpb * (unsigned)p.pool;
+        p.tail_len = (n_real - p.tpb * slots) * 64u; // <= pool: at most slots - 1 full chunks and the short one
+        // t / tpb by multiply-high, as magic_bx: exact for every t with t * (M * tpb - 2^32) < 2^32,
+        // M = ceil(2^32 / tpb); t < n_blocks * tpb.  (A power of two has M * tpb = 2^32, so the
+        // RTCORE_ITEM_ORDER=0 form always passes.)
+        p.magic_tpb = 0;
+        if (p.tpb <= 1) break;
+        const uint64_t M = ((1ull << 32) + p.tpb - 1) / p.tpb;
+        const uint64_t err = M * p.tpb - (1ull << 32);
+        if (M < (1ull << 32) && (uint64_t)n_blocks * p.tpb * err < (1ull << 32)) {
+            p.magic_tpb = (unsigned)M;
+            break;
+        }
+    }
+    p.linear = p.tail_len == 0 && p.tpb * slots == (unsigned)p.n_chunks;
+    for (int g = 0; g < kMaxSplit; g++) {
+        const unsigned b = g < p.n_split ? (p.split_start[g + 1] - p.split_start[g]) >> (p.log2_chunks + 6) : 0u;
+        p.split_full[g] = b * p.tpb;
+        p.split_tickets[g] = p.split_full[g] + (p.tail_len ? b : 0u);
+    }
+}
+
 // chunk_npix (default w * h): the pixel count the chunks per pixel are chosen for.  A column band of a
 // tile passes the whole tile's, so that every pixel's samples fall into the same chunks (and its
 // fp64 sum into the same order) as in one launch over the tile.
-PathParams make_params(rt_scene* s, int x0, int y0, int w, int h, int spp, uint64_t seed, uint64_t base,
-                       double chunk_npix)
+// kernel: 0 flat, 1 grouped brute force, 2 / 3 the BVH kernels; chunks_over / pool_over > 0 (the host
+// check, rt_debug_item_order): chunks per pixel and items per ticket instead of the tuned ones.
+PathParams make_params_for(int kernel, int chunks_over, int pool_over, int x0, int y0, int w, int h, int spp,
+                           uint64_t seed, uint64_t base, double chunk_npix)
 {
     PathParams p{};
     p.x0 = x0;
@@ -1533,8 +1587,9 @@ PathParams make_params(rt_scene* s, int x0, int y0, int w, int h, int spp, uint6
     // profiles/r06/chunk_sweep3.log, ms per step): C2 16 / 20 / 24 / 28 / 32 chunks 17.12 / 16.86 /
     // 16.84-16.86 / 16.85-16.87 / 16.98; C3 22.16-22.29 / 21.49-21.50 / 21.42-21.43 / 21.43-21.46 /
     // 21.86-21.93.  Fewer, longer items (and fewer partials to fold) until the launch tail grows;
-    // 24 chunks leave 8 of the 32 power-of-two chunk slots empty, items the refill skips.
-    const int base_chunks = (s->variant >> 1) >= 2 ? 64 : 24;
+    // 24 chunks leave 8 of the 32 power-of-two chunk slots empty: that sweep still dealt them as items
+    // whose lanes sat an iteration out; set_item_order no longer deals them (a re-sweep is due).
+    const int base_chunks = kernel >= 2 ? 64 : 24;
     int chunks = base_chunks;
     const double npix = chunk_npix > 0.0 ? chunk_npix : (double)w * (double)h;
     if (npix > 0 && npix < 2073600.0)
@@ -1545,6 +1600,7 @@ PathParams make_params(rt_scene* s, int x0, int y0, int w, int h, int spp, uint6
     else if (npix > 2073600.0)
         chunks = (int)std::max(base_chunks / 4.0, std::ceil(base_chunks * 2073600.0 / npix));
     if (const char* e = getenv("RTCORE_PATH_CHUNKS")) chunks = std::max(1, atoi(e));
+    if (chunks_over > 0) chunks = chunks_over;
     p.chunk = std::max(1, std::min(64, (spp + chunks - 1) / chunks));
     const int used = (spp + p.chunk - 1) / p.chunk;
     p.log2_chunks = 0;
@@ -1568,14 +1624,27 @@ PathParams make_params(rt_scene* s, int x0, int y0, int w, int h, int spp, uint6
     // With the XCD-local dispensers (8 words instead of one) smaller pools pay again (round 3, pool
     // multiples 1 / 2 / 4 / 8): flat brute force C2 19.54-19.57 / 19.63-19.69 / 20.05 ms, the BVH
     // kernels C4 44.54-44.57 / 44.25-44.28 / 45.0-45.2 / 46.8 ms; grouped C3 27.81 / - / 27.58-27.64.
-    const int kernel = s->variant >> 1;
     // Round 6, with the 24-chunk items (longer items, so fewer per atomic; profiles/r06/pool_sweep2.log):
     // grouped C3 pool multiples 2 / 4 / 8: 19.93 / 20.36-20.38 / 21.51-21.57 ms; flat C2 1 / 2: 16.27-16.28 /
     // 16.42-16.49 ms.
     int pool_mul = kernel == 0 ? 1 : 2;
     if (const char* e = getenv("RTCORE_POOL_MUL")) pool_mul = std::max(1, std::min(64, atoi(e)));
+    if (pool_over > 0) pool_mul = std::max(1, std::min(64, pool_over / 64));
     p.pool = 64;
     while (p.pool < 64 * pool_mul && p.pool < 64 * p.n_chunks) p.pool *= 2;
+    // Brute-force kernels: a wave whose pool is used up draws its next ticket only when all 64 lanes
+    // wait for an item (refill, kernels_path.hip), so a ticket's items open together and the lanes
+    // stay in step; which lane renders an item never changes what it computes.  The iterations in
+    // which no lane closes or opens an item branch over those sections, and more lanes share a
+    // shading branch.  PMC per launch before this (profiles/r07): where the lanes drifted further
+    // apart the same lane work took more wave instructions (C3 +3.75 % VALU instructions at +1.6 %
+    // lane cycles).  Kernel ms, 1080p, one call, RTCORE_ITEM_BATCH = 0 / 8 / 16 / 32 / 48 / 64 lanes:
+    // C2 16.64 / 16.60 / 16.61 / 16.48 / 16.22 / 16.08, C3 20.87 / 20.70 / 20.62 / 20.45 / 20.25 /
+    // 20.15.  Short items gain too (bounce.txt 1080p at 24 / 48 / 96 / 192 spp, 1 / 2 / 4 / 8 samples
+    // per item: 2.57 -> 2.53, 3.87 -> 3.73, 6.48 -> 6.08, 12.69 -> 11.96; C1 0.156 -> 0.147).
+    // Holding lanes back in the middle of a pool as well (until 4 .. 32 wait) lost 5-19 %.
+    p.batch = kernel < 2 ? 64 : 0;
+    if (const char* e = getenv("RTCORE_ITEM_BATCH")) p.batch = std::max(0, std::min(64, atoi(e)));
     // BVH kernels: the shading phase runs once 28 lanes wait; a leaf step once 12 lanes are blocked
     // on a pending leaf.  Round 5, C4 with the walls as outer records (profiles/r05/c4_outer_sweep.log):
     // refill 24 / 28 / 32 at spec 16: 44.0 / 43.6 / 43.6 ms; spec 12 / 16 / 20 at refill 24: 43.8 /
@@ -1597,10 +1666,17 @@ PathParams make_params(rt_scene* s, int x0, int y0, int w, int h, int spp, uint6
     if (want > 1 && n_blocks >= 4 * kMaxSplit) p.n_split = kMaxSplit;
     for (int g = 0; g <= p.n_split; g++)
         p.split_start[g] = (unsigned)((int64_t)n_blocks * g / p.n_split) * (unsigned)(p.n_chunks * 64);
+    set_item_order(p);
     p.seed = seed;
     p.seed_key = rt_rng_seed_key(seed);
     p.sample_base = base;
     return p;
+}
+
+PathParams make_params(rt_scene* s, int x0, int y0, int w, int h, int spp, uint64_t seed, uint64_t base,
+                       double chunk_npix)
+{
+    return make_params_for(s->variant >> 1, 0, 0, x0, y0, w, h, spp, seed, base, chunk_npix);
 }
 
 // Band-set launch: tile row r is frame row ((r / band) * stride + offset) * band + r % band; the
@@ -1715,7 +1791,12 @@ int prepare_jit(rt_scene* s)
 int run_path(rt_scene* s, PathParams& p, unsigned long long* d_rays, hipStream_t stream, bool timed)
 {
     const size_t need = (size_t)p.n_chunks * (size_t)p.n_pad;
-    if (need > 0xF0000000ull) { // 32-bit work-item counter (plus the pools' overshoot)
+    // 32-bit item indices: the end-of-work sentinel is `need` itself and a pool's end is at most
+    // p.pool past it.  The dispensers count tickets, one per >= 64 items, and every wave draws once
+    // more from each range it finds spent: with `need` in range a dispenser stays below 2^26 + waves.
+    uint64_t tickets = 0;
+    for (int g = 0; g < p.n_split; g++) tickets += p.split_tickets[g];
+    if (need > 0xF0000000ull || tickets > need / 64) {
         set_error("tile x spp too large for one launch; split the tile");
         return RT_ERR_ARG;
     }
@@ -3117,6 +3198,49 @@ int render_band_set(rt_scene* s, int band, int stride, int offset, int rows, siz
 } // namespace
 
 extern "C" {
+
+// Host only: the launch record of such a render (make_params_for, set_band) and every ticket of its
+// dispensers through ticket_items, the function the kernels' refill calls.
+int rt_debug_item_order(int32_t w, int32_t h, int32_t spp, int32_t chunks, int32_t pool, int32_t band,
+                        int32_t band_stride, int32_t band_offset, uint32_t* out, int64_t cap_words, int32_t* info)
+{
+    const bool banded = band > 0;
+    if (w <= 0 || h <= 0 || spp <= 0 || chunks < 0 || pool < 0 || pool % 64 != 0 || cap_words < 0 ||
+        (cap_words > 0 && !out) || (banded && (band_stride <= 0 || band_offset < 0 || band_offset >= band_stride))) {
+        set_error("rt_debug_item_order: bad argument");
+        return RT_ERR_ARG;
+    }
+    const int rows = banded ? band_set_rows(h, band, band_stride, band_offset) : h;
+    if (rows <= 0) return 0;
+    PathParams p = make_params_for(pool > 64 ? 1 : 0, chunks, pool, 0, 0, w, rows, spp, 0, 0, 0.0);
+    if (banded) set_band(p, band, band_stride, band_offset);
+    if ((uint64_t)p.n_chunks * (uint64_t)p.n_pad > 0xF0000000ull) {
+        set_error("rt_debug_item_order: tile x spp too large for one launch");
+        return RT_ERR_ARG;
+    }
+    if (info) {
+        info[0] = p.n_chunks;
+        info[1] = p.chunk;
+        info[2] = p.pool;
+        info[3] = p.n_split;
+    }
+    int64_t n = 0;
+    for (int g = 0; g < p.n_split; g++)
+        for (unsigned t = 0; t < p.split_tickets[g]; t++, n++) {
+            unsigned first = 0, len = 0;
+            ticket_items(p, (unsigned)g, t, first, len);
+            if (3 * (n + 1) <= cap_words) {
+                out[3 * n] = (uint32_t)g;
+                out[3 * n + 1] = first;
+                out[3 * n + 2] = len;
+            }
+        }
+    if (n > INT32_MAX) {
+        set_error("rt_debug_item_order: too many tickets");
+        return RT_ERR_ARG;
+    }
+    return (int)n;
+}
 
 int rt_render_bands(rt_scene* s, int32_t band, int32_t band_stride, int32_t band_offset, int32_t spp, uint64_t seed,
                     uint64_t sample_base, rt_color* sum_rgb, uint32_t* samples, uint32_t* misses, uint64_t* rays_out)
