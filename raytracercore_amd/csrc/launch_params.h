@@ -1,0 +1,27 @@
+// launch_params.h -- host-side planning of a path-tracing launch (launch_params.cpp): the work
+// decomposition of a tile (PathParams), the order its items are dealt in, and the row bands of the
+// multi-GPU frame.  No HIP calls.
+#pragma once
+#include "rt_kernels.h"
+
+namespace rtc {
+
+// kernel: 0 flat, 1 grouped brute force, 2 / 3 the BVH kernels; chunks_over / pool_over > 0 (the host
+// check, rt_debug_item_order): chunks per pixel and items per ticket instead of the tuned ones.
+PathParams make_params_for(int kernel, int chunks_over, int pool_over, int x0, int y0, int w, int h, int spp,
+                           uint64_t seed, uint64_t base, double chunk_npix);
+// The order in which the dispensers deal p's work items, from p's chunks, pool and ranges.
+void set_item_order(PathParams& p);
+// Band-set launch: tile row r is frame row ((r / band) * stride + offset) * band + r % band.
+void set_band(PathParams& p, int band, int stride, int offset);
+// Every ticket of p's dispensers through ticket_items, as (range, first item, items) triples into
+// out while they fit in cap_words; returns the number of tickets.
+int64_t list_tickets(const PathParams& p, uint32_t* out, int64_t cap_words);
+
+// A band set (band, stride, offset) is frame rows {y : (y / band) % stride == offset}.
+int band_set_rows(int H, int band, int stride, int offset);
+int band_slot_rows(int H, int band, int stride); // largest band set of the split
+void scatter_band_set(const unsigned char* slot, size_t plane, int W, int H, int band, int stride, int offset,
+                      rt_color* sum_rgb, uint32_t* samples, uint32_t* misses);
+
+} // namespace rtc

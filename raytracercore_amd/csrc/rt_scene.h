@@ -1,0 +1,277 @@
+// rt_scene.h -- the scene object behind the C ABI and what the API's translation units share
+// (rtcore_api.hip, scene_upload.hip, api_frame.hip, api_debug.hip).
+#pragma once
+#include <algorithm>
+#include <array>
+#include <functional>
+#include <string>
+#include <vector>
+
+#include "host_scene.h"
+#include "launch_params.h"
+#include "rt_jit.h"
+#include "rt_kernels.h"
+#include "scene_records.h"
+
+using namespace rtc;
+
+#define HIP_TRY(expr)                                                                                  \
+    do {                                                                                                \
+        hipError_t e_ = (expr);                                                                         \
+        if (e_ != hipSuccess) {                                                                         \
+            set_error(std::string(#expr) + ": " + hipGetErrorString(e_));                               \
+            return e_ == hipErrorOutOfMemory ? RT_ERR_OOM : RT_ERR_HIP;                                 \
+        }                                                                                               \
+    } while (0)
+
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t n = 0;
+    ~DevBuf() { release(); }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        n = 0;
+    }
+    hipError_t reserve(size_t count)
+    {
+        if (count <= n) return hipSuccess;
+        release();
+        hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
+        if (e == hipSuccess) n = count;
+        return e;
+    }
+    void adopt(T* q, size_t count) // take ownership of a hipMalloc'd array
+    {
+        release();
+        p = q;
+        n = q ? count : 0;
+    }
+    hipError_t upload(const std::vector<T>& v)
+    {
+        hipError_t e = reserve(v.size());
+        if (e != hipSuccess || v.empty()) return e;
+        return hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+    }
+};
+
+// Pinned host staging (hipHostMalloc) for the host-buffer entry points: device -> host copies at
+// DMA rate into it, then a multi-threaded pass into the caller's (pageable) arrays.
+template <class T>
+struct HostBuf {
+    T* p = nullptr;
+    size_t n = 0;
+    ~HostBuf() { release(); }
+    void release()
+    {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        n = 0;
+    }
+    hipError_t reserve(size_t count)
+    {
+        if (count <= n) return hipSuccess;
+        release();
+        hipError_t e = hipHostMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T), hipHostMallocDefault);
+        if (e == hipSuccess) n = count;
+        return e;
+    }
+};
+
+// The device arrays of one brute-force slot order (BruteOrder).
+struct BruteDev {
+    DevBuf<PrimF> prims;
+    DevBuf<TestRec> tests;
+    DevBuf<RectRec> rects;
+    DevBuf<FrameRec> frames; // FrameRecs and BoxRecs
+    DevBuf<GroupRec> groups;
+    hipError_t upload(const BruteOrder& o)
+    {
+        hipError_t e = prims.upload(o.prims);
+        if (e == hipSuccess) e = tests.upload(o.tests);
+        if (e == hipSuccess) e = rects.upload(o.rects);
+        if (e == hipSuccess) e = frames.upload(o.frames);
+        if (e == hipSuccess) e = groups.upload(o.groups);
+        return e;
+    }
+};
+
+struct rt_scene {
+    int device = 0;
+    int n_cu = 256;
+    rt_scene_params params{};
+    std::vector<HostPrim> host;
+    int traversal = RT_TRAVERSAL_AUTO, resolved = RT_TRAVERSAL_BRUTE;
+    int variant = 0;
+    int blocks_per_cu = 1;
+    RefBvh ref;
+    bool ref_built = false;
+    SahBvh sah;   // host-built trees (empty when the GPU builder made them)
+    Bvh4 bvh4;
+    struct {
+        int builder = RT_BVH_BUILDER_HOST; // the one that ran
+        int n_nodes2 = 0, n_nodes4 = 0, root2 = 0, root4 = 0, depth2 = 0, stack4 = 0, rounds = 0;
+        int leaves4 = 0, compact4 = 0; // leaf references of the wide tree, compact ones (kLeafCompact)
+        float gpu_ms = 0.0f;
+    } bvh;
+    DevBuf<int32_t> order_d;      // GPU builder: primitive IDs in leaf order, planes appended
+    // Outer records (host builder, large scenes): the axis-aligned rectangles left out of the tree
+    // and tested as one brute-force group (world rects and closed boxes) when a query ends
+    std::vector<char> bvh_outer;  // per primitive: 1 = outside the tree (empty: none)
+    double ms_prepare = 0, ms_bvh = 0, ms_upload = 0;
+    BruteLayout layout;           // the flat brute-force order's decomposition (build statistics)
+    int group_max = 0;            // primitives per group of the grouped order
+    DevScene dev{};
+    // the flat and the grouped order; the BVH order: the tree's and the planes' prims and tests (built
+    // by either builder, upload_scene) and the outer group's rects, BoxRecs (frames) and GroupRec
+    BruteDev flat_d, grouped_d, bvh_d;
+    DevBuf<float4> rows_bvh; // bvh_d.tests without the meta rows (compact leaves)
+    std::vector<GroupRec> groups_gr_host; // in build order; uploaded nearest-first per camera
+    // host copies of the brute-force records (the scene-specialised kernels, rt_jit.h)
+    struct BruteHost {
+        std::vector<GroupRec> groups; // the grouped order: in the current camera's upload order
+        std::vector<RectRec> rects;
+        std::vector<FrameRec> frames;
+        std::vector<TestRec> tests;
+    } flat_h, grouped_h;
+    std::vector<XformF> xf_h;
+    unsigned jit_gen = 0; // bumped by every camera change (and with it the grouped order's group order)
+    struct {
+        int variant = -1;          // the variant and group order the function was built for
+        unsigned gen = 0;
+        hipFunction_t fn = nullptr;
+        int blocks_per_cu = 0;
+        int status = 0;            // 1 built, 0 not used (off, or a BVH / staged-less variant), -1 failed
+        double compile_ms = 0;
+        bool from_cache = false;
+        std::string error;
+        std::string header;        // the generated scene header fn was built from
+    } jit;
+    double grouped_measured = 0; // calibrated brute-force cost ratio flat / grouped (AUTO picks grouped above 1.25)
+    DevBuf<NodeF> nodes;
+    DevBuf<Node4Q> nodes4;
+    DevBuf<Node4Q> hot4;        // top of the wide tree, breadth-first, staged in LDS by the wide kernel
+    DevBuf<XformF> xf;
+    DevBuf<MatF> mats;
+    DevBuf<float4> vnormals;
+    DevBuf<PrimD> prims_d;
+    DevBuf<XformD> xf_d;
+    DevBuf<RefNode> ref_nodes;
+    // work buffers
+    DevBuf<unsigned int> counter;
+    DevBuf<rt_key2> pkeys;       // pixel-key table of the brute-force kernels (PathParams::pkeys)
+    bool pkeys_valid = false;
+    uint64_t pkeys_seed = 0;
+    DevBuf<int> stack_ovf;
+    DevBuf<unsigned long long> rays;
+    DevBuf<float4> partial;
+    DevBuf<double> sum, colors;
+    DevBuf<float> colors32;        // rt_render_tile_1spp: one pass as fp32 rgb in the caller's order
+    HostBuf<unsigned char> stage;  // host-buffer entry points (rt_render_tile, rt_render_tile_1spp)
+    HostBuf<unsigned long long> rays_h;
+    static constexpr int kCopyChunks = 8; // chunked device -> host copies (copy_consume)
+    std::array<hipEvent_t, kCopyChunks> copy_ev{};
+    // rt_render_tile: band k's records are copied on copy_stream once band_ev[k] (recorded on the
+    // scene's stream after the band's layout kernel) has fired, so band k + 1 renders meanwhile
+    hipStream_t copy_stream = nullptr;
+    std::array<hipEvent_t, kCopyChunks> band_ev{};
+    DevBuf<uint32_t> samples, misses;
+    DevBuf<int32_t> ids;
+    bool stats_on = false;      // launch the instrumented kernel (rt_scene_set_stats)
+    float4* ray_log = nullptr;  // rt_debug_ray_log (instrumented BVH launches)
+    unsigned int* ray_log_n = nullptr;
+    unsigned int ray_log_cap = 0;
+    int stats_blocks_per_cu = 1;
+    DevBuf<unsigned long long> stats_buf;
+    // rt_trace_paths: its launch is the instrumented kernel's, with the counters aimed at a scratch
+    // block of its own (run_path), so stats_buf, an armed ray log and the scene-specialised kernel
+    // stay as they are
+    bool tracing = false;
+    DevBuf<unsigned long long> trace_stats;
+    DevBuf<float4> trace_rays, trace_samples, trace_out; // records and sample rows; both in the caller's order
+    CameraD camd{};
+    CameraF camf{};
+    DevBuf<CameraF> camf_d;     // the path kernels read the camera from device memory (not kernel arguments)
+    // ... and their launch parameters, from a ring of device slots filled from pinned host slots.
+    // A slot is rewritten kParamRing launches later; its event (recorded after the slot's upload)
+    // is waited on first, so a caller queueing more launches than that without a sync still
+    // hands every launch its own parameters.
+    static constexpr int kParamRing = 256;
+    DevBuf<PathParams> params_d;
+    PathParams* params_h = nullptr;
+    std::array<hipEvent_t, kParamRing> slot_ev{};
+    unsigned params_next = 0;
+    bool has_camera = false;
+    bool flat_overflow = false; // the flat brute-force order exceeds GroupRec's counts (BruteOrder::overflow)
+    hipStream_t stream = nullptr;
+    // Timing of the path kernels: the i-th launch records the event pair i % kTimeRing, so a caller
+    // can queue up to that many launches before it reads their durations (rt_kernel_times).
+    static constexpr int kTimeRing = 64;
+    std::array<hipEvent_t, kTimeRing> t_start{}, t_end{};
+    uint64_t launches = 0;
+    // Launches share per-scene scratch (partials, work counter, stack overflow area).  The end of
+    // the last render operation is recorded here; an operation on a different stream waits for it.
+    hipEvent_t done_ev = nullptr;
+    hipStream_t last_stream = nullptr;
+    bool any_op = false;
+    uint64_t device_bytes = 0;
+
+    ~rt_scene()
+    {
+        if (jit.fn) jit_release(device, jit.fn); // (the stream is synchronised by rt_scene_destroy)
+        if (params_h) (void)hipHostFree(params_h);
+        for (hipEvent_t e : slot_ev)
+            if (e) (void)hipEventDestroy(e);
+        if (done_ev) (void)hipEventDestroy(done_ev);
+        for (hipEvent_t e : copy_ev)
+            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : band_ev)
+            if (e) (void)hipEventDestroy(e);
+        if (copy_stream) {
+            (void)hipStreamSynchronize(copy_stream);
+            (void)hipStreamDestroy(copy_stream);
+        }
+        for (int i = 0; i < kTimeRing; i++) {
+            if (t_start[i]) (void)hipEventDestroy(t_start[i]);
+            if (t_end[i]) (void)hipEventDestroy(t_end[i]);
+        }
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+// The host-buffer entry points' device -> host step.  queue_copy queues records [a, b) of d_src (after
+// the work already on the scene's stream) into the same offsets of pinned staging, in k chunks whose
+// arrivals are recorded by events; consume_copies then runs consume(stage, a, b) on the host pool
+// for each chunk's items as soon as that chunk has landed, so the host pass over one chunk overlaps
+// the DMA of the next (and whatever device work was queued after it).  Staging must be reserved
+// for every queued record first.
+struct CopyPlan {
+    size_t a[rt_scene::kCopyChunks], b[rt_scene::kCopyChunks];
+    int n = 0;
+};
+
+namespace rtc {
+
+// scene_upload.hip
+int builder_for(int n_bvh);  // the BVH builder (RT_BVH_BUILDER_HOST / _GPU) a scene of n_bvh non-plane primitives gets
+int group_max_default();     // primitives per group of the grouped order, by the process's rt_set_jit state
+int build_bvhs(rt_scene* s);
+int upload_scene(rt_scene* s);
+int ensure_ref_bvh(rt_scene* s);
+int resolve_traversal(rt_scene* s);
+int calibrate_grouping(rt_scene* s);
+int prepare_jit(rt_scene* s);
+int check_tile(rt_scene* s, int x0, int y0, int w, int h);
+PathParams make_params(rt_scene* s, int x0, int y0, int w, int h, int spp, uint64_t seed, uint64_t base,
+                       double chunk_npix = 0.0);
+int run_path(rt_scene* s, PathParams& p, unsigned long long* d_rays, hipStream_t stream, bool timed = true);
+int end_op(rt_scene* s, hipStream_t stream);
+int queue_copy(rt_scene* s, CopyPlan& plan, const void* d_src, size_t a, size_t b, size_t rec_bytes, int k,
+               hipStream_t stream);
+int consume_copies(rt_scene* s, const CopyPlan& plan, const std::function<void(const unsigned char*, size_t, size_t)>& consume);
+int copy_consume(rt_scene* s, const void* d_src, size_t n_items, size_t rec_bytes,
+                 const std::function<void(const unsigned char*, size_t, size_t)>& consume);
+
+} // namespace rtc

@@ -6,8 +6,10 @@
 //   * have, for every wide node, dequantised child planes (origin + q * 2^e, in exact
 //     arithmetic) that contain every primitive box below that child;
 //   * never need more traversal-stack entries than the computed stack_need.
-// Prints "ok <n_prims> <bvh2 nodes> <wide nodes> <stack_need>" per collapse or the first failure;
-// with --ref also builds the reference BVH and the cameras (the host inputs of the exact pass).
+// Prints "ok <n_prims> <bvh2 nodes> <wide nodes> <stack_need>" per collapse or the first failure.
+// Then the brute-force records (make_host_records): every non-plane primitive has a slot in the flat
+// order and, where there is one, in the grouped order, and every rectangle record names a slot of
+// its order; prints "records ..." with the counts.  With --ref also builds the reference BVH and the cameras (the host inputs of the exact pass).
 // `make bvh_check_asan` builds it with AddressSanitizer and UndefinedBehaviorSanitizer on the host
 // sources (tests/test_host.py runs both builds).
 #include <chrono>
@@ -20,6 +22,7 @@
 #include <vector>
 
 #include "host_scene.h"
+#include "scene_records.h"
 
 using namespace rtc;
 
@@ -157,6 +160,35 @@ int main(int argc, char** argv)
         }
         std::printf("%s %zu %zu %zu %d\n", mode ? "" : "ok", H.size(), b2.nodes.size(), b4.nodes.size(), b4.stack_need);
     }
+    // the brute-force records (scene_records.cpp), over a grouping tree of their own
+    const HostRecords rec = make_host_records(H, grouping_max_leaf(GroupingTree::LayoutReport, (int)H.size(), false), 8);
+    for (const BruteOrder* o : {&rec.orders.flat, &rec.orders.grouped}) {
+        const char* name = o == &rec.orders.flat ? "flat" : "grouped";
+        if (o->groups.empty()) continue; // (no grouped order for this scene)
+        const size_t n_slots = o->prims.size() - (size_t)rec.n_planes;
+        std::vector<int> in_order(H.size(), 0);
+        for (size_t k = 0; k < n_slots; k++) {
+            const int id = as_i(o->prims[k].a.w);
+            if (id < 0 || (size_t)id >= H.size() || H[id].kind == RT_PRIM_PLANE) {
+                std::printf("FAIL %s order: slot %zu holds primitive %d\n", name, k, id);
+                return 1;
+            }
+            in_order[id] = 1;
+        }
+        for (size_t i = 0; i < H.size(); i++)
+            if (H[i].kind != RT_PRIM_PLANE && !in_order[i]) {
+                std::printf("FAIL %s order: primitive %zu has no slot\n", name, i);
+                return 1;
+            }
+        for (size_t k = 0; k + 1 < o->rects.size(); k++) // (the last record is the spare one)
+            if (o->rects[k].sg < 0 || (size_t)(o->rects[k].sg >> 1) >= n_slots) {
+                std::printf("FAIL %s order: rect %zu names slot %d of %zu\n", name, k, o->rects[k].sg >> 1, n_slots);
+                return 1;
+            }
+    }
+    std::printf("records %zu flat slots, %zu rects, %zu frames and boxes; %zu groups, %zu grouped slots\n",
+                rec.orders.flat.prims.size(), rec.orders.flat.rects.size() - 1, rec.orders.flat.frames.size() - 1,
+                rec.orders.grouped.groups.size(), rec.orders.grouped.prims.size());
     if (argc > 2 && std::strcmp(argv[2], "--ref") == 0) { // the exact pass's inputs too (sanitizer runs)
         const RefBvh r = build_ref_bvh(H);
         for (const rt_camera& cam : ps.cameras) {

@@ -495,7 +495,7 @@ def test_library_built_from_these_sources():
 def test_brute_layout_linear_on_large_rectangle_scenes():
     """The flat brute-force order is built for every scene; its box and frame finders pair
     rectangles by search, so a group with more than 4,096 candidates keeps its rectangles as they
-    are (rtcore_api.hip kFindMax): 30,000 axis-aligned single faces and 6,000 rotated cube faces lay
+    are (scene_records.cpp kFindMax): 30,000 axis-aligned single faces and 6,000 rotated cube faces lay
     out in well under a second instead of minutes, while a small scene still finds its boxes."""
     import time
 
