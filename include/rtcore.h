@@ -42,7 +42,9 @@ extern "C" {
                                 3: rt_set_jit, rt_scene_get_jit_error, build stats [15..17];
                                 4: rt_kernel_times;
                                 5: rt_frame_submit / rt_frame_collect / rt_frame_inject_fault;
-                                6: rt_trace_paths, rt_debug_ray, rt_bounce_type */
+                                6: rt_trace_paths, rt_debug_ray, rt_bounce_type; rt_query_rays, rt_query_rays_device
+                                   and rt_camera_rays were added under version 6 (purely additive): a host
+                                   detects them by symbol */
 
 typedef enum rt_status {
     RT_OK = 0,
@@ -379,6 +381,50 @@ typedef struct rt_debug_ray {
 int rt_trace_paths(rt_scene* scene, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t spp,
                    uint64_t seed, uint64_t sample_base, rt_debug_ray* rays_out, int32_t* n_rays_out,
                    rt_color* colors_out);
+
+/* ---------------------------------------------------------------- ray queries --- */
+/* Ray (Vectors/Ray.cs): origin (w = 1) and an already-normalised direction (w = 0), taken as given. 64 B. */
+typedef struct rt_ray { rt_vec4d origin, direction; } rt_ray;
+
+/* Hit (Hit.cs) of Scene.RayTrace(ray, null): 48 B, three 16-byte rows, no pointers.
+ *   0  prim_id      Primitive.ID (insertion order), -1 on a miss
+ *   4  inside       Hit.Inside after Primitive.Invert (0 / 1; 0 on a miss)
+ *   8  distance     Hit.Distance (0 on a miss); RT_QUERY_FAST: the kernel's fp32 value widened exactly
+ *  16  position[3]  RT_QUERY_FAST: as rt_debug_ray.position; RT_QUERY_EXACT: 0
+ *  28  normal[3]    RT_QUERY_FAST: as rt_debug_ray.normal (same NaN quirk); RT_QUERY_EXACT: 0
+ *  40  reserved[2]  0 */
+typedef struct rt_hit { int32_t prim_id, inside; double distance; float position[3], normal[3]; int32_t reserved[2]; } rt_hit;
+
+typedef enum rt_query_mode {
+    RT_QUERY_FAST = 0, /* the path kernels' own fp32 closest hit, in the scene's traversal mode (BRUTE, GROUPED
+                          or BVH; RT_ERR_STATE on a BVH2 scene); the ray rounded to fp32 component by component */
+    RT_QUERY_EXACT = 1 /* the fp64 reference query of rt_primary_ids (reference BVH, built on first use), in
+                          every traversal mode: the reference's own answer bit for bit */
+} rt_query_mode;
+
+/*
+ * Scene.RayTrace(ray, null) (Scene.cs:113-120) for rays the caller brings: hits_out[i] answers rays[i].
+ * A ray with a non-finite component or a zero direction is a miss.  n == 0 returns RT_OK and touches
+ * nothing; RT_ERR_ARG, before anything is launched, for a null pointer, n < 0 or an unknown mode.  The
+ * generic kernels run, whatever rt_set_jit says; the counters of rt_scene_get_stats, an armed
+ * rt_debug_ray_log, rt_kernel_times and the scene-specialised kernels are left as they were.  No camera
+ * is needed.  RT_QUERY_EXACT: RT_ERR_STATE from the host entry (prim_id -2 in the device entry's output)
+ * where the reference BVH is deeper than the exact kernel's traversal stack, as rt_primary_ids.
+ * rt_query_rays takes host buffers and is synchronous, on the scene's own stream: it works in chunks
+ * of at most 2^19 rays (RTCORE_QUERY_CHUNK in the environment sets another size), two of them resident,
+ * so its device scratch and its pinned staging stay at about 117 MB each for any n, and a chunk's
+ * upload and the previous chunk's download overlap the kernel between them.
+ * rt_query_rays_device takes device buffers and is asynchronous on `stream` (a hipStream_t, NULL = the
+ * default stream), ordered like the device-resident renders.
+ */
+int rt_query_rays(rt_scene* scene, int32_t mode, const rt_ray* rays, int64_t n, rt_hit* hits_out);
+int rt_query_rays_device(rt_scene* scene, int32_t mode, const rt_ray* d_rays, int64_t n, rt_hit* d_hits, void* stream);
+/* Host only, no device: Camera.GetRay(x, y).Offset(imagePlane) (DebugRaycaster.cs:241) for the integer
+   pixels of the tile [x0, x0+w) x [y0, y0+h) of a width x height frame, out[x*h + y]: the rays
+   rt_primary_ids traces.  RT_ERR_ARG for a null pointer, an unknown camera kind, w or h <= 0 or a tile
+   outside the frame. */
+int rt_camera_rays(const rt_camera* camera, int32_t width, int32_t height, int32_t x0, int32_t y0, int32_t w,
+                   int32_t h, rt_ray* out);
 
 /* -------------------------------------------------- device-resident renders --- */
 /*

@@ -12,6 +12,7 @@ calls raise ``RtError``.
 from __future__ import annotations
 
 import ctypes as C
+import enum
 import os
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
@@ -35,6 +36,15 @@ RT_BVH_BUILDER_AUTO, RT_BVH_BUILDER_HOST, RT_BVH_BUILDER_GPU = 0, 1, 2
 BOUNCE_TYPE_NAMES = ("Skipped", "Diffuse", "Specular", "SpecularFail", "Transmitted", "Emission", "PureBlack",
                      "RecursionComplete", "Missed", "Debug")
 RT_TRACE_MAX_RECORDS = 1 << 20  # records of one rt_trace_paths call
+
+
+class rt_query_mode(enum.IntEnum):
+    """Mode of rt_query_rays (include/rtcore.h)."""
+    RT_QUERY_FAST = 0   # the path kernels' fp32 closest hit, in the scene's traversal mode
+    RT_QUERY_EXACT = 1  # the fp64 reference query of rt_primary_ids
+
+
+RT_QUERY_FAST, RT_QUERY_EXACT = int(rt_query_mode.RT_QUERY_FAST), int(rt_query_mode.RT_QUERY_EXACT)
 BUILD_STAT_NAMES = ("prepare_ms", "bvh_ms", "upload_ms", "gpu_build_ms", "ploc_rounds", "wide_nodes", "stack_need",
                     "flat_rects", "flat_boxes", "flat_frames", "flat_frame_boxes", "flat_frame_rects", "flat_tris",
                     "flat_spheres", "hot_nodes", "jit_status", "jit_compile_ms", "jit_cached", "group_max",
@@ -121,6 +131,30 @@ DEBUG_RAY_DTYPE = np.dtype([
     ("direction", np.float32, (3,)), ("tint", np.float32, (3,)), ("reserved1", np.int32),
 ])
 
+
+class rt_ray(C.Structure):
+    """Ray (Vectors/Ray.cs): origin (w = 1) and unit direction (w = 0), 64 B."""
+    _fields_ = [("origin", rt_vec4d), ("direction", rt_vec4d)]
+
+
+class rt_hit(C.Structure):
+    """One answer of rt_query_rays (Hit.cs): 48 B, offsets in include/rtcore.h."""
+    _fields_ = [
+        ("prim_id", C.c_int32), ("inside", C.c_int32), ("distance", C.c_double),
+        ("position", C.c_float * 3), ("normal", C.c_float * 3), ("reserved", C.c_int32 * 2),
+    ]
+
+
+# the same records as numpy structured dtypes (GpuRaytracer.query_rays, camera_rays)
+RAY_DTYPE = np.dtype([("origin", np.float64, (4,)), ("direction", np.float64, (4,))])
+HIT_DTYPE = np.dtype([
+    ("prim_id", np.int32), ("inside", np.int32), ("distance", np.float64),
+    ("position", np.float32, (3,)), ("normal", np.float32, (3,)), ("reserved", np.int32, (2,)),
+])
+
+# entry points added under an unchanged ABI version: bound when the library has them (an older build
+# named by RTCORE_LIB may not)
+_OPTIONAL = ("rt_query_rays", "rt_query_rays_device", "rt_camera_rays")
 
 _lib: Optional[C.CDLL] = None
 
@@ -209,9 +243,12 @@ def load_library(path: str = "") -> C.CDLL:
                                         C.c_double, P(C.c_float), P(C.c_int32), P(C.c_double), P(C.c_double)]),
         "rt_debug_trace_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p,
                                           C.c_void_p, P(C.c_float)]),
+        "rt_query_rays": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+        "rt_query_rays_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+        "rt_camera_rays": (C.c_int, [P(rt_camera)] + [C.c_int32] * 6 + [C.c_void_p]),
     }
     for name, (res, args) in sig.items():
-        if name.startswith("rt_debug_") and not hasattr(lib, name):
+        if (name.startswith("rt_debug_") or name in _OPTIONAL) and not hasattr(lib, name):
             continue  # an older build (RTCORE_LIB, A/B measurements) without a newer debug entry point
         fn = getattr(lib, name)
         fn.restype = res
@@ -339,6 +376,35 @@ def sample_output(sum_rgb: Tuple[float, float, float], samples: int, misses: int
 
 def device_count() -> int:
     return load_library().rt_device_count()
+
+
+def camera_rays(camera: rt_camera, size: Tuple[int, int], x0: int = 0, y0: int = 0, w: Optional[int] = None,
+                h: Optional[int] = None) -> np.ndarray:
+    """rt_camera_rays (host code, no GPU): Camera.GetRay(x, y).Offset(imagePlane) for the integer pixels
+    of a tile of a size[0] x size[1] frame, as a RAY_DTYPE array indexed [x, y]: the rays primary_ids traces."""
+    lib = load_library()
+    if not hasattr(lib, "rt_camera_rays"):
+        raise RtError("this build of the library has no rt_camera_rays")
+    W, H = int(size[0]), int(size[1])
+    w = W - x0 if w is None else w
+    h = H - y0 if h is None else h
+    out = np.zeros((max(w, 0), max(h, 0)), RAY_DTYPE)
+    cam = rt_camera.from_buffer_copy(camera)
+    _check(lib.rt_camera_rays(C.byref(cam), W, H, x0, y0, w, h, out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def _pack_rays(origins, directions) -> np.ndarray:
+    """(n, 3) or (n, 4) origins and directions -> a contiguous RAY_DTYPE array; w is filled with 1 / 0."""
+    o = np.asarray(origins, np.float64)
+    d = np.asarray(directions, np.float64)
+    if o.ndim != 2 or d.ndim != 2 or o.shape[0] != d.shape[0] or o.shape[1] not in (3, 4) or d.shape[1] not in (3, 4):
+        raise ValueError("origins and directions must be (n, 3) or (n, 4) arrays of the same n")
+    rays = np.zeros(o.shape[0], RAY_DTYPE)
+    rays["origin"][:, 3] = 1.0
+    rays["origin"][:, :o.shape[1]] = o
+    rays["direction"][:, :d.shape[1]] = d
+    return rays
 
 
 class GpuRaytracer:
@@ -492,6 +558,30 @@ class GpuRaytracer:
                                        n_rays.ctypes.data_as(C.POINTER(C.c_int32)),
                                        colors.ctypes.data_as(C.POINTER(rt_color))))
         return records, n_rays, colors
+
+    def query_rays(self, origins, directions=None, exact: bool = False) -> np.ndarray:
+        """rt_query_rays (Scene.RayTrace(ray, null) for the caller's rays): origins and directions as
+        (n, 3) or (n, 4) arrays (w filled with 1 / 0), or one RAY_DTYPE array as camera_rays returns it.
+        exact: the fp64 reference query; else the path kernels' fp32 closest hit in the scene's
+        traversal mode.  Returns a HIT_DTYPE array of the rays' shape; prim_id -1 marks a miss."""
+        if directions is None:
+            rays = np.ascontiguousarray(origins, RAY_DTYPE)
+        else:
+            rays = _pack_rays(origins, directions)
+        hits = np.zeros(rays.shape, HIT_DTYPE)
+        _check(self.lib.rt_query_rays(self.handle, RT_QUERY_EXACT if exact else RT_QUERY_FAST,
+                                      rays.ctypes.data_as(C.c_void_p), rays.size, hits.ctypes.data_as(C.c_void_p)))
+        return hits
+
+    def query_rays_device(self, d_rays: int, n: int, d_hits: int, exact: bool = False, stream: int = 0) -> None:
+        """rt_query_rays_device: asynchronous query of n rt_ray at device pointer d_rays into n rt_hit at
+        d_hits (e.g. torch data_ptr()) on `stream` (a hipStream_t as an integer, 0 = the default stream)."""
+        _check(self.lib.rt_query_rays_device(self.handle, RT_QUERY_EXACT if exact else RT_QUERY_FAST, C.c_void_p(d_rays),
+                                             n, C.c_void_p(d_hits), C.c_void_p(stream)))
+
+    def camera_rays(self, x0: int = 0, y0: int = 0, w: Optional[int] = None, h: Optional[int] = None) -> np.ndarray:
+        """camera_rays for this scene's camera and frame size."""
+        return camera_rays(self.camera, (self.width, self.height), x0, y0, w, h)
 
     def render_device(self, x0, y0, w, h, spp, seed, sample_base, d_sum, d_samples, d_misses, d_rays,
                       stream: int = 0) -> None:

@@ -1,0 +1,219 @@
+// api_query.hip -- the C ABI's ray queries (include/rtcore.h, "ray queries"): Scene.RayTrace(ray, null)
+// (Scene.cs:113-120) for rays the caller brings, and the camera's own rays on the host.
+#include <atomic>
+#include <cstdlib>
+#include <cstring>
+
+#include "rt_scene.h"
+
+namespace {
+
+constexpr int64_t kQueryChunk = 1 << 19;    // rays of one chunk of rt_query_rays; two chunks are resident
+constexpr int64_t kQueryLaunchMax = 1 << 30; // rays of one launch (32-bit ray indices and dispenser)
+
+// One launch over n <= kQueryLaunchMax rays on `st`, after the stream ordering is settled.
+int launch_rays(rt_scene* s, int32_t mode, const rt_ray* d_rays, unsigned n, rt_hit* d_hits, hipStream_t st)
+{
+    if (mode == RT_QUERY_EXACT) {
+        HIP_TRY(launch_query_exact(s->dev, d_rays, n, d_hits, st));
+        return RT_OK;
+    }
+    // the generic kernel of the scene's traversal mode (path_variant's numbering), unstaged records
+    const int kernel = s->resolved == RT_TRAVERSAL_BVH ? 3 : s->resolved == RT_TRAVERSAL_GROUPED ? 1 : 0;
+    PathParams h{};
+    fill_launch(s->dev, path_variant(kernel, false), h);
+    QueryParams p{};
+    p.rays = reinterpret_cast<const double2*>(d_rays);
+    p.hits = reinterpret_cast<float4*>(d_hits);
+    p.n = n;
+    p.scene = h.scene;
+    p.tests = h.tests;
+    p.rows = h.rows;
+    p.rects = h.rects;
+    p.frames = h.frames;
+    p.prims = h.prims;
+    p.groups = h.groups;
+    p.nodes4 = s->dev.nodes4; // the global nodes, root included: no hot table in this kernel
+    p.root4 = s->dev.root4;
+    p.n_nodes4 = s->dev.n_nodes4;
+    p.xf = h.xf;
+    p.vnormals = h.vnormals;
+    const int blocks = (int)((n + 255u) / 256u);
+    int grid = std::min(blocks, s->n_cu * query_blocks_per_cu(kernel));
+    if (kernel == 3) {
+        HIP_TRY(s->stack_ovf.reserve((size_t)grid * 256 * kStackOverflow));
+        HIP_TRY(s->counter.reserve(1));
+        HIP_TRY(hipMemsetAsync(s->counter.p, 0, sizeof(unsigned int), st));
+        p.counter = s->counter.p;
+        p.stack_ovf = s->stack_ovf.p;
+        p.spec = 16;
+        if (const char* e = getenv("RTCORE_BVH_SPEC")) p.spec = std::max(1, std::min(64, atoi(e)));
+    }
+    HIP_TRY(launch_query(p, kernel, grid, st));
+    return RT_OK;
+}
+
+// Argument and state checks shared by both entry points; RT_OK with *empty set for n == 0.
+int check_query(rt_scene* s, int32_t mode, const void* rays, int64_t n, const void* hits, const char* name, bool* empty)
+{
+    *empty = false;
+    const bool known_mode = mode == RT_QUERY_FAST || mode == RT_QUERY_EXACT;
+    const char* bad = !s ? "null scene" : n < 0 ? "n < 0" : !known_mode ? "unknown mode" : nullptr;
+    if (!bad && n == 0) {
+        *empty = true;
+        return RT_OK;
+    }
+    if (!bad && (!rays || !hits)) bad = "null pointer";
+    if (bad) {
+        set_error(std::string(name) + ": bad argument (" + bad + ")");
+        return RT_ERR_ARG;
+    }
+    if (mode == RT_QUERY_FAST && s->resolved == RT_TRAVERSAL_BVH2) {
+        set_error(std::string(name) + ": RT_QUERY_FAST runs in the traversal modes BRUTE, GROUPED and BVH; this scene "
+                                      "is in BVH2 mode (rt_scene_set_traversal), use RT_TRAVERSAL_BVH or RT_QUERY_EXACT");
+        return RT_ERR_STATE;
+    }
+    return RT_OK;
+}
+
+int query_device(rt_scene* s, int32_t mode, const rt_ray* d_rays, int64_t n, rt_hit* d_hits, hipStream_t st)
+{
+    if (mode == RT_QUERY_EXACT) {
+        const int rc = ensure_ref_bvh(s);
+        if (rc != RT_OK) return rc;
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    // the work counter and the stack overflow area are the scene's: order after its last operation
+    if (s->any_op && st != s->last_stream) HIP_TRY(hipStreamWaitEvent(st, s->done_ev, 0));
+    for (int64_t a = 0; a < n; a += kQueryLaunchMax) {
+        const int rc = launch_rays(s, mode, d_rays + a, (unsigned)std::min(kQueryLaunchMax, n - a), d_hits + a, st);
+        if (rc != RT_OK) return rc;
+    }
+    return end_op(s, st);
+}
+
+} // namespace
+
+extern "C" {
+
+int rt_query_rays_device(rt_scene* s, int32_t mode, const rt_ray* d_rays, int64_t n, rt_hit* d_hits, void* stream)
+{
+    bool empty;
+    const int rc = check_query(s, mode, d_rays, n, d_hits, "rt_query_rays_device", &empty);
+    if (rc != RT_OK || empty) return rc;
+    return query_device(s, mode, d_rays, n, d_hits, static_cast<hipStream_t>(stream));
+}
+
+// Chunk k's rays go through pinned staging to device slot k & 1 on copy_stream, its kernel runs on the
+// scene's stream once they have landed, and its hits come back on copy_stream (queue_copy) into the
+// staging slot the host pool then copies out of (consume_copies).  The copy stream's order is
+// upload k + 1, download k: so chunk k's kernel runs beside download k - 1 and upload k + 1, and a
+// slot (device or pinned) is rewritten only after what last read it: upload k + 1 follows download
+// k - 1, which followed kernel k - 1, and the host refills a pinned ray slot after it has consumed the
+// download queued behind that slot's previous upload.
+int rt_query_rays(rt_scene* s, int32_t mode, const rt_ray* rays, int64_t n, rt_hit* hits_out)
+{
+    bool empty;
+    int rc = check_query(s, mode, rays, n, hits_out, "rt_query_rays", &empty);
+    if (rc != RT_OK || empty) return rc;
+    int64_t chunk = kQueryChunk;
+    if (const char* e = getenv("RTCORE_QUERY_CHUNK")) chunk = std::max<int64_t>(1, std::min<int64_t>(kQueryChunk, atoll(e)));
+    chunk = std::min(chunk, n);
+    if (mode == RT_QUERY_EXACT) {
+        rc = ensure_ref_bvh(s);
+        if (rc != RT_OK) return rc;
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    if (!s->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
+    HIP_TRY(hipStreamSynchronize(s->copy_stream)); // (copies a failed call left behind: see rt_render_tile)
+    const size_t C = (size_t)chunk;
+    HIP_TRY(s->query_rays.reserve(2 * C));
+    HIP_TRY(s->query_hits.reserve(2 * C));
+    // pinned staging: the two hit slots (at the offsets queue_copy gives them), then the two ray slots
+    HIP_TRY(s->stage.reserve(2 * C * (sizeof(rt_hit) + sizeof(rt_ray))));
+    rt_ray* stage_rays = reinterpret_cast<rt_ray*>(s->stage.p + 2 * C * sizeof(rt_hit));
+    for (int j = 0; j < 2; j++) {
+        if (!s->query_up_ev[j]) HIP_TRY(hipEventCreateWithFlags(&s->query_up_ev[j], hipEventDisableTiming));
+        if (!s->band_ev[j]) HIP_TRY(hipEventCreateWithFlags(&s->band_ev[j], hipEventDisableTiming));
+    }
+    hipStream_t st = s->stream;
+    if (s->any_op && st != s->last_stream) HIP_TRY(hipStreamWaitEvent(st, s->done_ev, 0));
+    const int64_t K = (n + chunk - 1) / chunk;
+    auto count = [&](int64_t k) { return (size_t)std::min(chunk, n - k * chunk); };
+    auto upload = [&](int64_t k) -> int {
+        const size_t m = count(k), slot = (size_t)(k & 1) * C;
+        const rt_ray* src = rays + k * chunk;
+        parallel_ranges(m, 65536, [&](size_t a, size_t b) { std::memcpy(stage_rays + slot + a, src + a, (b - a) * sizeof(rt_ray)); });
+        HIP_TRY(hipMemcpyAsync(s->query_rays.p + slot, stage_rays + slot, m * sizeof(rt_ray), hipMemcpyHostToDevice,
+                               s->copy_stream));
+        HIP_TRY(hipEventRecord(s->query_up_ev[k & 1], s->copy_stream));
+        return RT_OK;
+    };
+    std::atomic<bool> overflow{false};
+    CopyPlan plans[2];
+    auto consume = [&](int64_t k) -> int {
+        const size_t slot = (size_t)(k & 1) * C;
+        rt_hit* dst = hits_out + k * chunk;
+        return consume_copies(s, plans[k & 1], [&](const unsigned char* stage, size_t a, size_t b) {
+            const rt_hit* h = reinterpret_cast<const rt_hit*>(stage);
+            std::memcpy(dst + (a - slot), h + a, (b - a) * sizeof(rt_hit));
+            if (mode == RT_QUERY_EXACT)
+                for (size_t i = a; i < b; i++)
+                    if (h[i].prim_id == -2) overflow = true;
+        });
+    };
+    rc = upload(0);
+    if (rc != RT_OK) return rc;
+    for (int64_t k = 0; k < K; k++) {
+        const size_t m = count(k), slot = (size_t)(k & 1) * C;
+        HIP_TRY(hipStreamWaitEvent(st, s->query_up_ev[k & 1], 0));
+        rc = launch_rays(s, mode, s->query_rays.p + slot, (unsigned)m, s->query_hits.p + slot, st);
+        if (rc != RT_OK) return rc;
+        HIP_TRY(hipEventRecord(s->band_ev[k & 1], st));
+        if (k >= 1) {
+            rc = consume(k - 1);
+            if (rc != RT_OK) return rc;
+        }
+        if (k + 1 < K) {
+            rc = upload(k + 1);
+            if (rc != RT_OK) return rc;
+        }
+        HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->band_ev[k & 1], 0));
+        plans[k & 1] = CopyPlan{};
+        rc = queue_copy(s, plans[k & 1], s->query_hits.p, slot, slot + m, sizeof(rt_hit),
+                        (int)std::max<size_t>(1, std::min<size_t>(rt_scene::kCopyChunks, (m * sizeof(rt_hit)) >> 20)),
+                        s->copy_stream);
+        if (rc != RT_OK) return rc;
+    }
+    rc = end_op(s, st);
+    if (rc != RT_OK) return rc;
+    rc = consume(K - 1);
+    if (rc != RT_OK) return rc;
+    if (overflow) {
+        set_error("rt_query_rays: the reference BVH is deeper than the exact kernel's traversal stack");
+        return RT_ERR_STATE;
+    }
+    return RT_OK;
+}
+
+int rt_camera_rays(const rt_camera* cam, int32_t width, int32_t height, int32_t x0, int32_t y0, int32_t w, int32_t h,
+                   rt_ray* out)
+{
+    if (!cam || !out || (cam->kind != RT_CAMERA_FRUSTUM && cam->kind != RT_CAMERA_ORTHO) || width <= 0 || height <= 0 ||
+        w <= 0 || h <= 0 || x0 < 0 || y0 < 0 || (int64_t)x0 + w > width || (int64_t)y0 + h > height) {
+        set_error("rt_camera_rays: bad argument (null pointer, unknown camera kind, w or h <= 0, or a tile outside the frame)");
+        return RT_ERR_ARG;
+    }
+    CameraD camd;
+    CameraF camf;
+    camera_init(*cam, width, height, camd, camf);
+    for (int x = 0; x < w; x++)
+        for (int y = 0; y < h; y++) {
+            Vec4d o, d;
+            camera_ray_d(camd, (double)(x0 + x), (double)(y0 + y), o, d);
+            out[(size_t)x * h + y] = rt_ray{rt_vec4d{o.x, o.y, o.z, o.w}, rt_vec4d{d.x, d.y, d.z, d.w}};
+        }
+    return RT_OK;
+}
+
+} // extern "C"

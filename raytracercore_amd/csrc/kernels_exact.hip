@@ -140,6 +140,7 @@ struct LeafItem {
 struct LeafScan {
     int best = -1;
     double best_d = 0, prev_far = 0;
+    bool best_in = false; // Hit.Inside of the best hit (after Invert)
     bool have_prev = false;
     // returns false once the `Near > previous.Far` break is reached
     __device__ bool visit(const DevScene& s, const LeafItem& it, Vec4d o, Vec4d d)
@@ -149,6 +150,7 @@ struct LeafScan {
         if (prim_raytrace_d(s, s.ref_nodes[it.node].prim, o, d, h) && (best < 0 || h.dist < best_d)) {
             best = h.prim;
             best_d = h.dist;
+            best_in = h.inside;
             prev_far = it.fr;
             have_prev = true;
         }
@@ -192,9 +194,8 @@ __device__ static bool walk_leaves(const DevScene& s, Vec4d o, Vec4d d, F&& f)
 // Same result when more than kLeafCap leaves are pierced (large meshes): the leaves are taken in
 // sorted order by repeated selection, one depth-first walk per leaf the scan consumes (the scan
 // usually stops after a few leaves), so no list is stored.
-__device__ static int ref_raytrace_select(const DevScene& s, Vec4d o, Vec4d d)
+__device__ static int ref_raytrace_select(const DevScene& s, Vec4d o, Vec4d d, LeafScan& scan)
 {
-    LeafScan scan;
     double cur_n = 0;
     int cur_o = -1;
     bool first = true;
@@ -214,13 +215,13 @@ __device__ static int ref_raytrace_select(const DevScene& s, Vec4d o, Vec4d d)
         cur_o = next_o;
         first = false;
     }
-    return scan.best;
+    return 0;
 }
 
-// Returns the primitive ID, -1 on a miss, -2 if the traversal stack overflowed.
-__device__ int ref_raytrace(const DevScene& s, Vec4d o, Vec4d d)
+// Scene.RayTrace(ray, null) into scan (a fresh LeafScan; s.n_ref_nodes > 0): 0, or -2 if the
+// traversal stack overflowed.
+__device__ static int ref_raytrace_scan(const DevScene& s, Vec4d o, Vec4d d, LeafScan& scan)
 {
-    if (s.n_ref_nodes == 0) return -1;
     LeafItem leaves[kLeafCap];
     int nl = 0;
     bool overflow = false;
@@ -229,7 +230,7 @@ __device__ int ref_raytrace(const DevScene& s, Vec4d o, Vec4d d)
         else overflow = true;
     });
     if (!ok) return -2;
-    if (overflow) return ref_raytrace_select(s, o, d);
+    if (overflow) return ref_raytrace_select(s, o, d, scan);
     for (int i = 1; i < nl; i++) { // Util.InsertSort, stable
         LeafItem a = leaves[i];
         int j = i - 1;
@@ -239,9 +240,29 @@ __device__ int ref_raytrace(const DevScene& s, Vec4d o, Vec4d d)
         }
         leaves[j + 1] = a;
     }
-    LeafScan scan;
     for (int i = 0; i < nl; i++)
         if (!scan.visit(s, leaves[i], o, d)) break;
+    return 0;
+}
+
+// Returns the primitive ID, -1 on a miss, -2 if the traversal stack overflowed.
+__device__ int ref_raytrace(const DevScene& s, Vec4d o, Vec4d d)
+{
+    if (s.n_ref_nodes == 0) return -1;
+    LeafScan scan;
+    if (ref_raytrace_scan(s, o, d, scan) < 0) return -2;
+    return scan.best;
+}
+
+// The same query with the winning hit: h = (ID, Hit.Distance, Hit.Inside), (-1, 0, false) on a miss.
+// Returns the primitive ID, -1 or -2 as ref_raytrace.
+__device__ int ref_raytrace_hit(const DevScene& s, Vec4d o, Vec4d d, HitD& h)
+{
+    h = HitD{-1, 0.0, false};
+    if (s.n_ref_nodes == 0) return -1;
+    LeafScan scan;
+    if (ref_raytrace_scan(s, o, d, scan) < 0) return -2;
+    if (scan.best >= 0) h = HitD{scan.best, scan.best_d, scan.best_in};
     return scan.best;
 }
 
@@ -268,21 +289,6 @@ __device__ int ref_bvh_count(const DevScene& s, Vec4d o, Vec4d d)
     return count;
 }
 
-__device__ static void camera_ray_d(const CameraD& c, double x, double y, Vec4d& o, Vec4d& d)
-{
-    if (c.kind == RT_CAMERA_FRUSTUM) {
-        double ox = c.tan_x * ((x - c.w2) / c.w2);
-        double oy = c.tan_y * ((y - c.h2) / c.h2);
-        Vec4d dir = add(add(c.look, scale(c.side, ox)), scale(c.up, oy));
-        o = c.position;
-        d = normalize_v(dir);
-    } else {
-        o = add(add(c.position, scale(c.side, (x - c.w2) * c.h_mult)), scale(c.up, (y - c.h2) * c.v_mult));
-        d = normalize_v(c.look);
-    }
-    o = add(o, scale(d, c.image_plane)); // Ray.Offset (Ray.cs:59-62)
-}
-
 // mode 0: primary hit IDs (Primitives mode), mode 1: BVH node counts (BoundingVolumes mode)
 __global__ void __launch_bounds__(64) primary_ids_kernel(DevScene s, CameraD cam, int x0, int y0, int w, int h, int mode,
                                                          int32_t* ids)
@@ -293,6 +299,40 @@ __global__ void __launch_bounds__(64) primary_ids_kernel(DevScene s, CameraD cam
     Vec4d o, d;
     camera_ray_d(cam, (double)(x0 + x), (double)(y0 + y), o, d);
     ids[(size_t)y * w + x] = mode == 0 ? ref_raytrace(s, o, d) : ref_bvh_count(s, o, d);
+}
+
+// rt_query_rays, RT_QUERY_EXACT: the reference query on caller-supplied rays, one ray per lane.  A
+// ray is four 16-B rows (origin, direction as Vec4D), a hit three: (ID, inside, distance) and two
+// rows of zeros (rt_hit, rtcore.h).  A ray with a non-finite component or a zero direction is a miss
+// (decided here, where the ray is loaded); prim_id -2 reports a traversal-stack overflow.
+__global__ void __launch_bounds__(64) query_exact_kernel(DevScene s, const double2* __restrict__ rays, unsigned n,
+                                                         uint4* __restrict__ hits)
+{
+    const unsigned i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    const double2 r0 = rays[4 * (size_t)i], r1 = rays[4 * (size_t)i + 1], r2 = rays[4 * (size_t)i + 2],
+                  r3 = rays[4 * (size_t)i + 3];
+    const Vec4d o{r0.x, r0.y, r1.x, r1.y}, d{r2.x, r2.y, r3.x, r3.y};
+    const double inf = __builtin_huge_val();
+    const bool finite = (fabs(o.x) < inf) & (fabs(o.y) < inf) & (fabs(o.z) < inf) & (fabs(o.w) < inf) & (fabs(d.x) < inf) &
+                        (fabs(d.y) < inf) & (fabs(d.z) < inf) & (fabs(d.w) < inf); // false for NaN
+    const bool valid = finite & ((d.x != 0.0) | (d.y != 0.0) | (d.z != 0.0));
+    HitD h{-1, 0.0, false};
+    int id = -1;
+    if (valid) id = ref_raytrace_hit(s, o, d, h);
+    const unsigned long long db = (unsigned long long)__double_as_longlong(h.dist);
+    hits[3 * (size_t)i] = make_uint4((unsigned)id, h.inside ? 1u : 0u, (unsigned)db, (unsigned)(db >> 32));
+    hits[3 * (size_t)i + 1] = make_uint4(0u, 0u, 0u, 0u);
+    hits[3 * (size_t)i + 2] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+hipError_t launch_query_exact(const DevScene& s, const rt_ray* d_rays, unsigned n, rt_hit* d_hits, hipStream_t stream)
+{
+    static_assert(sizeof(rt_ray) == 64 && sizeof(rt_hit) == 48, "rt_ray is four 16-B rows, rt_hit three");
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(query_exact_kernel, dim3((n + 63u) / 64u), dim3(64), 0, stream, s,
+                       reinterpret_cast<const double2*>(d_rays), n, reinterpret_cast<uint4*>(d_hits));
+    return hipGetLastError();
 }
 
 hipError_t launch_primary_ids(const DevScene& s, const CameraD& cam, int x0, int y0, int w, int h, int mode,

@@ -1896,6 +1896,232 @@ __global__ void __launch_bounds__(256, WAVES) trace_rays_kernel(TraceRaysParams 
     }
 }
 
+// ---- rt_query_rays, RT_QUERY_FAST: the closest hit of caller-supplied rays -------------------------
+// Scene.RayTrace(ray, null) by the path kernels' own closest-hit code from "no previous hit" (prev
+// = -1, Best = none), one rt_hit per ray.  A ray arrives as rt_ray (fp64, four 16-B rows) and is
+// rounded to fp32 component by component.  valid: every component finite (before and after the
+// rounding) and the direction not zero.  Any other ray is a miss, decided here where the ray is
+// loaded and not by how a NaN would fall through the tests.
+struct QueryRay {
+    V3 o, d;
+    bool valid;
+};
+__device__ __forceinline__ QueryRay load_query_ray(const double2* __restrict__ rays, unsigned i)
+{
+    const double2 r0 = rays[4 * (size_t)i], r1 = rays[4 * (size_t)i + 1], r2 = rays[4 * (size_t)i + 2],
+                  r3 = rays[4 * (size_t)i + 3];
+    QueryRay q;
+    q.o = v3((float)r0.x, (float)r0.y, (float)r1.x);
+    q.d = v3((float)r2.x, (float)r2.y, (float)r3.x);
+    const float inf = __builtin_huge_valf();
+    const bool finite = (fabsf(q.o.x) < inf) & (fabsf(q.o.y) < inf) & (fabsf(q.o.z) < inf) & (fabsf(q.d.x) < inf) &
+                        (fabsf(q.d.y) < inf) & (fabsf(q.d.z) < inf) & (fabs(r1.y) < __builtin_huge_val()) &
+                        (fabs(r3.y) < __builtin_huge_val()); // (every compare is false for NaN)
+    q.valid = finite & ((q.d.x != 0.0f) | (q.d.y != 0.0f) | (q.d.z != 0.0f));
+    return q;
+}
+
+__device__ __forceinline__ void store_query_miss(float4* __restrict__ out)
+{
+    out[0] = make_float4(__int_as_float(-1), 0.0f, 0.0f, 0.0f);
+    out[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    out[2] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+// The Hit of a finished query as rt_hit (kHitRows 16-B rows): the geometric head of shade() -- the hit
+// point (an axis-aligned rectangle's on its plane), a rectangle's side recomputed from its normal,
+// sphere, ellipsoid and vertex-normal normals with Triangle.GetNormal's NaN-inside quirk, Inside after
+// Invert and the normal turned toward the ray -- restated for both record forms: SLOT, the BVH
+// order's records (rows a, b, d), else the brute-force orders' with the shading row c.  The same
+// operations in the same order as shade(), so the values are the ones rt_trace_paths records.
+template <bool SLOT, class VnP, class TestP>
+__device__ __forceinline__ void query_hit(uint32_t facts, const PrimF* __restrict__ prims, const XformF* __restrict__ xfs,
+                                          VnP vnormals, TestP tests, const Best& b, V3 o, V3 d, float4* __restrict__ out)
+{
+    if (b.sg < 0) {
+        store_query_miss(out);
+        return;
+    }
+    bool gin = (b.sg & 1) != 0;
+    const PrimF& P = prims[b.sg >> 1];
+    const float4 Pa = P.a, Pb = P.b, Pd = P.d;
+    const uint32_t fl = __float_as_uint(Pb.w);
+    const int id = __float_as_int(Pa.w);
+    const uint32_t kind = fl & KIND_MASK;
+    V3 pos = madd(d, b.t, o);
+    const bool sph = (facts & FACT_SPHERE) && kind == RT_PRIM_SPHERE;
+    V3 n;
+    if (SLOT) {
+        const uint32_t axis = (fl & F_AXIS_MASK) >> F_AXIS_SHIFT;
+        if (axis | (fl & F_FRAME_RECT)) gin = dot(d, xyz(Pd)) > 0.0f;
+        pos.x = axis == 1 ? Pa.x : pos.x;
+        pos.y = axis == 2 ? Pa.y : pos.y;
+        pos.z = axis == 3 ? Pa.z : pos.z;
+        n = sph ? (pos - xyz(Pa)) * Pb.y : xyz(Pd);
+    } else {
+        const float4 Pc = P.c;
+        pos = v3(fmaf(Pc.x, Pa.x - pos.x, pos.x), fmaf(Pc.y, Pa.y - pos.y, pos.y), fmaf(Pc.z, Pa.z - pos.z, pos.z));
+        n = madd(pos, Pc.w, xyz(Pd));
+        if (fl & (F_AXIS_MASK | F_FRAME_RECT)) gin = dot(d, xyz(Pd)) > 0.0f;
+    }
+    if ((facts & (FACT_XF | FACT_VN)) && (fl & (F_TRANSFORMED | F_HASNORMALS))) {
+        if (sph) {
+            n = normalize(xf_point(xfs[__float_as_int(Pb.z)].normal, pos));
+        } else if (facts & FACT_VN) {
+            const VnP vn = vnormals + 3 * id;
+            const TestRec R = tests[b.sg >> 1];
+            const float bu = dot4(R.r0, pos);
+            const float bv = dot4(R.r1, pos);
+            n = normalize(madd(xyz(vn[2]), bu + bv, madd(xyz(vn[1]), bv, xyz(vn[0]) * bu)));
+            if (gin) n = v3(__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""));
+        }
+    }
+    const V3 nrm = gin ? -n : n;
+    const bool inside = gin ^ ((fl & F_INVERT) != 0);
+    const unsigned long long tb = (unsigned long long)__double_as_longlong((double)b.t); // fp32 widened exactly
+    out[0] = make_float4(__int_as_float(id), __int_as_float(inside ? 1 : 0), __uint_as_float((unsigned)tb),
+                         __uint_as_float((unsigned)(tb >> 32)));
+    out[1] = make_float4(pos.x, pos.y, pos.z, nrm.x);
+    out[2] = make_float4(nrm.y, nrm.z, 0.0f, 0.0f);
+}
+
+// Brute force (CULL: the grouped order): one ray per lane in a grid-stride loop whose bounds are
+// wave-uniform, so the records arrive through scalar loads as in path_body; then the planes.
+template <bool CULL>
+__global__ void __launch_bounds__(256, CULL ? RT_GROUPED_WAVES : RT_PATH_WAVES) query_brute_kernel(QueryParams p)
+{
+    const auto tests = (const RT_AS_CONST TestRec*)p.tests;
+    const auto rects = (const RT_AS_CONST RectRec*)p.rects;
+    const auto frames = (const RT_AS_CONST FrameRec*)p.frames;
+    const auto boxes = (const RT_AS_CONST BoxRec*)p.frames;
+    const auto groups = (const RT_AS_CONST GroupRec*)p.groups;
+    const auto xf = (const RT_AS_CONST XformF*)p.xf;
+    const auto vnormals = (const RT_AS_CONST float4*)p.vnormals;
+    for (unsigned base = blockIdx.x * 256u; base < p.n; base += gridDim.x * 256u) {
+        const unsigned i = base + threadIdx.x;
+        if (i >= p.n) continue;
+        const QueryRay q = load_query_ray(p.rays, i);
+        Best b{__builtin_huge_valf(), -1};
+        if (q.valid) {
+            unsigned n_flat = 0, n_sph = 0, n_node = 0;
+            trace_brute<CULL, false>(p.scene, groups, tests, rects, frames, boxes, xf, q.o, q.d, -1, b, n_flat, n_sph,
+                                     n_node);
+            const int pln0 = p.scene.n_bvh;
+            for (int k = pln0; k < pln0 + p.scene.n_pln; k++) {
+                const TestRec tr = tests[k];
+                hit_plane<true>(tr, k, q.o, q.d, -1, b);
+            }
+        }
+        query_hit<false>(p.scene.facts, p.prims, p.xf, vnormals, tests, b, q.o, q.d, p.hits + (size_t)kHitRows * i);
+    }
+}
+
+// The wide BVH: trace_rays_kernel's speculative loop (ballot refill, one atomicAdd per 256 rays per
+// wave, LDS stack with the global overflow area), and when a query ends what path_kernel_bvh does
+// then: the outer records, the planes that follow the BVH order, and the hit.
+template <int STACK>
+__global__ void __launch_bounds__(256, RT_BVH_WAVES) query_bvh_kernel(QueryParams p)
+{
+    __shared__ int stack_mem[STACK * 256];
+    const TravStack stk = make_stack(stack_mem, p.stack_ovf);
+    const int lane = threadIdx.x & 63;
+    const RT_AS_CONST TestRec* tests = (const RT_AS_CONST TestRec*)p.tests;
+    const RT_AS_CONST float4* rows = (const RT_AS_CONST float4*)p.rows;
+    const RT_AS_CONST Node4Q* nodes4 = (const RT_AS_CONST Node4Q*)p.nodes4;
+    const RT_AS_CONST XformF* xf = (const RT_AS_CONST XformF*)p.xf;
+    const RT_AS_CONST float4* vnormals = (const RT_AS_CONST float4*)p.vnormals;
+    bool trav = false, more = false, exhausted = false;
+    int ref = 0, sp = 0, pend = -1;
+    unsigned n_tri = 0, n_sph = 0;
+    unsigned idx = 0, pool_next = 0, pool_end = 0; // the wave's pool of ray indices (uniform)
+    V3 o{0, 0, 0}, d{0, 0, 0}, id{0, 0, 0}, oi{0, 0, 0};
+    Best b{__builtin_huge_valf(), -1};
+    while (true) {
+        const bool need = !trav && !exhausted;
+        const unsigned long long m = __ballot(need);
+        if (m) { // lanes without a query take the next rays (one atomic per 256 rays per wave)
+            const unsigned kk = (unsigned)__popcll(m), avail = pool_end - pool_next;
+            unsigned fresh = 0;
+            if (kk > avail) {
+                if (lane == 0) fresh = atomicAdd(p.counter, 256u);
+                fresh = __builtin_amdgcn_readfirstlane(fresh);
+            }
+            if (need) {
+                const unsigned r = (unsigned)__popcll(m & ((1ull << lane) - 1ull));
+                idx = r < avail ? pool_next + r : fresh + (r - avail);
+                if (idx >= p.n) {
+                    exhausted = true;
+                } else {
+                    const QueryRay q = load_query_ray(p.rays, idx);
+                    if (!q.valid) { // a miss; the lane takes another ray at the next refill
+                        store_query_miss(p.hits + (size_t)kHitRows * idx);
+                    } else {
+                        o = q.o;
+                        d = q.d;
+                        id = v3(slab_rcp(d.x), slab_rcp(d.y), slab_rcp(d.z));
+                        oi = o * id;
+                        ref = p.root4;
+                        sp = 0;
+                        pend = -1;
+                        more = p.n_nodes4 > 0; // (no tree at all: only planes, and the query ends at once)
+                        if (ref < 0) {
+                            pend = ~ref;
+                            more = false;
+                        }
+                        b = Best{__builtin_huge_valf(), -1};
+                        trav = true;
+                    }
+                }
+            }
+            if (kk > avail) {
+                pool_next = fresh + (kk - avail);
+                pool_end = fresh + 256u;
+            } else {
+                pool_next += kk;
+            }
+        }
+        if (!__any(trav)) {
+            if (__any(!exhausted)) continue; // only invalid rays this round: refill again
+            break;
+        }
+        const bool can_node = trav && more && ref >= 0;
+        const bool blocked = trav && pend >= 0 && !can_node;
+        const bool leaf_step = __ballot(can_node) == 0 || __popcll(__ballot(blocked)) >= p.spec;
+        if (trav) {
+            if (leaf_step) {
+                if (pend >= 0) {
+                    test_leaf<false>(tests, rows, xf, pend, o, d, -1, b, n_tri, n_sph);
+                    pend = leaf_advance(pend, RT_SPEC_PRIMS);
+                }
+            } else if (can_node) {
+                bool pop = true;
+                const Node4Q node = nodes4[ref];
+                wide_visit<STACK>(node, id, oi, b.t, ref, sp, stk, pop);
+                if (pop) {
+                    if (sp > 0) ref = pop_ref<STACK>(stk, sp);
+                    else more = false;
+                }
+            }
+            if (more && ref < 0 && pend < 0) {
+                pend = ~ref;
+                if (sp > 0) ref = pop_ref<STACK>(stk, sp);
+                else more = false;
+            }
+            if (!more && pend < 0) { // the query ended: the records outside the tree, then its Hit
+                trav = false;
+                if (p.scene.n_groups > 0)
+                    test_outer<false>((const RT_AS_CONST GroupRec*)p.groups, (const RT_AS_CONST RectRec*)p.rects,
+                                      (const RT_AS_CONST BoxRec*)p.frames, o, d, -1, b, n_tri);
+                for (int k = p.scene.n_bvh; k < p.scene.n_bvh + p.scene.n_pln; k++) {
+                    const TestRec tr = tests[k];
+                    hit_plane<true>(tr, k, o, d, -1, b);
+                }
+                query_hit<true>(p.scene.facts, p.prims, p.xf, vnormals, tests, b, o, d, p.hits + (size_t)kHitRows * idx);
+            }
+        }
+    }
+}
+
 // plane: element stride between the R, G and B planes of sum (>= w*h; a gather slot may be taller
 // than the band set written into it)
 __global__ void accumulate_kernel(PathParams p, double* sum, uint32_t* samples, uint32_t* misses, size_t plane)
@@ -2293,6 +2519,29 @@ int trace_rays_blocks_per_cu(int waves)
 hipError_t launch_trace_rays(const TraceRaysParams& p, int waves, int grid_blocks, hipStream_t stream)
 {
     hipLaunchKernelGGL(pick_trace(waves, p.stats != nullptr), dim3(grid_blocks), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+using QueryKernel = void (*)(QueryParams);
+QueryKernel pick_query(int kernel)
+{
+    if (kernel == 3) return query_bvh_kernel<RT_WIDE_STACK>;
+    return kernel == 1 ? query_brute_kernel<true> : query_brute_kernel<false>;
+}
+
+int query_blocks_per_cu(int kernel)
+{
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(pick_query(kernel)), 256, 0) !=
+            hipSuccess ||
+        n < 1)
+        n = 1;
+    return n;
+}
+
+hipError_t launch_query(const QueryParams& p, int kernel, int grid_blocks, hipStream_t stream)
+{
+    hipLaunchKernelGGL(pick_query(kernel), dim3(grid_blocks), dim3(256), 0, stream, p);
     return hipGetLastError();
 }
 

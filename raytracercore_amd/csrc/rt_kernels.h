@@ -132,6 +132,39 @@ struct TraceRaysParams {
 };
 
 #ifndef __HIPCC_RTC__ // host-side launch interface (not part of a hiprtc-compiled kernel)
+// Closest-hit queries over caller-supplied rays (rt_query_rays, RT_QUERY_FAST): the scene as the
+// generic path kernel of the traversal mode walks it (fill_launch; the wide tree from its global
+// nodes, without the hot table) and the ray and hit arrays.
+struct QueryParams {
+    const double2* rays;        // rt_ray: four 16-B rows (origin xy, origin zw, direction xy, direction zw)
+    float4* hits;               // rt_hit: three 16-B rows
+    unsigned int n;
+    unsigned int* counter;      // BVH kernel: ray dispenser (zeroed before the launch)
+    int* stack_ovf;             // BVH kernel: traversal-stack overflow area
+    PathScene scene;            // n_groups, n_bvh, n_pln, facts (the brute-force orders; the BVH order's outer group)
+    const TestRec* tests;
+    const float4* rows;
+    const RectRec* rects;
+    const FrameRec* frames;
+    const PrimF* prims;
+    const GroupRec* groups;
+    const Node4Q* nodes4;
+    const XformF* xf;
+    const float4* vnormals;
+    int root4;
+    int n_nodes4;               // wide nodes (0: root4 names a leaf, or the scene holds only planes)
+    int spec;                   // BVH kernel: blocked lanes that trigger a leaf step (as PathParams.spec)
+};
+constexpr int kHitRows = 3;     // sizeof(rt_hit) / 16
+
+// rt_query_rays: kernel 0 brute force, 1 grouped brute force, 3 the wide BVH (the numbering of
+// path_variant).  query_blocks_per_cu: blocks of 256 per CU the kernel can hold; the brute-force
+// kernels take any grid (grid-stride loop), the BVH kernel deals rays to whatever grid it gets.
+int query_blocks_per_cu(int kernel);
+hipError_t launch_query(const QueryParams& p, int kernel, int grid_blocks, hipStream_t stream);
+// RT_QUERY_EXACT (kernels_exact.hip): the fp64 reference query, one ray per lane; prim_id -2 where
+// the reference BVH is deeper than the kernel's traversal stack.
+hipError_t launch_query_exact(const DevScene& s, const rt_ray* d_rays, unsigned n, rt_hit* d_hits, hipStream_t stream);
 // Sets p.scene and the record pointers of the given kernel variant's slot order.
 void fill_launch(const DevScene& s, int variant, PathParams& p);
 

@@ -101,4 +101,22 @@ RT_HDI bool aabb_hit_ref(Vec4d mn, Vec4d mx, Vec4d o, Vec4d d, double& nr, doubl
     return true;
 }
 
+// camera.GetRay(x, y).Offset(camera.imagePlane) (DebugRaycaster.cs:241; FrustumCamera.cs:33-41;
+// OrthoCamera.cs:33-38) from the post-InitRender state: the one copy the exact kernel
+// (kernels_exact.hip) and the host's rt_camera_rays (api_query.hip) share.
+RT_HDI void camera_ray_d(const CameraD& c, double x, double y, Vec4d& o, Vec4d& d)
+{
+    if (c.kind == RT_CAMERA_FRUSTUM) {
+        double ox = c.tan_x * ((x - c.w2) / c.w2);
+        double oy = c.tan_y * ((y - c.h2) / c.h2);
+        Vec4d dir = add(add(c.look, scale(c.side, ox)), scale(c.up, oy));
+        o = c.position;
+        d = normalize_v(dir);
+    } else {
+        o = add(add(c.position, scale(c.side, (x - c.w2) * c.h_mult)), scale(c.up, (y - c.h2) * c.v_mult));
+        d = normalize_v(c.look);
+    }
+    o = add(o, scale(d, c.image_plane)); // Ray.Offset (Ray.cs:59-62)
+}
+
 } // namespace rtc

@@ -1,5 +1,5 @@
 // rt_scene.h -- the scene object behind the C ABI and what the API's translation units share
-// (rtcore_api.hip, scene_upload.hip, api_frame.hip, api_debug.hip).
+// (rtcore_api.hip, scene_upload.hip, api_frame.hip, api_debug.hip, api_query.hip).
 #pragma once
 #include <algorithm>
 #include <array>
@@ -179,6 +179,10 @@ struct rt_scene {
     std::array<hipEvent_t, kCopyChunks> band_ev{};
     DevBuf<uint32_t> samples, misses;
     DevBuf<int32_t> ids;
+    // rt_query_rays: two chunks of rays and of hits, and the events of the chunks' uploads
+    DevBuf<rt_ray> query_rays;
+    DevBuf<rt_hit> query_hits;
+    std::array<hipEvent_t, 2> query_up_ev{};
     bool stats_on = false;      // launch the instrumented kernel (rt_scene_set_stats)
     float4* ray_log = nullptr;  // rt_debug_ray_log (instrumented BVH launches)
     unsigned int* ray_log_n = nullptr;
@@ -228,6 +232,8 @@ struct rt_scene {
         for (hipEvent_t e : copy_ev)
             if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : band_ev)
+            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : query_up_ev)
             if (e) (void)hipEventDestroy(e);
         if (copy_stream) {
             (void)hipStreamSynchronize(copy_stream);
