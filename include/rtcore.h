@@ -44,7 +44,8 @@ extern "C" {
                                 5: rt_frame_submit / rt_frame_collect / rt_frame_inject_fault;
                                 6: rt_trace_paths, rt_debug_ray, rt_bounce_type; rt_query_rays, rt_query_rays_device
                                    and rt_camera_rays were added under version 6 (purely additive): a host
-                                   detects them by symbol */
+                                   detects them by symbol; so were rt_select_pixels, rt_select_pixels_device,
+                                   rt_select_rays, rt_select_rays_device and rt_debug_select_rays */
 
 typedef enum rt_status {
     RT_OK = 0,
@@ -425,6 +426,61 @@ int rt_query_rays_device(rt_scene* scene, int32_t mode, const rt_ray* d_rays, in
    outside the frame. */
 int rt_camera_rays(const rt_camera* camera, int32_t width, int32_t height, int32_t x0, int32_t y0, int32_t w,
                    int32_t h, rt_ray* out);
+
+/* ------------------------------------------------------------ selection pass --- */
+/* DebugRaycaster's Selection mode (DebugRaycaster.cs:174-192): the overlay that shows only what
+ * SceneInspector handed to SetDisplayOnly.  One ray per pixel (or per caller's ray) is tested against
+ * every item of a list, in list order:
+ *     dist = +inf; winner = none
+ *     for each item: curD = item.Intersect(ray); if (curD <= dist) { dist = curD; winner = item }
+ * so NaN never wins, the later of two items at equal distances wins, and +inf wins over "none".
+ *   RT_SELECT_PRIM  PrimitiveIntersector: Primitive.RayTrace(ray, null) of primitive `index` (its
+ *                   Primitive.ID, insertion order) with its two-sided / invert culling; Hit.Distance,
+ *                   NaN on a miss.  No bounding box is tested first.
+ *   RT_SELECT_NODE  BVHIntersector: AABB.IntersectAVX of the box of node `index` of the reference BVH
+ *                   in depth-first pre-order (node, left subtree, right subtree: the index of its box
+ *                   in rt_ref_bvh_export's `boxes`); near when near >= 0, else far (the origin inside
+ *                   the box), NaN on a miss.  SkipVolume nodes are tested like every other.
+ * All in fp64, in the reference's rounding order: the reference's own answer bit for bit. */
+typedef enum rt_select_kind { RT_SELECT_PRIM = 0, RT_SELECT_NODE = 1 } rt_select_kind;
+typedef struct rt_select_item { int32_t kind, index; } rt_select_item; /* 8 B */
+/* 16 B, one 16-byte row:
+ *   0  item      index in the caller's list of the winner, -1 when nothing won
+ *   4  reserved  0
+ *   8  distance  the winning curD (may be +inf), 0 when nothing won */
+typedef struct rt_selection { int32_t item, reserved; double distance; } rt_selection;
+/* Most item tests (w * h * n_items, or n * n_items) of one call. */
+#define RT_SELECT_MAX_TESTS (1ull << 32)
+
+/*
+ * rt_select_pixels*: the rays of rt_primary_ids (Camera.GetRay(x, y).Offset(imagePlane) at the integer
+ * pixels of the tile; a camera must be set).  Host output out[x*h + y], device output d_out[y*w + x].
+ * rt_select_rays*: rays the caller brings, out[i] answers rays[i]; a ray with a non-finite component
+ * or a zero direction gives item -1 (the rule of rt_query_rays).  No camera is needed.
+ * `items` is always a host array of n_items records; the library copies it to the device.  n_items == 0
+ * is valid (item -1 everywhere); n == 0 returns RT_OK and touches nothing.  RT_ERR_ARG, before anything
+ * is launched, for a null pointer, n_items < 0, n < 0, an unknown kind, a primitive index outside
+ * [0, n_prims), a node index outside the reference BVH, a tile outside the frame, or more than
+ * RT_SELECT_MAX_TESTS item tests.  The reference BVH is built (on first use) only when a node item is
+ * present.  The counters of rt_scene_get_stats, an armed rt_debug_ray_log, rt_kernel_times and the
+ * scene-specialised kernels are left as they were.
+ * The host-buffer entry points are synchronous, on the scene's own stream (rt_select_rays in chunks of
+ * at most 2^19 rays); the _device ones take device buffers and are asynchronous on `stream` (a
+ * hipStream_t, NULL = the default stream), ordered like the device-resident renders.
+ */
+int rt_select_pixels(rt_scene* scene, const rt_select_item* items, int32_t n_items, int32_t x0, int32_t y0, int32_t w,
+                     int32_t h, rt_selection* out);
+int rt_select_pixels_device(rt_scene* scene, const rt_select_item* items, int32_t n_items, int32_t x0, int32_t y0,
+                            int32_t w, int32_t h, rt_selection* d_out, void* stream);
+int rt_select_rays(rt_scene* scene, const rt_select_item* items, int32_t n_items, const rt_ray* rays, int64_t n,
+                   rt_selection* out);
+int rt_select_rays_device(rt_scene* scene, const rt_select_item* items, int32_t n_items, const rt_ray* d_rays, int64_t n,
+                          rt_selection* d_out, void* stream);
+/* Host only, no device: rt_select_rays for the scene these primitives make, by the same per-item
+   functions and the same fold compiled for the CPU (the reference BVH is built when a node item asks
+   for it).  RT_ERR_ARG as rt_select_rays, and for n_prims < 0 or an unknown primitive kind. */
+int rt_debug_select_rays(const rt_prim* prims, int32_t n_prims, const rt_select_item* items, int32_t n_items,
+                         const rt_ray* rays, int64_t n, rt_selection* out);
 
 /* -------------------------------------------------- device-resident renders --- */
 /*

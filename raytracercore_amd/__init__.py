@@ -45,6 +45,8 @@ class rt_query_mode(enum.IntEnum):
 
 
 RT_QUERY_FAST, RT_QUERY_EXACT = int(rt_query_mode.RT_QUERY_FAST), int(rt_query_mode.RT_QUERY_EXACT)
+RT_SELECT_PRIM, RT_SELECT_NODE = 0, 1  # rt_select_kind: a primitive ID / a reference-BVH node in pre-order
+RT_SELECT_MAX_TESTS = 1 << 32  # item tests (pixels or rays x items) of one selection call
 BUILD_STAT_NAMES = ("prepare_ms", "bvh_ms", "upload_ms", "gpu_build_ms", "ploc_rounds", "wide_nodes", "stack_need",
                     "flat_rects", "flat_boxes", "flat_frames", "flat_frame_boxes", "flat_frame_rects", "flat_tris",
                     "flat_spheres", "hot_nodes", "jit_status", "jit_compile_ms", "jit_cached", "group_max",
@@ -145,6 +147,19 @@ class rt_hit(C.Structure):
     ]
 
 
+class rt_select_item(C.Structure):
+    """One item of a selection list: (rt_select_kind, Primitive.ID or reference-BVH node index), 8 B."""
+    _fields_ = [("kind", C.c_int32), ("index", C.c_int32)]
+
+
+class rt_selection(C.Structure):
+    """One answer of the selection pass: the winner's index in the caller's list (-1: none), 0, its distance; 16 B."""
+    _fields_ = [("item", C.c_int32), ("reserved", C.c_int32), ("distance", C.c_double)]
+
+
+SELECT_ITEM_DTYPE = np.dtype([("kind", np.int32), ("index", np.int32)])
+SELECTION_DTYPE = np.dtype([("item", np.int32), ("reserved", np.int32), ("distance", np.float64)])
+
 # the same records as numpy structured dtypes (GpuRaytracer.query_rays, camera_rays)
 RAY_DTYPE = np.dtype([("origin", np.float64, (4,)), ("direction", np.float64, (4,))])
 HIT_DTYPE = np.dtype([
@@ -154,7 +169,8 @@ HIT_DTYPE = np.dtype([
 
 # entry points added under an unchanged ABI version: bound when the library has them (an older build
 # named by RTCORE_LIB may not)
-_OPTIONAL = ("rt_query_rays", "rt_query_rays_device", "rt_camera_rays")
+_OPTIONAL = ("rt_query_rays", "rt_query_rays_device", "rt_camera_rays", "rt_select_pixels", "rt_select_pixels_device",
+             "rt_select_rays", "rt_select_rays_device")
 
 _lib: Optional[C.CDLL] = None
 
@@ -246,6 +262,13 @@ def load_library(path: str = "") -> C.CDLL:
         "rt_query_rays": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
         "rt_query_rays_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
         "rt_camera_rays": (C.c_int, [P(rt_camera)] + [C.c_int32] * 6 + [C.c_void_p]),
+        "rt_select_pixels": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p]),
+        "rt_select_pixels_device": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p]),
+        "rt_select_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+        "rt_select_rays_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                            C.c_void_p]),
+        "rt_debug_select_rays": (C.c_int, [P(rt_prim), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
+                                           C.c_void_p]),
     }
     for name, (res, args) in sig.items():
         if (name.startswith("rt_debug_") or name in _OPTIONAL) and not hasattr(lib, name):
@@ -405,6 +428,43 @@ def _pack_rays(origins, directions) -> np.ndarray:
     rays["origin"][:, :o.shape[1]] = o
     rays["direction"][:, :d.shape[1]] = d
     return rays
+
+
+def _pack_items(items) -> np.ndarray:
+    """A selection list -- an (n, 2) int array, a sequence of (kind, index) pairs or a SELECT_ITEM_DTYPE
+    array -- as a contiguous SELECT_ITEM_DTYPE array."""
+    if isinstance(items, np.ndarray) and items.dtype == SELECT_ITEM_DTYPE:
+        return np.ascontiguousarray(items.reshape(-1))
+    a = np.asarray(items, np.int64)
+    if a.size == 0:
+        return np.zeros(0, SELECT_ITEM_DTYPE)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError("items must be an (n, 2) int array or a sequence of (kind, index) pairs")
+    if a.min() < -2 ** 31 or a.max() >= 2 ** 31:
+        raise ValueError("items: kind and index must fit in int32")
+    out = np.zeros(a.shape[0], SELECT_ITEM_DTYPE)
+    out["kind"], out["index"] = a[:, 0], a[:, 1]
+    return out
+
+
+def _rays_arg(origins, directions) -> np.ndarray:
+    return np.ascontiguousarray(origins, RAY_DTYPE) if directions is None else _pack_rays(origins, directions)
+
+
+def select_rays_host(prims: Sequence[rt_prim], items, origins, directions=None) -> np.ndarray:
+    """rt_debug_select_rays (host code, no GPU): GpuRaytracer.select_rays for the scene these primitives
+    make, by the same fold compiled for the CPU.  Returns a SELECTION_DTYPE array of the rays' shape."""
+    lib = load_library()
+    if not hasattr(lib, "rt_debug_select_rays"):
+        raise RtError("this build of the library has no rt_debug_select_rays")
+    n = len(prims)
+    arr = prims if isinstance(prims, C.Array) and n > 0 else (rt_prim * max(1, n))(*prims)
+    it = _pack_items(items)
+    rays = _rays_arg(origins, directions)
+    out = np.zeros(rays.shape, SELECTION_DTYPE)
+    _check(lib.rt_debug_select_rays(arr, n, it.ctypes.data_as(C.c_void_p), it.size, rays.ctypes.data_as(C.c_void_p),
+                                    rays.size, out.ctypes.data_as(C.c_void_p)))
+    return out
 
 
 class GpuRaytracer:
@@ -578,6 +638,44 @@ class GpuRaytracer:
         d_hits (e.g. torch data_ptr()) on `stream` (a hipStream_t as an integer, 0 = the default stream)."""
         _check(self.lib.rt_query_rays_device(self.handle, RT_QUERY_EXACT if exact else RT_QUERY_FAST, C.c_void_p(d_rays),
                                              n, C.c_void_p(d_hits), C.c_void_p(stream)))
+
+    def select_pixels(self, items, x0: int = 0, y0: int = 0, w: Optional[int] = None,
+                      h: Optional[int] = None) -> np.ndarray:
+        """rt_select_pixels (DebugRaycaster Selection mode): per pixel of the tile, which item of the list
+        -- (kind, index) pairs, RT_SELECT_PRIM with a Primitive.ID or RT_SELECT_NODE with a reference-BVH
+        node's pre-order index -- the primary ray meets nearest, the later of two at equal distances.
+        Returns a SELECTION_DTYPE array indexed [x, y]; item -1 where nothing is met."""
+        w = self.width - x0 if w is None else w
+        h = self.height - y0 if h is None else h
+        it = _pack_items(items)
+        out = np.zeros((max(w, 0), max(h, 0)), SELECTION_DTYPE)
+        _check(self.lib.rt_select_pixels(self.handle, it.ctypes.data_as(C.c_void_p), it.size, x0, y0, w, h,
+                                         out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def select_pixels_device(self, items, x0: int, y0: int, w: int, h: int, d_out: int, stream: int = 0) -> None:
+        """rt_select_pixels_device: asynchronous selection pass over the tile into w*h rt_selection at device
+        pointer d_out, row-major (y*w + x), on `stream` (a hipStream_t as an integer, 0 = the default stream)."""
+        it = _pack_items(items)
+        _check(self.lib.rt_select_pixels_device(self.handle, it.ctypes.data_as(C.c_void_p), it.size, x0, y0, w, h,
+                                                C.c_void_p(d_out), C.c_void_p(stream)))
+
+    def select_rays(self, items, origins, directions=None) -> np.ndarray:
+        """rt_select_rays: the selection fold for the caller's rays (given as for query_rays).  Returns a
+        SELECTION_DTYPE array of the rays' shape; item -1 where nothing is met or the ray is invalid."""
+        it = _pack_items(items)
+        rays = _rays_arg(origins, directions)
+        out = np.zeros(rays.shape, SELECTION_DTYPE)
+        _check(self.lib.rt_select_rays(self.handle, it.ctypes.data_as(C.c_void_p), it.size,
+                                       rays.ctypes.data_as(C.c_void_p), rays.size, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def select_rays_device(self, items, d_rays: int, n: int, d_out: int, stream: int = 0) -> None:
+        """rt_select_rays_device: asynchronous selection of n rt_ray at device pointer d_rays into n
+        rt_selection at d_out on `stream`; `items` is a host list, copied to the device by the call."""
+        it = _pack_items(items)
+        _check(self.lib.rt_select_rays_device(self.handle, it.ctypes.data_as(C.c_void_p), it.size, C.c_void_p(d_rays),
+                                              n, C.c_void_p(d_out), C.c_void_p(stream)))
 
     def camera_rays(self, x0: int = 0, y0: int = 0, w: Optional[int] = None, h: Optional[int] = None) -> np.ndarray:
         """camera_rays for this scene's camera and frame size."""

@@ -8,117 +8,14 @@
 // `Near > previous.Far` early break and the strict `<` replacement, with
 // Primitive.RayTrace (Primitive.cs:46-75) over Triangle.RayTraceAVXFaster
 // (Triangle.cs:77-146), Sphere.RayTraceAVX (Sphere.cs:50-155) and Plane.DoRayTrace
-// (Plane.cs:36-66).  Every operation keeps the reference's order and FMA use, and the file
+// (Plane.cs:36-66), which rt_exact_prims.h holds together with the Selection mode's fold
+// (the selection kernels below).  Every operation keeps the reference's order and FMA use, and the file
 // is compiled with -ffp-contract=off, so the result is bit-identical to an fp64 host
 // restatement on the same inputs.
 #include "rt_kernels.h"
-#include "rt_refmath.h"
+#include "rt_exact_prims.h"
 
 namespace rtc {
-
-struct HitD {
-    int prim;
-    double dist;
-    bool inside;
-};
-
-__device__ static int tri_trace_d(const PrimD& p, Vec4d o, Vec4d d, HitD* out)
-{
-    Vec4d off = sub(o, p.a);
-    Vec4d s1 = cross_fma(off, p.b);
-    Vec4d s2 = cross_fma(d, p.c);
-    double uu = hsum(mul(off, s2)), vv = hsum(mul(d, s1)), tt = hsum(mul(p.c, s1)), det = hsum(mul(p.b, s2));
-    double inv = 1.0 / det;
-    double invz = (inv == inv) ? inv : 0.0;
-    double u = uu * invz, v = vv * invz, t = tt * invz;
-    bool rej = (u < 0) | (v < 0);
-    if (p.flags & F_MIRROR)
-        rej |= (u > 1) | (v > 1);
-    else
-        rej |= ((u + v) > 1);
-    rej |= (t < 0);
-    if (rej) return 0;
-    out[0].dist = t;
-    out[0].inside = invz < 0;
-    return 1;
-}
-
-__device__ static int sphere_trace_d(const PrimD& p, const XformD* xf, Vec4d o, Vec4d d, HitD* out)
-{
-    Vec4d oo = o, od = d;
-    const bool tr = (p.flags & F_TRANSFORMED) != 0;
-    if (tr) {
-        oo = mat_vec(xf[p.xf].to_world, o);
-        od = normalize_v(mat_vec(xf[p.xf].to_world, d));
-    }
-    Vec4d off = sub(oo, p.a);
-    double b = -2 * dot_v(off, od);
-    double c = dot_v(off, off) - p.b.y;
-    double radix = sqrt((b * b) - (4 * c));
-    double dfar = (b + radix) / 2, dclose = (b - radix) / 2;
-    if (tr) {
-        Vec4d pfar = mat_vec(xf[p.xf].to_obj, fma4(dfar, od, oo));
-        Vec4d pclose = mat_vec(xf[p.xf].to_obj, fma4(dclose, od, oo));
-        dfar = dot_v(d, sub(pfar, o));
-        dclose = dot_v(d, sub(pclose, o));
-    }
-    if (!(dfar >= 0)) return 0;
-    if (!(dclose >= 0)) {
-        out[0] = HitD{0, dfar, true};
-        return 1;
-    }
-    out[0] = HitD{0, dclose, false};
-    out[1] = HitD{0, dfar, true};
-    return 2;
-}
-
-__device__ static bool nearly_equal_d(double a, double b, double delta) // Util.cs:41-51
-{
-    const double min_normal = 4.9406564584124654e-324 * 1e7;
-    if (delta == 0) return true;
-    delta = fabs(delta);
-    return delta <= min_normal || delta / net_max(a, b) < 1e-24;
-}
-
-__device__ static int plane_trace_d(const PrimD& p, Vec4d o, Vec4d d, HitD* out)
-{
-    double ray_dist = dot_s(o, p.a);
-    double denom = dot_s(d, p.a);
-    const double od = p.b.x;
-    if (nearly_equal_d(denom, 0, denom - 0) && nearly_equal_d(od, ray_dist, od - ray_dist)) {
-        out[0] = HitD{0, 0.0, true};
-        return 1;
-    }
-    if (denom == 0) return 0;
-    double dist = (od - ray_dist) / denom;
-    if (dist >= -1e-24) {
-        Vec4d hp = add(o, scale(d, dist));
-        out[0] = HitD{0, length_s(sub(hp, o)), dot_s(p.a, d) > 0};
-        return 1;
-    }
-    return 0;
-}
-
-// Primitive.RayTrace with a null skip hit (primary rays): first hit that survives culling.
-__device__ static bool prim_raytrace_d(const DevScene& s, int pi, Vec4d o, Vec4d d, HitD& h)
-{
-    const PrimD& p = s.prims_d[pi];
-    HitD hits[2];
-    int n;
-    switch (p.flags & KIND_MASK) {
-    case RT_PRIM_TRIANGLE: n = tri_trace_d(p, o, d, hits); break;
-    case RT_PRIM_SPHERE: n = sphere_trace_d(p, s.xf_d, o, d, hits); break;
-    default: n = plane_trace_d(p, o, d, hits); break;
-    }
-    for (int i = 0; i < n; i++) {
-        bool inside = hits[i].inside;
-        if (p.flags & F_INVERT) inside = !inside;
-        if (inside && !(p.flags & F_TWOSIDED)) continue;
-        h = HitD{pi, hits[i].dist, inside};
-        return true;
-    }
-    return false;
-}
 
 constexpr int kLeafCap = 64;
 constexpr int kStackCap = 96;
@@ -324,6 +221,58 @@ __global__ void __launch_bounds__(64) query_exact_kernel(DevScene s, const doubl
     hits[3 * (size_t)i] = make_uint4((unsigned)id, h.inside ? 1u : 0u, (unsigned)db, (unsigned)(db >> 32));
     hits[3 * (size_t)i + 1] = make_uint4(0u, 0u, 0u, 0u);
     hits[3 * (size_t)i + 2] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+// DebugRaycaster Selection mode (rt_select_pixels, rt_select_rays): select_items (rt_exact_prims.h)
+// for one ray per lane.  The item loop is the same for every lane of the wave (no early exit, no
+// LDS); a result is one 16-B row (rt_selection: item, 0, distance), written with one store.
+__device__ static void store_selection(uint4* out, size_t i, const rt_selection& r)
+{
+    const unsigned long long db = (unsigned long long)__double_as_longlong(r.distance);
+    out[i] = make_uint4((unsigned)r.item, 0u, (unsigned)db, (unsigned)(db >> 32));
+}
+
+__global__ void __launch_bounds__(64) select_pixels_kernel(DevScene s, CameraD cam, const rt_select_item* __restrict__ items,
+                                                           int n_items, int x0, int y0, int w, int h, uint4* __restrict__ out)
+{
+    int x = blockIdx.x * 8 + (threadIdx.x & 7);
+    int y = blockIdx.y * 8 + (threadIdx.x >> 3);
+    if (x >= w || y >= h) return;
+    Vec4d o, d;
+    camera_ray_d(cam, (double)(x0 + x), (double)(y0 + y), o, d);
+    store_selection(out, (size_t)y * w + x, select_items(s, items, n_items, o, d));
+}
+
+__global__ void __launch_bounds__(64) select_rays_kernel(DevScene s, const rt_select_item* __restrict__ items, int n_items,
+                                                         const double2* __restrict__ rays, unsigned n, uint4* __restrict__ out)
+{
+    const unsigned i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    const double2 r0 = rays[4 * (size_t)i], r1 = rays[4 * (size_t)i + 1], r2 = rays[4 * (size_t)i + 2],
+                  r3 = rays[4 * (size_t)i + 3];
+    const Vec4d o{r0.x, r0.y, r1.x, r1.y}, d{r2.x, r2.y, r3.x, r3.y};
+    rt_selection r{-1, 0, 0.0};
+    if (ray_valid_d(o, d)) r = select_items(s, items, n_items, o, d);
+    store_selection(out, i, r);
+}
+
+hipError_t launch_select_pixels(const DevScene& s, const CameraD& cam, const rt_select_item* d_items, int n_items, int x0,
+                                int y0, int w, int h, rt_selection* d_out, hipStream_t stream)
+{
+    static_assert(sizeof(rt_selection) == 16 && sizeof(rt_select_item) == 8, "rt_selection is one 16-B row");
+    dim3 grid((w + 7) / 8, (h + 7) / 8);
+    hipLaunchKernelGGL(select_pixels_kernel, grid, dim3(64), 0, stream, s, cam, d_items, n_items, x0, y0, w, h,
+                       reinterpret_cast<uint4*>(d_out));
+    return hipGetLastError();
+}
+
+hipError_t launch_select_rays(const DevScene& s, const rt_select_item* d_items, int n_items, const rt_ray* d_rays,
+                              unsigned n, rt_selection* d_out, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(select_rays_kernel, dim3((n + 63u) / 64u), dim3(64), 0, stream, s, d_items, n_items,
+                       reinterpret_cast<const double2*>(d_rays), n, reinterpret_cast<uint4*>(d_out));
+    return hipGetLastError();
 }
 
 hipError_t launch_query_exact(const DevScene& s, const rt_ray* d_rays, unsigned n, rt_hit* d_hits, hipStream_t stream)

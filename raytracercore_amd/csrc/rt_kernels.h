@@ -172,6 +172,14 @@ void fill_launch(const DevScene& s, int variant, PathParams& p);
 hipError_t launch_primary_ids(const DevScene& s, const CameraD& cam, int x0, int y0, int w, int h, int mode,
                               int32_t* d_ids, hipStream_t stream);
 
+// DebugRaycaster Selection mode (kernels_exact.hip): the fold of rt_exact_prims.h's select_items over
+// n_items device-resident items, for the camera's pixels of a tile (d_out row-major, y*w + x) or for
+// n <= 2^32 - 64 caller-supplied rays (d_out by ray).
+hipError_t launch_select_pixels(const DevScene& s, const CameraD& cam, const rt_select_item* d_items, int n_items, int x0,
+                                int y0, int w, int h, rt_selection* d_out, hipStream_t stream);
+hipError_t launch_select_rays(const DevScene& s, const rt_select_item* d_items, int n_items, const rt_ray* d_rays,
+                              unsigned n, rt_selection* d_out, hipStream_t stream);
+
 // Kernel variant: kernel 0 brute force, 1 grouped brute force, 2 BVH2 (24-entry stack), 3 wide BVH
 // (RT_WIDE_STACK = 16-entry stack), both + kStackOverflow entries in global memory;
 // lds stages the shading records in LDS.

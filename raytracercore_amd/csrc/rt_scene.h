@@ -1,5 +1,5 @@
 // rt_scene.h -- the scene object behind the C ABI and what the API's translation units share
-// (rtcore_api.hip, scene_upload.hip, api_frame.hip, api_debug.hip, api_query.hip).
+// (rtcore_api.hip, scene_upload.hip, api_frame.hip, api_debug.hip, api_query.hip, api_select.hip).
 #pragma once
 #include <algorithm>
 #include <array>
@@ -183,6 +183,11 @@ struct rt_scene {
     DevBuf<rt_ray> query_rays;
     DevBuf<rt_hit> query_hits;
     std::array<hipEvent_t, 2> query_up_ev{};
+    // the selection pass (api_select.hip): the caller's item list on the device, and the host-buffer
+    // entry points' rays (one chunk) and results
+    DevBuf<rt_select_item> select_items;
+    DevBuf<rt_ray> select_rays;
+    DevBuf<rt_selection> select_out;
     bool stats_on = false;      // launch the instrumented kernel (rt_scene_set_stats)
     float4* ray_log = nullptr;  // rt_debug_ray_log (instrumented BVH launches)
     unsigned int* ray_log_n = nullptr;

@@ -27,6 +27,41 @@ float as_f(uint32_t v)
     return f;
 }
 
+void make_exact_records(const std::vector<HostPrim>& H, std::vector<PrimD>& pd, std::vector<XformD>& xd)
+{
+    const int n = (int)H.size();
+    pd.resize(n);
+    xd.clear();
+    for (int i = 0; i < n; i++) {
+        const HostPrim& p = H[i];
+        PrimD& d = pd[i];
+        std::memset(&d, 0, sizeof d);
+        d.flags = p.flags;
+        d.xf = -1;
+        if (p.kind == RT_PRIM_TRIANGLE) {
+            d.a = p.v[0];
+            d.b = p.e01;
+            d.c = p.e02;
+            d.d = p.n;
+            for (int k = 0; k < 3; k++) d.vn[k] = p.vn[k];
+        } else if (p.kind == RT_PRIM_SPHERE) {
+            d.a = p.center;
+            d.b = v4d(p.radius, p.radius_sqr, 0, 0);
+            if (p.flags & F_TRANSFORMED) {
+                d.xf = (int)xd.size(); // = xf_index[i]: both sets list the transformed spheres in ID order
+                XformD X;
+                std::memcpy(X.to_world, p.to_world, sizeof X.to_world);
+                std::memcpy(X.to_obj, p.to_obj, sizeof X.to_obj);
+                std::memcpy(X.to_normal, p.to_normal, sizeof X.to_normal);
+                xd.push_back(X);
+            }
+        } else {
+            d.a = p.pn;
+            d.b = v4d(p.pd, 0, 0, 0);
+        }
+    }
+}
+
 namespace {
 
 double luminance(rt_color c) { return 0.299 * c.r + 0.587 * c.g + 0.114 * c.b; } // DoubleColor.cs:76-79

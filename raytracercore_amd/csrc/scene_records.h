@@ -12,6 +12,9 @@ TestRec make_testrec(const std::vector<HostPrim>& H, const std::vector<int>& xf_
 float as_f(int v); // the bits of v as a float
 float as_f(uint32_t v);
 float4 f4(Vec4d v, float w);
+// The exact fp64 set (rt_internal.h): one PrimD per primitive ID, one XformD per transformed sphere.
+// Shared by the scene upload and the host twin of the selection pass (rt_debug_select_rays).
+void make_exact_records(const std::vector<HostPrim>& H, std::vector<PrimD>& pd, std::vector<XformD>& xd);
 
 // The brute-force slot orders of a scene (flat and grouped), built on the host only: world
 // rectangles, closed and open boxes, frames, triangles, spheres and planes.

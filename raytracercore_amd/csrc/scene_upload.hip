@@ -123,40 +123,13 @@ int upload_scene(rt_scene* s)
     const std::vector<int>& xf_index = rec.xf_index;
     const std::vector<XformF>& xf = rec.xf;
     // --- exact fp64 set
-    std::vector<PrimD> pd(n);
+    std::vector<PrimD> pd;
     std::vector<XformD> xd;
+    make_exact_records(H, pd, xd);
     std::vector<float4> vn((size_t)std::max(1, n) * 3, make_float4(0, 0, 0, 0));
-    for (int i = 0; i < n; i++) {
-        const HostPrim& p = H[i];
-        PrimD& d = pd[i];
-        std::memset(&d, 0, sizeof d);
-        d.flags = p.flags;
-        d.xf = -1;
-        if (p.kind == RT_PRIM_TRIANGLE) {
-            d.a = p.v[0];
-            d.b = p.e01;
-            d.c = p.e02;
-            d.d = p.n;
-            for (int k = 0; k < 3; k++) {
-                d.vn[k] = p.vn[k];
-                vn[3 * i + k] = f4(p.vn[k], 0.0f);
-            }
-        } else if (p.kind == RT_PRIM_SPHERE) {
-            d.a = p.center;
-            d.b = v4d(p.radius, p.radius_sqr, 0, 0);
-            if (p.flags & F_TRANSFORMED) {
-                d.xf = (int)xd.size(); // = xf_index[i]: both sets list the transformed spheres in ID order
-                XformD X;
-                std::memcpy(X.to_world, p.to_world, sizeof X.to_world);
-                std::memcpy(X.to_obj, p.to_obj, sizeof X.to_obj);
-                std::memcpy(X.to_normal, p.to_normal, sizeof X.to_normal);
-                xd.push_back(X);
-            }
-        } else {
-            d.a = p.pn;
-            d.b = v4d(p.pd, 0, 0, 0);
-        }
-    }
+    for (int i = 0; i < n; i++)
+        if (H[i].kind == RT_PRIM_TRIANGLE)
+            for (int k = 0; k < 3; k++) vn[3 * i + k] = f4(H[i].vn[k], 0.0f);
     auto primf = [&](int i) { return make_primf(H, xf_index, i); };
     auto testrec = [&](int i) { return make_testrec(H, xf_index, i); };
     BruteOrders& orders = rec.orders;
