@@ -45,7 +45,8 @@ extern "C" {
                                 6: rt_trace_paths, rt_debug_ray, rt_bounce_type; rt_query_rays, rt_query_rays_device
                                    and rt_camera_rays were added under version 6 (purely additive): a host
                                    detects them by symbol; so were rt_select_pixels, rt_select_pixels_device,
-                                   rt_select_rays, rt_select_rays_device and rt_debug_select_rays */
+                                   rt_select_rays, rt_select_rays_device and rt_debug_select_rays, and
+                                   rt_render_rays and rt_render_rays_device */
 
 typedef enum rt_status {
     RT_OK = 0,
@@ -494,6 +495,68 @@ int rt_debug_select_rays(const rt_prim* prims, int32_t n_prims, const rt_select_
 int rt_render_device(rt_scene* scene, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t spp,
                      uint64_t seed, uint64_t sample_base, double* d_sum, uint32_t* d_samples,
                      uint32_t* d_misses, unsigned long long* d_rays, void* stream);
+
+/* ------------------------------------------------------------ radiance queries --- */
+/*
+ * Raytracer.GetColor(ray) (Raytracer.cs:248-252, the bounce loop of :65-246) for rays the caller
+ * brings: spp path-traced samples of every ray, by the fp32 path kernels in the scene's traversal mode
+ * (BRUTE, GROUPED or BVH with either builder; RT_ERR_STATE on a BVH2 scene, as RT_QUERY_FAST), always
+ * the generic kernels, whatever rt_set_jit says.  A probe, a bake, or a camera the library does not
+ * have (equirectangular, fisheye, a stereo pair, a lens model of the host's own).  No camera is needed.
+ *
+ * Accumulation is SampleSet's, exactly as rt_render_tile / rt_render_device define it, with "pixel"
+ * replaced by "ray i"; everything is added to, not written:
+ *   sum_rgb[i] += the colours of the samples of rays[i] that are not primary misses
+ *   samples[i] += the count of those samples
+ *   misses[i]  += the samples whose bounce 0 misses (DoubleColor.Placeholder, Raytracer.cs:86-87)
+ *   rays_out / d_rays_count (may be NULL) += the Scene.RayTrace equivalents, in rt_render_tile's unit
+ * Device layout: d_sum is three planes R | G | B of n doubles each; d_samples, d_misses n each.
+ *
+ * The ray follows rt_ray's contract: the direction is already normalised and is taken as given.  Origin
+ * and direction are rounded to fp32 component by component (the rule of RT_QUERY_FAST) and traced as
+ * bounce 0.  Nothing normalises them: Ray.Directional at i = 0 (Raytracer.cs:74-75) is the caller's job,
+ * as the camera's ray is normalised once where it is made; the renormalisations of the rays that leave
+ * bounces 2, 5, ... (traced as bounces 3, 6, ...) stay as they are.  A ray with a non-finite component
+ * or a zero direction is a primary miss for all spp samples (the rule of rt_query_rays) and adds nothing
+ * to the ray count.
+ *
+ * The random stream (normative): sample k of ray i draws from
+ *     rt_rng_init(seed, stream_base + i, sample_base + k)      (rtcore_rng.h)
+ * with the first two draws discarded -- the two GetCameraRay spends on subX and subY (Raytracer.cs:264-265),
+ * which a caller's ray has no use for -- and the bounce draws following in rtcore_rng.h's order.  So
+ *   - a ray's result depends only on (seed, stream_base + i, the sample indices, the ray) and on the
+ *     scene's traversal mode: not on n, on the ray's position in the list, on the host entry's chunking
+ *     or on the wave it lands in (the samples per work item are a function of spp alone);
+ *   - for a camera without depth of field, the bounce-0 ray rt_trace_paths reports for sample k of frame
+ *     pixel (x, y) (fp32 origin and direction of record 0), brought back with
+ *     stream_base = y * frame_width + x, sample_base = k, spp = 1, gives that sample's colour bit for
+ *     bit: a host can recompute, re-order or redistribute the library's own samples.
+ * Coherence: rays 64 j .. 64 j + 63 of a call share a wave for every sample (work items are (sample
+ * chunk, ray) pairs dealt in blocks of 64 consecutive rays), so list neighbouring rays next to each
+ * other: the grouped order's wave-level box skip and the BVH kernel's memory locality depend on it.
+ *
+ * n == 0 returns RT_OK and touches nothing.  RT_ERR_ARG, before anything is launched, for a null scene,
+ * rays, sum, samples or misses pointer, n < 0 or spp <= 0.  The counters of rt_scene_get_stats, an armed
+ * rt_debug_ray_log, rt_kernel_times and the scene-specialised kernels are left as they were.
+ * rt_render_rays takes host buffers, is synchronous on the scene's own stream and accepts any n: it
+ * works in chunks of at most 2^19 rays (RTCORE_QUERY_CHUNK in the environment sets another size, as for
+ * rt_query_rays; fewer when spp is so large that a chunk's work items would pass 2^26), two of them
+ * resident, so device scratch (1 GiB of partial sums at most, 96 MiB of rays and records) and pinned
+ * staging (96 MiB) stay bounded, and a chunk's upload and the previous chunk's download overlap the
+ * kernel between them.  RT_ERR_ARG when not even 64 rays fit (spp above about 2^26 samples).
+ * rt_render_rays_device takes device buffers and is asynchronous on `stream` (a hipStream_t, NULL =
+ * the default stream), ordered like the device-resident renders (the per-scene scratch rule of the
+ * preamble).  One launch with 32-bit work items: RT_ERR_ARG for n above
+ *     min(2^30, 64 * floor(0xF0000000 / (64 * C))),  C = the chunk slots per ray at this spp:
+ * the samples per item are s = min(64, ceil(spp / B)), B = 24 (BRUTE, GROUPED) or 64 (BVH), and C is
+ * ceil(spp / s) rounded up to a power of two; 2^30 rays up to 2 spp, and at 64 spp 125,829,120 rays
+ * (BRUTE, GROUPED) or 62,914,560 (BVH).
+ */
+int rt_render_rays(rt_scene* scene, const rt_ray* rays, int64_t n, int32_t spp, uint64_t seed, uint64_t sample_base,
+                   uint64_t stream_base, rt_color* sum_rgb, uint32_t* samples, uint32_t* misses, uint64_t* rays_out);
+int rt_render_rays_device(rt_scene* scene, const rt_ray* d_rays, int64_t n, int32_t spp, uint64_t seed,
+                          uint64_t sample_base, uint64_t stream_base, double* d_sum, uint32_t* d_samples,
+                          uint32_t* d_misses, unsigned long long* d_rays_count, void* stream);
 
 /* Device-side DebugRaycaster Primitives pass: d_ids[y*w + x].  Asynchronous. */
 int rt_primary_ids_device(rt_scene* scene, int32_t x0, int32_t y0, int32_t w, int32_t h,

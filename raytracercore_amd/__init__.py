@@ -170,7 +170,7 @@ HIT_DTYPE = np.dtype([
 # entry points added under an unchanged ABI version: bound when the library has them (an older build
 # named by RTCORE_LIB may not)
 _OPTIONAL = ("rt_query_rays", "rt_query_rays_device", "rt_camera_rays", "rt_select_pixels", "rt_select_pixels_device",
-             "rt_select_rays", "rt_select_rays_device")
+             "rt_select_rays", "rt_select_rays_device", "rt_render_rays", "rt_render_rays_device")
 
 _lib: Optional[C.CDLL] = None
 
@@ -269,6 +269,10 @@ def load_library(path: str = "") -> C.CDLL:
                                             C.c_void_p]),
         "rt_debug_select_rays": (C.c_int, [P(rt_prim), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
                                            C.c_void_p]),
+        "rt_render_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64,
+                                     P(rt_color), P(C.c_uint32), P(C.c_uint32), P(C.c_uint64)]),
+        "rt_render_rays_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64,
+                                            C.c_uint64] + [C.c_void_p] * 4 + [C.c_void_p]),
     }
     for name, (res, args) in sig.items():
         if (name.startswith("rt_debug_") or name in _OPTIONAL) and not hasattr(lib, name):
@@ -638,6 +642,44 @@ class GpuRaytracer:
         d_hits (e.g. torch data_ptr()) on `stream` (a hipStream_t as an integer, 0 = the default stream)."""
         _check(self.lib.rt_query_rays_device(self.handle, RT_QUERY_EXACT if exact else RT_QUERY_FAST, C.c_void_p(d_rays),
                                              n, C.c_void_p(d_hits), C.c_void_p(stream)))
+
+    def render_rays(self, origins, directions, spp: int, seed: int, sample_base: int = 0, stream_base: int = 0,
+                    normalize: bool = False, out=None):
+        """rt_render_rays (Raytracer.GetColor(ray) for the caller's rays): spp path-traced samples of each
+        ray, sample k of ray i from the stream (seed, stream_base + i, sample_base + k).  origins and
+        directions as (n, 3) or (n, 4) arrays, or one RAY_DTYPE array with directions None (as query_rays).
+        The directions are taken as given, already normalised; normalize=True normalises them in fp64 here.
+        Returns (sum[n, 3] f64, samples[n] u32, misses[n] u32, rays): new zeroed arrays, or the caller's
+        `out` = (sum, samples, misses), which the call adds into."""
+        rays = np.ascontiguousarray(origins, RAY_DTYPE).reshape(-1) if directions is None \
+            else _pack_rays(origins, directions)
+        if normalize:
+            if directions is None:
+                rays = rays.copy()  # (the caller's array is not written)
+            d = rays["direction"]
+            d[:, :3] /= np.sqrt(np.sum(d[:, :3] * d[:, :3], axis=1))[:, None]
+        n = rays.shape[0]
+        if out is None:
+            out = (np.zeros((n, 3), np.float64), np.zeros(n, np.uint32), np.zeros(n, np.uint32))
+        s, ns, ms = out
+        for a, shape, dt in ((s, (n, 3), np.float64), (ns, (n,), np.uint32), (ms, (n,), np.uint32)):
+            if a.shape != shape or a.dtype != dt or not a.flags.c_contiguous:
+                raise ValueError("out must be C-contiguous (sum f64 [n, 3], samples u32 [n], misses u32 [n])")
+        count = C.c_uint64(0)
+        _check(self.lib.rt_render_rays(self.handle, rays.ctypes.data_as(C.c_void_p), n, spp, seed, sample_base,
+                                       stream_base, s.ctypes.data_as(C.POINTER(rt_color)),
+                                       ns.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                       ms.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(count)))
+        return s, ns, ms, count.value
+
+    def render_rays_device(self, d_ray_list: int, n: int, spp: int, seed: int, sample_base: int, stream_base: int,
+                           d_sum: int, d_samples: int, d_misses: int, d_rays: int = 0, stream: int = 0) -> None:
+        """rt_render_rays_device: asynchronous radiance query of n rt_ray at device pointer d_ray_list, added
+        into device accumulators (d_sum: planes R | G | B of n doubles; d_samples, d_misses: n uint32;
+        d_rays: one uint64 ray counter or 0) on `stream` (a hipStream_t as an integer, 0 = the default)."""
+        _check(self.lib.rt_render_rays_device(self.handle, C.c_void_p(d_ray_list), n, spp, seed, sample_base,
+                                              stream_base, C.c_void_p(d_sum), C.c_void_p(d_samples),
+                                              C.c_void_p(d_misses), C.c_void_p(d_rays), C.c_void_p(stream)))
 
     def select_pixels(self, items, x0: int = 0, y0: int = 0, w: Optional[int] = None,
                       h: Optional[int] = None) -> np.ndarray:

@@ -1139,6 +1139,38 @@ __device__ __forceinline__ void item_pixel(unsigned item, const ParT& p, int& px
     }
 }
 
+// A caller's ray (rt_query_rays, rt_render_rays): it arrives as rt_ray (fp64, four 16-B rows) and is
+// rounded to fp32 component by component.  valid: every component finite (before and after the
+// rounding) and the direction not zero.  Any other ray is a miss, decided here where the ray is
+// loaded and not by how a NaN would fall through the tests.
+struct QueryRay {
+    V3 o, d;
+    bool valid;
+};
+__device__ __forceinline__ QueryRay load_query_ray(const double2* __restrict__ rays, unsigned i)
+{
+    const double2 r0 = rays[4 * (size_t)i], r1 = rays[4 * (size_t)i + 1], r2 = rays[4 * (size_t)i + 2],
+                  r3 = rays[4 * (size_t)i + 3];
+    QueryRay q;
+    q.o = v3((float)r0.x, (float)r0.y, (float)r1.x);
+    q.d = v3((float)r2.x, (float)r2.y, (float)r3.x);
+    const float inf = __builtin_huge_valf();
+    const bool finite = (fabsf(q.o.x) < inf) & (fabsf(q.o.y) < inf) & (fabsf(q.o.z) < inf) & (fabsf(q.d.x) < inf) &
+                        (fabsf(q.d.y) < inf) & (fabsf(q.d.z) < inf) & (fabs(r1.y) < __builtin_huge_val()) &
+                        (fabs(r3.y) < __builtin_huge_val()); // (every compare is false for NaN)
+    q.valid = finite & ((q.d.x != 0.0f) | (q.d.y != 0.0f) | (q.d.z != 0.0f));
+    return q;
+}
+
+// rt_render_rays (the RAYS instances): the ray a work item names, item = ((block << log2_chunks) +
+// chunk) * 64 + pixel with ray = block * 64 + pixel, so a wave's 64 items of one chunk are 64
+// consecutive rays.  No division and no frame: make_params_rays plans the launch.
+template <class ParT>
+__device__ __forceinline__ unsigned item_ray(unsigned item, const ParT& p)
+{
+    return ((item >> (6 + p.log2_chunks)) << 6) | (item & 63u);
+}
+
 // The next sample of the lane's item.  The BVH (NT) kernels hold no register for it: the item's
 // first sample (its chunk, from the item index) plus the samples it finished (samples + misses).
 template <bool NT, class ParT>
@@ -1148,7 +1180,12 @@ __device__ __forceinline__ int item_sample(const Lane& L, const ParT& p)
     const int c = (int)((L.item >> 6) & (unsigned)(p.n_chunks - 1));
     return c * p.chunk + (int)(L.cnt & 0xFFu) + (int)((L.cnt >> 8) & 0xFFu);
 }
-template <bool NT, class ParT, class SceneT, class CamT>
+// RAYS (rt_render_rays' instances): an item names a ray of p.ray_list instead of a pixel (item_ray),
+// its pixel key is that of p.stream_base + ray, and a sample starts from the ray as given, with the
+// two draws GetCameraRay would have spent discarded; the camera is never read.  The brute-force
+// kernels keep the ray index in L.fx; every kernel loads the ray's rows again at each sample start
+// (they stay in the cache between an item's samples) instead of holding six more registers.
+template <bool NT, bool RAYS = false, class ParT, class SceneT, class CamT>
 __device__ __forceinline__ void refill(Lane& L, Sample& S, const ParT& p, const SceneT& s, const CamT& cam, int lane,
                                       unsigned total)
 {
@@ -1220,6 +1257,18 @@ __device__ __forceinline__ void refill(Lane& L, Sample& S, const ParT& p, const 
                 // (no ticket drawn for it yet: it asks again in the next iteration)
             } else if (L.item >= total) {
                 L.active = false;
+            } else if constexpr (RAYS) {
+                const unsigned ri = item_ray(L.item, p);
+                const int s0 = (int)((L.item >> 6) & (unsigned)(p.n_chunks - 1)) * p.chunk;
+                if (ri < p.n_rays && s0 < p.spp) {
+                    L.item_open = true;
+                    if (!NT) L.s_next = s0;
+                    L.cnt = (unsigned)(min(p.spp, s0 + p.chunk) - s0) << 16; // chunk <= 64
+                    if (!NT) {
+                        L.fx = (int)ri;
+                        L.pkey = rt_rng_pixel_key(p.seed_key, p.stream_base + (unsigned long long)ri);
+                    }
+                }
             } else {
                 int px, py, c, fx, fy;
                 item_pixel(L.item, p, px, py, c, fx, fy);
@@ -1249,6 +1298,29 @@ __device__ __forceinline__ void refill(Lane& L, Sample& S, const ParT& p, const 
         } else {
             L.pool_next += k;
         }
+    }
+    if constexpr (RAYS) {
+        if (L.active && L.item_open && !L.live && L.cnt >= 65536u) {
+            const unsigned ri = NT ? item_ray(L.item, p) : (unsigned)L.fx;
+            if (NT) L.pkey = rt_rng_pixel_key(p.seed_key, p.stream_base + (unsigned long long)ri);
+            const QueryRay q = load_query_ray(p.ray_list, ri);
+            if (q.valid) {
+                S.rng = rt_rng_from_pixel_key(L.pkey, p.sample_base + (unsigned long long)item_sample<NT>(L, p));
+                (void)rt_rng_next24(&S.rng); // GetCameraRay's subX and subY (Raytracer.cs:264-265)
+                (void)rt_rng_next24(&S.rng);
+                S.o = q.o;
+                S.d = q.d;
+                S.tint = v3(1.0f, 1.0f, 1.0f);
+                S.bounce = 0;
+                S.prev = -1;
+                L.live = true;
+            } else { // every sample the item has left is a primary miss; no query, so no ray counted
+                const unsigned left = L.cnt >> 16;
+                L.cnt = (L.cnt & 0xFFFFu) + (left << 8);
+                if (!NT) L.s_next += (int)left;
+            }
+        }
+        return;
     }
     if (L.active && L.item_open && !L.live && L.cnt >= 65536u) {
         int fx = L.fx, fy = L.fy;
@@ -1373,7 +1445,7 @@ typedef RT_AS_CONST const PathParams ParamsC;
 
 // Brute-force megakernel: every loop iteration issues one closest-hit query per live lane
 // (the scene's records arrive through scalar loads) and shades it.
-template <bool CULL, bool LDS, bool STATS, bool VN>
+template <bool CULL, bool LDS, bool STATS, bool VN, bool RAYS = false>
 __device__ __forceinline__ void path_body(const CameraF* __restrict__ camp, const PathParams* __restrict__ pp)
 {
     // everything but the LDS staging is read from the launch record *pp (fill_launch) in the
@@ -1412,7 +1484,7 @@ __device__ __forceinline__ void path_body(const CameraF* __restrict__ camp, cons
 #if defined(RT_SCENE_CONST) && RT_SCENE_CONST_CAMERA
         refill<false>(L, S, *pq, sc, *(const CameraF*)kCameraW, lane, total); // the camera compiled in too
 #else
-        refill<false>(L, S, *pq, sc, *cp, lane, total);
+        refill<false, RAYS>(L, S, *pq, sc, *cp, lane, total);
 #endif
         if (!__any(L.active)) break;
         if (STATS) t1 = __builtin_readcyclecounter();
@@ -1464,13 +1536,14 @@ __device__ __forceinline__ void path_body(const CameraF* __restrict__ camp, cons
     flush_counts<STATS>(wave_rays, cnt, *(const ParamsC*)pp, lane);
 }
 
-template <bool CULL, bool LDS, bool STATS, bool VN>
+// RAYS: rt_render_rays' instances (refill); every other instance is as it was without the switch.
+template <bool CULL, bool LDS, bool STATS, bool VN, bool RAYS = false>
 __global__ void __launch_bounds__(256, CULL ? RT_GROUPED_WAVES : RT_PATH_WAVES)
     path_kernel(PathScene, const CameraF* __restrict__ camp, const PathParams* __restrict__ pp, const TestRec*,
                 const RectRec*, const FrameRec*, const PrimF*, const NodeF*, const Node4Q*, const GroupRec*,
                 const XformF*, const MatF*, const float4*)
 {
-    path_body<CULL, LDS, STATS, VN>(camp, pp); // the other arguments are the BVH kernels' (same launch)
+    path_body<CULL, LDS, STATS, VN, RAYS>(camp, pp); // the other arguments are the BVH kernels' (same launch)
 }
 
 // The BVH order's outer group (DevScene::groups_bvh): the world rects and closed boxes left out of
@@ -1551,7 +1624,7 @@ __device__ __forceinline__ void test_leaf(TestP tests, RowP rows, XfP xf, int pe
 // runs only once at least p.refill lanes wait (or none is still traversing).  So one long
 // traversal no longer holds the other 63 lanes of its wave, and the divergent shading code is
 // paid once per batch of finished queries.
-template <int WIDTH, int STACK, bool LDS, bool STATS, bool VN>
+template <int WIDTH, int STACK, bool LDS, bool STATS, bool VN, bool RAYS = false>
 __global__ void __launch_bounds__(256, WIDTH == 4 ? RT_BVH_WAVES : RT_BVH2_WAVES)
     path_kernel_bvh(PathScene, const CameraF* __restrict__ camp, const PathParams* __restrict__ pp, const TestRec*,
                     const RectRec*, const FrameRec*, const PrimF*, const NodeF*, const Node4Q*, const GroupRec*,
@@ -1640,7 +1713,7 @@ __global__ void __launch_bounds__(256, WIDTH == 4 ? RT_BVH_WAVES : RT_BVH2_WAVES
                 bounce<VN, !LDS, true, STATS>(L, S, s, R, vnormals, tests, pq->prims_d, b, p);
                 done = false;
             }
-            refill<true>(L, S, p, s, *cp, lane, total);
+            refill<true, RAYS>(L, S, p, s, *cp, lane, total);
             if (L.live && !trav) { // start the next query
                 ref = s.root;
                 sp = 0;
@@ -1898,28 +1971,8 @@ __global__ void __launch_bounds__(256, WAVES) trace_rays_kernel(TraceRaysParams 
 
 // ---- rt_query_rays, RT_QUERY_FAST: the closest hit of caller-supplied rays -------------------------
 // Scene.RayTrace(ray, null) by the path kernels' own closest-hit code from "no previous hit" (prev
-// = -1, Best = none), one rt_hit per ray.  A ray arrives as rt_ray (fp64, four 16-B rows) and is
-// rounded to fp32 component by component.  valid: every component finite (before and after the
-// rounding) and the direction not zero.  Any other ray is a miss, decided here where the ray is
-// loaded and not by how a NaN would fall through the tests.
-struct QueryRay {
-    V3 o, d;
-    bool valid;
-};
-__device__ __forceinline__ QueryRay load_query_ray(const double2* __restrict__ rays, unsigned i)
-{
-    const double2 r0 = rays[4 * (size_t)i], r1 = rays[4 * (size_t)i + 1], r2 = rays[4 * (size_t)i + 2],
-                  r3 = rays[4 * (size_t)i + 3];
-    QueryRay q;
-    q.o = v3((float)r0.x, (float)r0.y, (float)r1.x);
-    q.d = v3((float)r2.x, (float)r2.y, (float)r3.x);
-    const float inf = __builtin_huge_valf();
-    const bool finite = (fabsf(q.o.x) < inf) & (fabsf(q.o.y) < inf) & (fabsf(q.o.z) < inf) & (fabsf(q.d.x) < inf) &
-                        (fabsf(q.d.y) < inf) & (fabsf(q.d.z) < inf) & (fabs(r1.y) < __builtin_huge_val()) &
-                        (fabs(r3.y) < __builtin_huge_val()); // (every compare is false for NaN)
-    q.valid = finite & ((q.d.x != 0.0f) | (q.d.y != 0.0f) | (q.d.z != 0.0f));
-    return q;
-}
+// = -1, Best = none), one rt_hit per ray, loaded by load_query_ray (above, with the path kernels'
+// refill, which starts rt_render_rays' samples from the same rows).
 
 __device__ __forceinline__ void store_query_miss(float4* __restrict__ out)
 {
@@ -2151,6 +2204,48 @@ __global__ void accumulate_kernel(PathParams p, double* sum, uint32_t* samples, 
     misses[i] += nm;
 }
 
+// rt_render_rays: the same fold per ray (ray i's partials are pixel i & 63 of block i >> 6), in chunk
+// order.  recs null: added to the planar accumulators (n each, planes n apart); else written, from
+// zero, as one TileRec per ray for the host entry's download.
+__global__ void accumulate_rays_kernel(PathParams p, double* sum, uint32_t* samples, uint32_t* misses, TileRec* recs)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t n = p.n_rays;
+    if (i >= n) return;
+    double r = 0.0, g = 0.0, bl = 0.0;
+    if (!recs) {
+        r = sum[i];
+        g = sum[n + i];
+        bl = sum[2 * n + i];
+    }
+    uint32_t ns = 0, nm = 0;
+    const int used = (p.spp + p.chunk - 1) / p.chunk;
+    for (int c = 0; c < used; c++) {
+        const float4 v = p.partial[((((i >> 6) << p.log2_chunks) + c) << 6) + (i & 63)];
+        r += v.x;
+        g += v.y;
+        bl += v.z;
+        const uint32_t k = __float_as_uint(v.w);
+        ns += k & 0xFFFFu;
+        nm += k >> 16;
+    }
+    if (recs) {
+        TileRec t;
+        t.r = r;
+        t.g = g;
+        t.b = bl;
+        t.samples = ns;
+        t.misses = nm;
+        recs[i] = t;
+    } else {
+        sum[i] = r;
+        sum[n + i] = g;
+        sum[2 * n + i] = bl;
+        samples[i] += ns;
+        misses[i] += nm;
+    }
+}
+
 // SampleSet.GetOutput / GetColorCode (SampleSet.cs:50-113) per pixel of planar accumulators.
 __device__ __forceinline__ uint32_t color_code(double r, double g, double b, double a)
 {
@@ -2298,31 +2393,38 @@ using PathKernel = void (*)(PathScene, const CameraF*, const PathParams*, const 
 // vn: the scene has vertex-normal triangles (their re-hit test, vn_rehit_test, is fp64 code that
 // costs the other scenes' kernels registers, so it is compiled only into separate instances)
 template <bool CULL, bool LDS>
-PathKernel pick_brute(bool stats, bool vn)
+PathKernel pick_brute(bool stats, bool vn, bool rays)
 {
+    if (rays) return vn ? path_kernel<CULL, LDS, false, true, true> : path_kernel<CULL, LDS, false, false, true>;
     if (vn) return stats ? path_kernel<CULL, LDS, true, true> : path_kernel<CULL, LDS, false, true>;
     return stats ? path_kernel<CULL, LDS, true, false> : path_kernel<CULL, LDS, false, false>;
 }
 template <int WIDTH, int STACK, bool LDS>
-PathKernel pick_bvh(bool stats, bool vn)
+PathKernel pick_bvh(bool stats, bool vn, bool rays)
 {
+    if (rays) { // (the wide kernel only; rt_render_rays refuses a BVH2 scene before it gets here)
+        if constexpr (WIDTH == 4)
+            return vn ? path_kernel_bvh<WIDTH, STACK, LDS, false, true, true> : path_kernel_bvh<WIDTH, STACK, LDS, false, false, true>;
+        return nullptr;
+    }
     if (vn) return stats ? path_kernel_bvh<WIDTH, STACK, LDS, true, true> : path_kernel_bvh<WIDTH, STACK, LDS, false, true>;
     return stats ? path_kernel_bvh<WIDTH, STACK, LDS, true, false> : path_kernel_bvh<WIDTH, STACK, LDS, false, false>;
 }
 
 // variant = kernel * 2 + lds; kernel 0 brute force (flat), 1 brute force (grouped, culled),
-// 2 BVH2 (24-entry LDS stack), 3 wide BVH (RT_WIDE_STACK-entry LDS stack); both overflow to global memory
-PathKernel pick(int variant, bool stats, bool vn)
+// 2 BVH2 (24-entry LDS stack), 3 wide BVH (RT_WIDE_STACK-entry LDS stack); both overflow to global memory.
+// rays: rt_render_rays' instance of the variant (never instrumented; none for the BVH2 kernel)
+PathKernel pick(int variant, bool stats, bool vn, bool rays = false)
 {
     switch (variant) {
-    case 1: return pick_brute<false, true>(stats, vn);
-    case 2: return pick_brute<true, false>(stats, vn);
-    case 3: return pick_brute<true, true>(stats, vn);
-    case 4: return pick_bvh<2, 24, false>(stats, vn);
-    case 5: return pick_bvh<2, 24, true>(stats, vn);
-    case 6: return pick_bvh<4, RT_WIDE_STACK, false>(stats, vn);
-    case 7: return pick_bvh<4, RT_WIDE_STACK, true>(stats, vn);
-    default: return pick_brute<false, false>(stats, vn);
+    case 1: return pick_brute<false, true>(stats, vn, rays);
+    case 2: return pick_brute<true, false>(stats, vn, rays);
+    case 3: return pick_brute<true, true>(stats, vn, rays);
+    case 4: return pick_bvh<2, 24, false>(stats, vn, rays);
+    case 5: return pick_bvh<2, 24, true>(stats, vn, rays);
+    case 6: return pick_bvh<4, RT_WIDE_STACK, false>(stats, vn, rays);
+    case 7: return pick_bvh<4, RT_WIDE_STACK, true>(stats, vn, rays);
+    default: return pick_brute<false, false>(stats, vn, rays);
     }
 }
 
@@ -2392,10 +2494,10 @@ size_t path_dyn_lds(const DevScene& s, int variant)
     return b;
 }
 
-int path_blocks_per_cu(int variant, size_t dyn_lds, bool stats, bool vn)
+int path_blocks_per_cu(int variant, size_t dyn_lds, bool stats, bool vn, bool rays)
 {
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(pick(variant, stats, vn)), 256,
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(pick(variant, stats, vn, rays)), 256,
                                                      dyn_lds) != hipSuccess ||
         n < 1)
         n = 1;
@@ -2436,8 +2538,10 @@ void fill_launch(const DevScene& s, int variant, PathParams& p)
 }
 
 hipError_t launch_path(const DevScene& s, const CameraF* d_cam, const PathParams* d_params, int variant,
-                       int grid_blocks, hipStream_t stream, bool stats)
+                       int grid_blocks, hipStream_t stream, bool stats, bool rays)
 {
+    const PathKernel kernel = pick(variant, stats, s.n_vn > 0, rays);
+    if (!kernel) return hipErrorInvalidValue;
     PathParams h{}; // the same launch record as the device copy: the BVH kernels take it as arguments
     fill_launch(s, variant, h);
     PathScene ps = h.scene;
@@ -2455,8 +2559,7 @@ hipError_t launch_path(const DevScene& s, const CameraF* d_cam, const PathParams
     const float4* vn = h.vnormals;
     void* args[] = {&ps, &ca, &pa, &tests, &rects, &frames, &prims, &nodes, &nodes4, &groups, &xf, &mats, &vn};
     const size_t dyn = path_dyn_lds(s, variant);
-    return hipLaunchKernel(reinterpret_cast<const void*>(pick(variant, stats, s.n_vn > 0)), dim3(grid_blocks), dim3(256), args, dyn,
-                           stream);
+    return hipLaunchKernel(reinterpret_cast<const void*>(kernel), dim3(grid_blocks), dim3(256), args, dyn, stream);
 }
 
 hipError_t launch_accumulate(const PathParams& p, double* d_sum, uint32_t* d_samples, uint32_t* d_misses, hipStream_t stream,
@@ -2465,6 +2568,15 @@ hipError_t launch_accumulate(const PathParams& p, double* d_sum, uint32_t* d_sam
     if (plane == 0) plane = (size_t)p.w * p.h;
     dim3 grid((p.w + 15) / 16, (p.h + 15) / 16);
     hipLaunchKernelGGL(accumulate_kernel, grid, dim3(256), 0, stream, p, d_sum, d_samples, d_misses, plane);
+    return hipGetLastError();
+}
+
+hipError_t launch_accumulate_rays(const PathParams& p, double* d_sum, uint32_t* d_samples, uint32_t* d_misses,
+                                  TileRec* d_recs, hipStream_t stream)
+{
+    if (p.n_rays == 0) return hipSuccess;
+    hipLaunchKernelGGL(accumulate_rays_kernel, dim3((p.n_rays + 255u) / 256u), dim3(256), 0, stream, p, d_sum, d_samples,
+                       d_misses, d_recs);
     return hipGetLastError();
 }
 

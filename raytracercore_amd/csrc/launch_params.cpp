@@ -172,6 +172,31 @@ PathParams make_params_for(int kernel, int chunks_over, int pool_over, int x0, i
     return p;
 }
 
+// rt_render_rays: a list of n rays planned as the tile 8 pixels wide and ceil(n / 8) tall, so that
+// the item space is linear in the ray index: blocks_x = 1, block b's 64 pixels are the rays 64 b ..
+// 64 b + 63 (ray = py * 8 + px), and the dispensers, the XCD ranges (runs of consecutive rays) and
+// the partial layout are the tile's.  The RAYS kernels decode an item without the tile (item_ray)
+// and bound it by n_rays.  The samples per item are those of a 1080p frame at this spp whatever n
+// is (chunk_npix), so that a ray's fp32 partial sums, and with them its result, do not depend on
+// how many rays share its call or on the host entry's chunking.
+PathParams make_params_rays(int kernel, int64_t n, int spp, uint64_t seed, uint64_t base, uint64_t stream_base)
+{
+    PathParams p = make_params_for(kernel, 0, 0, 0, 0, 8, (int)((n + 7) / 8), spp, seed, base, 2073600.0);
+    p.n_rays = (unsigned)n;
+    p.stream_base = stream_base;
+    return p;
+}
+
+// Most rays of one RAYS launch at this spp: 32-bit item indices, n_chunks slots per ray padded to
+// whole blocks of 64, below the bound run_path holds every launch to (0xF0000000 items), and below
+// 2^30 rays (n_pad is an int).  0 when not even one block fits.
+int64_t render_rays_max_n(int kernel, int spp)
+{
+    const PathParams p = make_params_for(kernel, 0, 0, 0, 0, 8, 8, spp, 0, 0, 2073600.0);
+    const int64_t blocks = (int64_t)(0xF0000000ull / ((uint64_t)p.n_chunks * 64u));
+    return std::min<int64_t>(blocks * 64, (int64_t)1 << 30);
+}
+
 // Band-set launch: tile row r is frame row ((r / band) * stride + offset) * band + r % band; the
 // kernel divides by a shift for power-of-two bands, else by the fp32 reciprocal.
 void set_band(PathParams& p, int band, int stride, int offset)

@@ -10,6 +10,11 @@ namespace rtc {
 // check, rt_debug_item_order): chunks per pixel and items per ticket instead of the tuned ones.
 PathParams make_params_for(int kernel, int chunks_over, int pool_over, int x0, int y0, int w, int h, int spp,
                            uint64_t seed, uint64_t base, double chunk_npix);
+// rt_render_rays: the launch record of n caller-supplied rays (a tile 8 wide, so that ray i is pixel
+// i & 63 of block i >> 6; p.ray_list is set by the caller), and the most rays one launch takes at
+// this spp (32-bit item indices).
+PathParams make_params_rays(int kernel, int64_t n, int spp, uint64_t seed, uint64_t base, uint64_t stream_base);
+int64_t render_rays_max_n(int kernel, int spp);
 // The order in which the dispensers deal p's work items, from p's chunks, pool and ranges.
 void set_item_order(PathParams& p);
 // Band-set launch: tile row r is frame row ((r / band) * stride + offset) * band + r % band.

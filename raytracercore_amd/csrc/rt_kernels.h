@@ -87,6 +87,13 @@ struct PathParams {
     float4* rec_rays;
     float4* rec_samples;
     unsigned int rec_max;       // records in rec_rays (no store at or past it)
+    // rt_render_rays, the RAYS instances only (null / 0 on every other launch; last, so that no other
+    // field moves): the caller's rays as rt_ray rows.  The launch is planned as a tile 8 pixels wide
+    // (make_params_rays), so the 64 items of block b and one chunk are the rays 64 b .. 64 b + 63: ray
+    // i = (block << 6) | pixel of the item, and its pixel key is that of stream_base + i.
+    const double2* ray_list;    // four 16-B rows per ray (origin xy, origin zw, direction xy, direction zw)
+    unsigned int n_rays;        // rays of the launch (the items of the last block past it stay closed)
+    unsigned long long stream_base;
 };
 constexpr int kRecRows = 6;     // sizeof(rt_debug_ray) / 16
 
@@ -191,9 +198,11 @@ size_t path_lds_bytes(const DevScene& s);   // dynamic LDS of the staged (lds) v
 size_t path_dyn_lds(const DevScene& s, int variant); // all dynamic LDS of a variant (+ the wide kernel's hot nodes)
 // Launch the persistent kernel; stats counts node visits / primitive tests (slower build).
 // The camera and the launch parameters are read from device memory (d_cam, d_params).
+// rays: rt_render_rays' instance of the variant (PathParams::ray_list; the brute-force and the wide
+// BVH kernels, never instrumented), which does not read the camera.
 hipError_t launch_path(const DevScene& s, const CameraF* d_cam, const PathParams* d_params, int variant,
-                       int grid_blocks, hipStream_t stream, bool stats);
-int path_blocks_per_cu(int variant, size_t dyn_lds, bool stats, bool vn); // vn: scene has vertex-normal triangles
+                       int grid_blocks, hipStream_t stream, bool stats, bool rays = false);
+int path_blocks_per_cu(int variant, size_t dyn_lds, bool stats, bool vn, bool rays = false); // vn: scene has vertex-normal triangles
 // The trace-only kernel (waves per SIMD 6 / 7 / 8 with LDS stacks of 20 / 16 / 16 entries): blocks
 // per CU and launch (grid blocks of 256).
 int trace_rays_blocks_per_cu(int waves);
@@ -224,6 +233,10 @@ struct TileRec {
     double r, g, b;
     uint32_t samples, misses;
 };
+// rt_render_rays: a RAYS launch's partials folded per ray, in chunk order.  d_recs null: added to
+// d_sum (planes R | G | B of p.n_rays doubles), d_samples, d_misses; else written to d_recs[p.n_rays].
+hipError_t launch_accumulate_rays(const PathParams& p, double* d_sum, uint32_t* d_samples, uint32_t* d_misses,
+                                  TileRec* d_recs, hipStream_t stream);
 // planar row-major accumulators (w*h) -> TileRec[w*h] in x*h + y order
 hipError_t launch_tile_host_layout(int w, int h, const double* d_sum, const uint32_t* d_samples,
                                   const uint32_t* d_misses, TileRec* d_out, hipStream_t stream);

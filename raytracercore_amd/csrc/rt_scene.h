@@ -1,5 +1,5 @@
 // rt_scene.h -- the scene object behind the C ABI and what the API's translation units share
-// (rtcore_api.hip, scene_upload.hip, api_frame.hip, api_debug.hip, api_query.hip, api_select.hip).
+// (rtcore_api.hip, scene_upload.hip, api_frame.hip, api_debug.hip, api_query.hip, api_select.hip, api_render_rays.hip).
 #pragma once
 #include <algorithm>
 #include <array>
@@ -183,6 +183,10 @@ struct rt_scene {
     DevBuf<rt_ray> query_rays;
     DevBuf<rt_hit> query_hits;
     std::array<hipEvent_t, 2> query_up_ev{};
+    // rt_render_rays: two chunks of per-ray records (its rays share query_rays and query_up_ev), and
+    // the blocks per CU of the RAYS instance of `rays_variant`
+    DevBuf<TileRec> render_rays_recs;
+    int rays_variant = -1, rays_blocks_per_cu = 1;
     // the selection pass (api_select.hip): the caller's item list on the device, and the host-buffer
     // entry points' rays (one chunk) and results
     DevBuf<rt_select_item> select_items;
@@ -278,6 +282,7 @@ int check_tile(rt_scene* s, int x0, int y0, int w, int h);
 PathParams make_params(rt_scene* s, int x0, int y0, int w, int h, int spp, uint64_t seed, uint64_t base,
                        double chunk_npix = 0.0);
 int run_path(rt_scene* s, PathParams& p, unsigned long long* d_rays, hipStream_t stream, bool timed = true);
+int upload_params(rt_scene* s, const PathParams& p, hipStream_t stream, const PathParams** d_out);
 int end_op(rt_scene* s, hipStream_t stream);
 int queue_copy(rt_scene* s, CopyPlan& plan, const void* d_src, size_t a, size_t b, size_t rec_bytes, int k,
                hipStream_t stream);

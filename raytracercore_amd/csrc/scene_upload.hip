@@ -589,6 +589,24 @@ int prepare_jit(rt_scene* s)
     return 1;
 }
 
+// A launch record into the next slot of the scene's ring (rt_scene::params_d), queued on `stream`.
+int upload_params(rt_scene* s, const PathParams& p, hipStream_t stream, const PathParams** d_out)
+{
+    if (!s->params_h) {
+        HIP_TRY(hipHostMalloc(&s->params_h, sizeof(PathParams) * rt_scene::kParamRing, hipHostMallocDefault));
+        HIP_TRY(s->params_d.reserve(rt_scene::kParamRing));
+    }
+    const unsigned slot = s->params_next++ % rt_scene::kParamRing;
+    hipEvent_t& sev = s->slot_ev[slot];
+    if (sev) HIP_TRY(hipEventSynchronize(sev)); // the slot's previous upload has been read
+    else HIP_TRY(hipEventCreateWithFlags(&sev, hipEventDisableTiming));
+    s->params_h[slot] = p;
+    HIP_TRY(hipMemcpyAsync(s->params_d.p + slot, s->params_h + slot, sizeof(PathParams), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(sev, stream));
+    *d_out = s->params_d.p + slot;
+    return RT_OK;
+}
+
 // Launch the path kernel for p (work buffers sized here), timing it with the scene's events.
 int run_path(rt_scene* s, PathParams& p, unsigned long long* d_rays, hipStream_t stream, bool timed)
 {
@@ -644,10 +662,6 @@ int run_path(rt_scene* s, PathParams& p, unsigned long long* d_rays, hipStream_t
     }
     const int tslot = (int)(s->launches % rt_scene::kTimeRing);
     if (timed) HIP_TRY(hipEventRecord(s->t_start[tslot], stream));
-    if (!s->params_h) {
-        HIP_TRY(hipHostMalloc(&s->params_h, sizeof(PathParams) * rt_scene::kParamRing, hipHostMallocDefault));
-        HIP_TRY(s->params_d.reserve(rt_scene::kParamRing));
-    }
     fill_launch(s->dev, s->variant, p);
     // The brute-force kernels read each item's pixel key (two lowbias32 rounds of the seed key and
     // the frame pixel index, rtcore_rng.h) from a per-scene table, built here once per seed (a
@@ -664,21 +678,16 @@ int run_path(rt_scene* s, PathParams& p, unsigned long long* d_rays, hipStream_t
         }
         p.pkeys = s->pkeys.p;
     }
-    const unsigned slot = s->params_next++ % rt_scene::kParamRing;
-    hipEvent_t& sev = s->slot_ev[slot];
-    if (sev) HIP_TRY(hipEventSynchronize(sev)); // the slot's previous upload has been read
-    else HIP_TRY(hipEventCreateWithFlags(&sev, hipEventDisableTiming));
-    s->params_h[slot] = p;
-    HIP_TRY(hipMemcpyAsync(s->params_d.p + slot, s->params_h + slot, sizeof(PathParams), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipEventRecord(sev, stream));
+    const PathParams* pa = nullptr;
+    const int urc = upload_params(s, p, stream, &pa);
+    if (urc != RT_OK) return urc;
     if (jit) {
         const CameraF* ca = s->camf_d.p;
-        const PathParams* pa = s->params_d.p + slot;
         void* args[] = {&ca, &pa};
         HIP_TRY(hipModuleLaunchKernel(s->jit.fn, jit_grid, 1, 1, 256, 1, 1,
                                       (unsigned)path_dyn_lds(s->dev, s->variant), stream, args, nullptr));
     } else {
-        HIP_TRY(launch_path(s->dev, s->camf_d.p, s->params_d.p + slot, s->variant, grid, stream, s->stats_on));
+        HIP_TRY(launch_path(s->dev, s->camf_d.p, pa, s->variant, grid, stream, s->stats_on));
     }
     if (timed) {
         HIP_TRY(hipEventRecord(s->t_end[tslot], stream));

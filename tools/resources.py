@@ -23,4 +23,5 @@ for line in out.splitlines():
         rows[cur][m.group(1).strip()] = m.group(2)
 for k, v in rows.items():
     print(f"{k:40s} VGPR {v.get('VGPRs','?'):>4} SGPR {v.get('SGPRs','?'):>4} spillV {v.get('VGPRs Spill','?'):>3} "
-          f"spillS {v.get('SGPRs Spill','?'):>3} occ {v.get('Occupancy','?')} LDS {v.get('LDS Size','?')}")
+          f"spillS {v.get('SGPRs Spill','?'):>3} scratch {v.get('ScratchSize','?'):>4} occ {v.get('Occupancy','?')} "
+          f"LDS {v.get('LDS Size','?')}")
