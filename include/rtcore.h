@@ -46,7 +46,8 @@ extern "C" {
                                    and rt_camera_rays were added under version 6 (purely additive): a host
                                    detects them by symbol; so were rt_select_pixels, rt_select_pixels_device,
                                    rt_select_rays, rt_select_rays_device and rt_debug_select_rays, and
-                                   rt_render_rays and rt_render_rays_device */
+                                   rt_render_rays and rt_render_rays_device, and rt_occluded_rays and
+                                   rt_occluded_rays_device */
 
 typedef enum rt_status {
     RT_OK = 0,
@@ -427,6 +428,49 @@ int rt_query_rays_device(rt_scene* scene, int32_t mode, const rt_ray* d_rays, in
    outside the frame. */
 int rt_camera_rays(const rt_camera* camera, int32_t width, int32_t height, int32_t x0, int32_t y0, int32_t w,
                    int32_t h, rt_ray* out);
+
+/* ------------------------------------------------------------ occlusion queries --- */
+/*
+ * "Is anything between this point and that one": any-hit visibility for segments the caller brings.
+ *   occluded_out[i] = 1  when Scene.RayTrace(rays[i], null) returns a hit with Hit.Distance < t_max[i]
+ *                        (strictly, as RayTracePrimitives' own currentHit.Distance < hit.Distance,
+ *                        Scene.cs:85-86), with the culling of Primitive.RayTrace (Primitive.cs:46-75) and
+ *                        no skip hit: one-sided, two-sided and inverted primitives as in a render;
+ *                     0  otherwise.
+ * The segment starts at the ray's origin: there is no skip primitive and no t_min, and a caller that
+ * leaves a surface offsets the origin itself.
+ * t_max: NULL means +inf for every ray ("does this ray hit anything").  t_max[i] that is NaN, <= 0 or
+ * (RT_QUERY_FAST) rounds to 0 in fp32 is an empty segment: the answer is 0.  +inf is valid.  A ray with a
+ * non-finite component or a zero direction gives 0 (the rule of rt_query_rays).
+ * RT_QUERY_FAST: the fp32 tests of the path kernels in the scene's traversal mode (BRUTE, GROUPED, or BVH
+ *   with either builder; on a BVH2 scene RT_ERR_STATE with the message rt_query_rays gives), always the
+ *   generic kernels, whatever rt_set_jit says.  The ray is rounded to fp32 as for rt_query_rays and
+ *   t_max[i] to fp32 to nearest.  The traversal is not the closest-hit one: it is unordered, bounded by
+ *   t_max and ends at the first accepted primitive.  Its answer is that of rt_query_rays(RT_QUERY_FAST)
+ *   on the same ray in the same mode: a hit exists and its fp32 distance is < (float)t_max[i].  The two
+ *   may differ only where that distance lies within the slack of the kernels' box culling of t_max: boxes
+ *   (the grouped order's group boxes, the wide tree's children) are kept up to t_max * 1.00000024, the
+ *   factor in the kernels' slab and wide_visit, and the closest-hit search culls by its shrinking best
+ *   distance with the same factor, so a primitive within 2.4e-7 (relative) of the bound or of another hit
+ *   can be tested by one search and not by the other.
+ * RT_QUERY_EXACT: the fp64 reference query of rt_primary_ids in every traversal mode (reference BVH,
+ *   built on first use): its Hit.Distance compared with t_max[i] in fp64, the reference's own answer.  On
+ *   a traversal-stack overflow the device entry writes 255 for that ray and the host entry returns
+ *   RT_ERR_STATE (rt_query_rays reports the same by prim_id -2).
+ * n == 0 returns RT_OK and touches nothing; RT_ERR_ARG, before anything is launched, for a null scene,
+ * rays or output pointer, n < 0 or an unknown mode.  The counters of rt_scene_get_stats, an armed
+ * rt_debug_ray_log, the rt_kernel_times ring and the scene-specialised kernels are left as they were.  No
+ * camera is needed.
+ * rt_occluded_rays takes host buffers and is synchronous, on the scene's own stream; any n, in chunks of at
+ * most 2^19 rays (RTCORE_QUERY_CHUNK sets another size), two of them resident with the overlap of
+ * rt_query_rays; per ray it stages 72 B up (64 B when t_max is NULL) and 1 B down.
+ * rt_occluded_rays_device takes device buffers and is asynchronous on `stream`, ordered like the
+ * device-resident renders (the per-scene scratch rule of the preamble); launches are split at 2^30 rays.
+ */
+int rt_occluded_rays(rt_scene* scene, int32_t mode, const rt_ray* rays, const double* t_max, int64_t n,
+                     uint8_t* occluded_out);
+int rt_occluded_rays_device(rt_scene* scene, int32_t mode, const rt_ray* d_rays, const double* d_t_max, int64_t n,
+                            uint8_t* d_occluded, void* stream);
 
 /* ------------------------------------------------------------ selection pass --- */
 /* DebugRaycaster's Selection mode (DebugRaycaster.cs:174-192): the overlay that shows only what

@@ -170,7 +170,8 @@ HIT_DTYPE = np.dtype([
 # entry points added under an unchanged ABI version: bound when the library has them (an older build
 # named by RTCORE_LIB may not)
 _OPTIONAL = ("rt_query_rays", "rt_query_rays_device", "rt_camera_rays", "rt_select_pixels", "rt_select_pixels_device",
-             "rt_select_rays", "rt_select_rays_device", "rt_render_rays", "rt_render_rays_device")
+             "rt_select_rays", "rt_select_rays_device", "rt_render_rays", "rt_render_rays_device",
+             "rt_occluded_rays", "rt_occluded_rays_device")
 
 _lib: Optional[C.CDLL] = None
 
@@ -273,6 +274,9 @@ def load_library(path: str = "") -> C.CDLL:
                                      P(rt_color), P(C.c_uint32), P(C.c_uint32), P(C.c_uint64)]),
         "rt_render_rays_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64,
                                             C.c_uint64] + [C.c_void_p] * 4 + [C.c_void_p]),
+        "rt_occluded_rays": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+        "rt_occluded_rays_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                              C.c_void_p]),
     }
     for name, (res, args) in sig.items():
         if (name.startswith("rt_debug_") or name in _OPTIONAL) and not hasattr(lib, name):
@@ -453,6 +457,32 @@ def _pack_items(items) -> np.ndarray:
 
 def _rays_arg(origins, directions) -> np.ndarray:
     return np.ascontiguousarray(origins, RAY_DTYPE) if directions is None else _pack_rays(origins, directions)
+
+
+def segment_rays(points_a, points_b) -> Tuple[np.ndarray, np.ndarray]:
+    """The segments a -> b as rays for occluded_rays (GpuRaytracer.visible): points as (..., 3) arrays of
+    one shape.  Returns a RAY_DTYPE array of the leading shape with origin a and direction
+    normalize(b - a), and t_max = |b - a| (fp64, hypot-scaled so that tiny and huge separations keep
+    their precision).  Coincident points give a zero direction and t_max 0: an empty segment, which
+    nothing occludes."""
+    a = np.asarray(points_a, np.float64)
+    b = np.asarray(points_b, np.float64)
+    if a.shape != b.shape or a.ndim < 1 or a.shape[-1] != 3:
+        raise ValueError("points_a and points_b must be (..., 3) arrays of the same shape")
+    v = b - a
+    scale = np.max(np.abs(v), axis=-1)
+    safe = np.where(scale > 0, scale, 1.0)
+    u = v / safe[..., None]
+    norm = np.sqrt(np.sum(u * u, axis=-1))
+    t_max = np.where(scale > 0, norm * safe, 0.0)
+    d = u / np.where(scale > 0, norm, 1.0)[..., None]
+    # one more normalisation step: |d| = 1 to the last bit or two
+    d = d / np.where(scale > 0, np.sqrt(np.sum(d * d, axis=-1)), 1.0)[..., None]
+    rays = np.zeros(a.shape[:-1], RAY_DTYPE)
+    rays["origin"][..., :3] = a
+    rays["origin"][..., 3] = 1.0
+    rays["direction"][..., :3] = d
+    return rays, t_max
 
 
 def select_rays_host(prims: Sequence[rt_prim], items, origins, directions=None) -> np.ndarray:
@@ -642,6 +672,41 @@ class GpuRaytracer:
         d_hits (e.g. torch data_ptr()) on `stream` (a hipStream_t as an integer, 0 = the default stream)."""
         _check(self.lib.rt_query_rays_device(self.handle, RT_QUERY_EXACT if exact else RT_QUERY_FAST, C.c_void_p(d_rays),
                                              n, C.c_void_p(d_hits), C.c_void_p(stream)))
+
+    def occluded_rays(self, origins, directions=None, t_max=None, exact: bool = False) -> np.ndarray:
+        """rt_occluded_rays (any-hit visibility): True where Scene.RayTrace(ray, null) hits something at a
+        distance < t_max.  Rays as for query_rays; t_max None (+inf for every ray), a scalar, or an array
+        of the rays' shape.  A NaN or non-positive t_max, and an invalid ray, give False.  exact: the fp64
+        reference query; else the path kernels' fp32 tests, unordered and ending at the first hit.
+        Returns a bool array of the rays' shape."""
+        rays = _rays_arg(origins, directions)
+        if t_max is None:
+            tm, ptr = None, None
+        else:
+            tm = np.ascontiguousarray(np.broadcast_to(np.asarray(t_max, np.float64), rays.shape))
+            ptr = tm.ctypes.data_as(C.c_void_p)
+        out = np.zeros(rays.shape, np.uint8)
+        _check(self.lib.rt_occluded_rays(self.handle, RT_QUERY_EXACT if exact else RT_QUERY_FAST,
+                                         rays.ctypes.data_as(C.c_void_p), ptr, rays.size, out.ctypes.data_as(C.c_void_p)))
+        return out.view(np.bool_)
+
+    def occluded_rays_device(self, d_rays: int, d_t_max: int, n: int, d_out: int, exact: bool = False, stream: int = 0) -> None:
+        """rt_occluded_rays_device: asynchronous query of n rt_ray at device pointer d_rays, bounded by the
+        n doubles at d_t_max (0: unbounded), into n bytes at d_out (0 / 1; exact: 255 on a traversal-stack
+        overflow) on `stream` (a hipStream_t as an integer, 0 = the default stream)."""
+        _check(self.lib.rt_occluded_rays_device(self.handle, RT_QUERY_EXACT if exact else RT_QUERY_FAST, C.c_void_p(d_rays),
+                                                C.c_void_p(d_t_max) if d_t_max else None, n, C.c_void_p(d_out),
+                                                C.c_void_p(stream)))
+
+    def visible(self, points_a, points_b, exact: bool = False) -> np.ndarray:
+        """True where nothing lies on the segment from points_a[i] to points_b[i] ((..., 3) arrays of one
+        shape): occluded_rays with direction normalize(b - a) and t_max = |b - a| (segment_rays), negated.
+        Coincident points count as visible.  The segment is taken as given: a far point that lies on a
+        surface is hidden by that surface whenever rounding puts the hit just short of |b - a|, and a
+        near point on a surface by its own, unless the caller shortens the segment or offsets its ends
+        (e.g. a + eps * n, and t_max * (1 - eps))."""
+        rays, t_max = segment_rays(points_a, points_b)
+        return ~self.occluded_rays(rays, None, t_max, exact=exact)
 
     def render_rays(self, origins, directions, spp: int, seed: int, sample_base: int = 0, stream_base: int = 0,
                     normalize: bool = False, out=None):

@@ -1,5 +1,6 @@
 // api_query.hip -- the C ABI's ray queries (include/rtcore.h, "ray queries"): Scene.RayTrace(ray, null)
-// (Scene.cs:113-120) for rays the caller brings, and the camera's own rays on the host.
+// (Scene.cs:113-120) for rays the caller brings, and the camera's own rays on the host; and "occlusion
+// queries": whether that query has a hit nearer than a bound, by an any-hit traversal.
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
@@ -11,20 +12,17 @@ namespace {
 constexpr int64_t kQueryChunk = 1 << 19;    // rays of one chunk of rt_query_rays; two chunks are resident
 constexpr int64_t kQueryLaunchMax = 1 << 30; // rays of one launch (32-bit ray indices and dispenser)
 
-// One launch over n <= kQueryLaunchMax rays on `st`, after the stream ordering is settled.
-int launch_rays(rt_scene* s, int32_t mode, const rt_ray* d_rays, unsigned n, rt_hit* d_hits, hipStream_t st)
+// The generic kernel of the scene's traversal mode (path_variant's numbering).
+int query_kernel(const rt_scene* s) { return s->resolved == RT_TRAVERSAL_BVH ? 3 : s->resolved == RT_TRAVERSAL_GROUPED ? 1 : 0; }
+
+// The RT_QUERY_FAST launch record of n rays for that kernel (unstaged records) and its grid; the BVH
+// kernel's ray dispenser is zeroed on `st` and its overflow area reserved.
+int fill_query(rt_scene* s, int kernel, int blocks_per_cu, const rt_ray* d_rays, unsigned n, hipStream_t st, QueryParams& p,
+               int& grid)
 {
-    if (mode == RT_QUERY_EXACT) {
-        HIP_TRY(launch_query_exact(s->dev, d_rays, n, d_hits, st));
-        return RT_OK;
-    }
-    // the generic kernel of the scene's traversal mode (path_variant's numbering), unstaged records
-    const int kernel = s->resolved == RT_TRAVERSAL_BVH ? 3 : s->resolved == RT_TRAVERSAL_GROUPED ? 1 : 0;
     PathParams h{};
     fill_launch(s->dev, path_variant(kernel, false), h);
-    QueryParams p{};
     p.rays = reinterpret_cast<const double2*>(d_rays);
-    p.hits = reinterpret_cast<float4*>(d_hits);
     p.n = n;
     p.scene = h.scene;
     p.tests = h.tests;
@@ -39,7 +37,7 @@ int launch_rays(rt_scene* s, int32_t mode, const rt_ray* d_rays, unsigned n, rt_
     p.xf = h.xf;
     p.vnormals = h.vnormals;
     const int blocks = (int)((n + 255u) / 256u);
-    int grid = std::min(blocks, s->n_cu * query_blocks_per_cu(kernel));
+    grid = std::min(blocks, s->n_cu * blocks_per_cu);
     if (kernel == 3) {
         HIP_TRY(s->stack_ovf.reserve((size_t)grid * 256 * kStackOverflow));
         HIP_TRY(s->counter.reserve(1));
@@ -49,7 +47,47 @@ int launch_rays(rt_scene* s, int32_t mode, const rt_ray* d_rays, unsigned n, rt_
         p.spec = 16;
         if (const char* e = getenv("RTCORE_BVH_SPEC")) p.spec = std::max(1, std::min(64, atoi(e)));
     }
+    return RT_OK;
+}
+
+// One launch over n <= kQueryLaunchMax rays on `st`, after the stream ordering is settled.
+int launch_rays(rt_scene* s, int32_t mode, const rt_ray* d_rays, unsigned n, rt_hit* d_hits, hipStream_t st)
+{
+    if (mode == RT_QUERY_EXACT) {
+        HIP_TRY(launch_query_exact(s->dev, d_rays, n, d_hits, st));
+        return RT_OK;
+    }
+    const int kernel = query_kernel(s);
+    QueryParams p{};
+    int grid = 0;
+    const int rc = fill_query(s, kernel, query_blocks_per_cu(kernel), d_rays, n, st, p, grid);
+    if (rc != RT_OK) return rc;
+    p.hits = reinterpret_cast<float4*>(d_hits);
     HIP_TRY(launch_query(p, kernel, grid, st));
+    return RT_OK;
+}
+
+// rt_occluded_rays: one launch over n <= kQueryLaunchMax segments (d_t_max null: rays).
+int launch_segments(rt_scene* s, int32_t mode, const rt_ray* d_rays, const double* d_t_max, unsigned n,
+                    unsigned char* d_out, hipStream_t st)
+{
+    if (mode == RT_QUERY_EXACT) {
+        HIP_TRY(launch_occluded_exact(s->dev, d_rays, d_t_max, n, d_out, st));
+        return RT_OK;
+    }
+    const int kernel = query_kernel(s);
+    OccludedParams p{};
+    int grid = 0;
+    const int rc = fill_query(s, kernel, occluded_blocks_per_cu(kernel), d_rays, n, st, p.q, grid);
+    if (rc != RT_OK) return rc;
+    p.t_max = d_t_max;
+    p.out = d_out;
+    // the records outside the main loop (planes; BVH: and the outer group) first: measured at or below
+    // testing them last in every workload of DESIGN.md 4.5; RTCORE_OCCLUDED_EARLY=0 tests them last (BVH:
+    // only for a ray the tree did not answer), for A/B measurements
+    p.early = 1;
+    if (const char* e = getenv("RTCORE_OCCLUDED_EARLY")) p.early = atoi(e) != 0;
+    HIP_TRY(launch_occluded(p, kernel, grid, st));
     return RT_OK;
 }
 
@@ -191,6 +229,120 @@ int rt_query_rays(rt_scene* s, int32_t mode, const rt_ray* rays, int64_t n, rt_h
     if (rc != RT_OK) return rc;
     if (overflow) {
         set_error("rt_query_rays: the reference BVH is deeper than the exact kernel's traversal stack");
+        return RT_ERR_STATE;
+    }
+    return RT_OK;
+}
+
+int rt_occluded_rays_device(rt_scene* s, int32_t mode, const rt_ray* d_rays, const double* d_t_max, int64_t n,
+                            uint8_t* d_occluded, void* stream)
+{
+    bool empty;
+    int rc = check_query(s, mode, d_rays, n, d_occluded, "rt_occluded_rays_device", &empty);
+    if (rc != RT_OK || empty) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (mode == RT_QUERY_EXACT) {
+        rc = ensure_ref_bvh(s);
+        if (rc != RT_OK) return rc;
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    if (s->any_op && st != s->last_stream) HIP_TRY(hipStreamWaitEvent(st, s->done_ev, 0));
+    for (int64_t a = 0; a < n; a += kQueryLaunchMax) {
+        rc = launch_segments(s, mode, d_rays + a, d_t_max ? d_t_max + a : nullptr, (unsigned)std::min(kQueryLaunchMax, n - a),
+                             d_occluded + a, st);
+        if (rc != RT_OK) return rc;
+    }
+    return end_op(s, st);
+}
+
+// rt_query_rays' pipeline (above) with 72 B up (64 B without t_max) and 1 B down per ray: the pinned
+// staging holds the two answer slots (at the offsets queue_copy gives them), then the two ray slots
+// and the two slots of segment ends.
+int rt_occluded_rays(rt_scene* s, int32_t mode, const rt_ray* rays, const double* t_max, int64_t n, uint8_t* occluded_out)
+{
+    bool empty;
+    int rc = check_query(s, mode, rays, n, occluded_out, "rt_occluded_rays", &empty);
+    if (rc != RT_OK || empty) return rc;
+    int64_t chunk = kQueryChunk;
+    if (const char* e = getenv("RTCORE_QUERY_CHUNK")) chunk = std::max<int64_t>(1, std::min<int64_t>(kQueryChunk, atoll(e)));
+    chunk = std::min(chunk, n);
+    if (mode == RT_QUERY_EXACT) {
+        rc = ensure_ref_bvh(s);
+        if (rc != RT_OK) return rc;
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    if (!s->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
+    HIP_TRY(hipStreamSynchronize(s->copy_stream)); // (copies a failed call left behind: see rt_render_tile)
+    const size_t C = (size_t)chunk;
+    HIP_TRY(s->query_rays.reserve(2 * C));
+    HIP_TRY(s->occluded_out.reserve(2 * C));
+    if (t_max) HIP_TRY(s->occluded_t_max.reserve(2 * C));
+    const size_t rays_at = (2 * C + 63) & ~(size_t)63;
+    HIP_TRY(s->stage.reserve(rays_at + 2 * C * (sizeof(rt_ray) + sizeof(double))));
+    rt_ray* stage_rays = reinterpret_cast<rt_ray*>(s->stage.p + rays_at);
+    double* stage_t = reinterpret_cast<double*>(stage_rays + 2 * C);
+    for (int j = 0; j < 2; j++) {
+        if (!s->query_up_ev[j]) HIP_TRY(hipEventCreateWithFlags(&s->query_up_ev[j], hipEventDisableTiming));
+        if (!s->band_ev[j]) HIP_TRY(hipEventCreateWithFlags(&s->band_ev[j], hipEventDisableTiming));
+    }
+    hipStream_t st = s->stream;
+    if (s->any_op && st != s->last_stream) HIP_TRY(hipStreamWaitEvent(st, s->done_ev, 0));
+    const int64_t K = (n + chunk - 1) / chunk;
+    auto count = [&](int64_t k) { return (size_t)std::min(chunk, n - k * chunk); };
+    auto upload = [&](int64_t k) -> int {
+        const size_t m = count(k), slot = (size_t)(k & 1) * C;
+        const rt_ray* src = rays + k * chunk;
+        const double* src_t = t_max ? t_max + k * chunk : nullptr;
+        parallel_ranges(m, 65536, [&](size_t a, size_t b) {
+            std::memcpy(stage_rays + slot + a, src + a, (b - a) * sizeof(rt_ray));
+            if (src_t) std::memcpy(stage_t + slot + a, src_t + a, (b - a) * sizeof(double));
+        });
+        HIP_TRY(hipMemcpyAsync(s->query_rays.p + slot, stage_rays + slot, m * sizeof(rt_ray), hipMemcpyHostToDevice,
+                               s->copy_stream));
+        if (src_t)
+            HIP_TRY(hipMemcpyAsync(s->occluded_t_max.p + slot, stage_t + slot, m * sizeof(double), hipMemcpyHostToDevice,
+                                   s->copy_stream));
+        HIP_TRY(hipEventRecord(s->query_up_ev[k & 1], s->copy_stream));
+        return RT_OK;
+    };
+    std::atomic<bool> overflow{false};
+    CopyPlan plans[2];
+    auto consume = [&](int64_t k) -> int {
+        const size_t slot = (size_t)(k & 1) * C;
+        uint8_t* dst = occluded_out + k * chunk;
+        return consume_copies(s, plans[k & 1], [&](const unsigned char* stage, size_t a, size_t b) {
+            std::memcpy(dst + (a - slot), stage + a, b - a);
+            if (mode == RT_QUERY_EXACT && std::memchr(stage + a, 255, b - a)) overflow = true;
+        });
+    };
+    rc = upload(0);
+    if (rc != RT_OK) return rc;
+    for (int64_t k = 0; k < K; k++) {
+        const size_t m = count(k), slot = (size_t)(k & 1) * C;
+        HIP_TRY(hipStreamWaitEvent(st, s->query_up_ev[k & 1], 0));
+        rc = launch_segments(s, mode, s->query_rays.p + slot, t_max ? s->occluded_t_max.p + slot : nullptr, (unsigned)m,
+                             s->occluded_out.p + slot, st);
+        if (rc != RT_OK) return rc;
+        HIP_TRY(hipEventRecord(s->band_ev[k & 1], st));
+        if (k >= 1) {
+            rc = consume(k - 1);
+            if (rc != RT_OK) return rc;
+        }
+        if (k + 1 < K) {
+            rc = upload(k + 1);
+            if (rc != RT_OK) return rc;
+        }
+        HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->band_ev[k & 1], 0));
+        plans[k & 1] = CopyPlan{};
+        rc = queue_copy(s, plans[k & 1], s->occluded_out.p, slot, slot + m, 1, 1, s->copy_stream);
+        if (rc != RT_OK) return rc;
+    }
+    rc = end_op(s, st);
+    if (rc != RT_OK) return rc;
+    rc = consume(K - 1);
+    if (rc != RT_OK) return rc;
+    if (overflow) {
+        set_error("rt_occluded_rays: the reference BVH is deeper than the exact kernel's traversal stack");
         return RT_ERR_STATE;
     }
     return RT_OK;

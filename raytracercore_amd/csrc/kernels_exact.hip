@@ -223,6 +223,29 @@ __global__ void __launch_bounds__(64) query_exact_kernel(DevScene s, const doubl
     hits[3 * (size_t)i + 2] = make_uint4(0u, 0u, 0u, 0u);
 }
 
+// rt_occluded_rays, RT_QUERY_EXACT: the same query with its Hit.Distance held against t_max in fp64
+// (strictly below: RayTracePrimitives' own comparison), one answer byte per ray.  No early exit: this
+// is the reference's answer.  An invalid ray (ray_valid_d) or an empty segment (t_max NaN or <= 0)
+// gives 0 without a query; 255 reports a traversal-stack overflow.
+__global__ void __launch_bounds__(64) occluded_exact_kernel(DevScene s, const double2* __restrict__ rays,
+                                                            const double* __restrict__ t_max, unsigned n,
+                                                            unsigned char* __restrict__ out)
+{
+    const unsigned i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    const double2 r0 = rays[4 * (size_t)i], r1 = rays[4 * (size_t)i + 1], r2 = rays[4 * (size_t)i + 2],
+                  r3 = rays[4 * (size_t)i + 3];
+    const Vec4d o{r0.x, r0.y, r1.x, r1.y}, d{r2.x, r2.y, r3.x, r3.y};
+    const double tm = t_max ? t_max[i] : __builtin_huge_val();
+    unsigned char r = 0;
+    if (ray_valid_d(o, d) && tm > 0.0) {
+        HitD h;
+        const int id = ref_raytrace_hit(s, o, d, h);
+        r = id == -2 ? 255 : (id >= 0 && h.dist < tm) ? 1 : 0;
+    }
+    out[i] = r;
+}
+
 // DebugRaycaster Selection mode (rt_select_pixels, rt_select_rays): select_items (rt_exact_prims.h)
 // for one ray per lane.  The item loop is the same for every lane of the wave (no early exit, no
 // LDS); a result is one 16-B row (rt_selection: item, 0, distance), written with one store.
@@ -281,6 +304,15 @@ hipError_t launch_query_exact(const DevScene& s, const rt_ray* d_rays, unsigned 
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(query_exact_kernel, dim3((n + 63u) / 64u), dim3(64), 0, stream, s,
                        reinterpret_cast<const double2*>(d_rays), n, reinterpret_cast<uint4*>(d_hits));
+    return hipGetLastError();
+}
+
+hipError_t launch_occluded_exact(const DevScene& s, const rt_ray* d_rays, const double* d_t_max, unsigned n,
+                                 unsigned char* d_out, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(occluded_exact_kernel, dim3((n + 63u) / 64u), dim3(64), 0, stream, s,
+                       reinterpret_cast<const double2*>(d_rays), d_t_max, n, d_out);
     return hipGetLastError();
 }
 

@@ -349,7 +349,11 @@ __device__ __forceinline__ bool slab(float4 lo, float4 hi, V3 oi, V3 id, float t
 // index, so the scene-specialised build still unrolls the loop.
 // The record pointers are in the constant address space (RT_AS_CONST) or generic.
 // boxes: the frame array viewed as BoxRecs (they share it).
-template <bool CULL, bool STATS, class SceneT, class GroupP, class TestP, class RectP, class FrameP, class BoxP, class XfP>
+// ANY (rt_occluded_rays): the query is over once b.sg >= 0.  A lane with its answer no longer votes
+// for a group's box, and the wave leaves as soon as no active lane is without one: between groups
+// in the grouped order, between the record classes in the flat one.  The bounds stay wave-uniform.
+template <bool CULL, bool STATS, bool ANY = false, class SceneT, class GroupP, class TestP, class RectP, class FrameP,
+          class BoxP, class XfP>
 __device__ __forceinline__ void trace_brute(const SceneT& s, GroupP groups, TestP tests, RectP rects, FrameP frames,
                                             BoxP boxes, XfP xf, V3 o, V3 d, int prev, Best& b, unsigned& n_flat,
                                             unsigned& n_sph, unsigned& n_node)
@@ -367,7 +371,7 @@ __device__ __forceinline__ void trace_brute(const SceneT& s, GroupP groups, Test
         if (CULL) {
             if (STATS) n_node++; // the group's box: a node of a shallow tree (SURVEY 8(d) N_node)
             float tn;
-            if (!__any(slab<true>(G.lo, G.hi, oi, id, b.t, tn))) {
+            if (!__any((!ANY || b.sg < 0) && slab<true>(G.lo, G.hi, oi, id, b.t, tn))) {
                 skip_to = g + 1 + G.skip;
                 continue;
             }
@@ -386,6 +390,7 @@ __device__ __forceinline__ void trace_brute(const SceneT& s, GroupP groups, Test
             const BoxRec B = boxes[j];
             hit_box<false>(B, o, d, id, oi, prev, b);
         }
+        if (ANY && !CULL && !__any(b.sg < 0)) return;
         // rectangles in a common affine frame: the ray mapped once, then the same rect tests (t is
         // invariant under the map; a local d of 0 gives an infinite or NaN t, which never hits)
         for (int f = G.frame_first; f < G.frame_first + G.n_frames; f++) {
@@ -404,6 +409,7 @@ __device__ __forceinline__ void trace_brute(const SceneT& s, GroupP groups, Test
                 hit_box<true>(B, lo, ld, lid, lo, prev, b);
             }
         }
+        if (ANY && !CULL && !__any(b.sg < 0)) return;
         int i = __float_as_int(G.hi.w);
         int end = i + (G.n_tri_sph & 0xFFFF);
         if (i < end) {
@@ -414,6 +420,7 @@ __device__ __forceinline__ void trace_brute(const SceneT& s, GroupP groups, Test
                 cur = nxt;
             }
         }
+        if (ANY && !CULL && !__any(b.sg < 0)) return;
         end = i + (G.n_tri_sph >> 16);
         if (i < end) {
             TestRec cur = tests[i];
@@ -423,6 +430,7 @@ __device__ __forceinline__ void trace_brute(const SceneT& s, GroupP groups, Test
                 cur = nxt;
             }
         }
+        if (ANY && CULL && !__any(b.sg < 0)) return;
     }
 }
 
@@ -2175,6 +2183,222 @@ __global__ void __launch_bounds__(256, RT_BVH_WAVES) query_bvh_kernel(QueryParam
     }
 }
 
+// ---- rt_occluded_rays, RT_QUERY_FAST: is anything on the segment [origin, origin + t_max d) ---------
+// The per-primitive tests accept a hit only when t < b.t, so the closest-hit code started from
+// Best{(float)t_max, -1} is the bounded query and b.sg >= 0 its answer; nothing closer is looked for.
+// hit_rect and hit_box compare bit patterns and need b.t >= 0: an empty segment (t_max NaN, <= 0 or
+// rounding to 0 in fp32) is decided where t_max is loaded, like an invalid ray.
+
+// The fp32 end of ray i's segment; not above 0 (NaN included): the segment is empty.
+__device__ __forceinline__ float load_t_max(const double* __restrict__ t_max, unsigned i)
+{
+    return t_max ? (float)t_max[i] : __builtin_huge_valf();
+}
+
+template <class TestP>
+__device__ __forceinline__ void occluded_planes(const PathScene& s, TestP tests, V3 o, V3 d, Best& b)
+{
+    for (int k = s.n_bvh; k < s.n_bvh + s.n_pln; k++) {
+        const TestRec tr = tests[k];
+        hit_plane<true>(tr, k, o, d, -1, b);
+    }
+}
+
+// Brute force (CULL: the grouped order): query_brute_kernel's loop around trace_brute's any-hit form.
+template <bool CULL>
+__global__ void __launch_bounds__(256, CULL ? RT_GROUPED_WAVES : RT_PATH_WAVES) occluded_brute_kernel(OccludedParams P)
+{
+    const QueryParams& p = P.q;
+    const auto tests = (const RT_AS_CONST TestRec*)p.tests;
+    const auto rects = (const RT_AS_CONST RectRec*)p.rects;
+    const auto frames = (const RT_AS_CONST FrameRec*)p.frames;
+    const auto boxes = (const RT_AS_CONST BoxRec*)p.frames;
+    const auto groups = (const RT_AS_CONST GroupRec*)p.groups;
+    const auto xf = (const RT_AS_CONST XformF*)p.xf;
+    for (unsigned base = blockIdx.x * 256u; base < p.n; base += gridDim.x * 256u) {
+        const unsigned i = base + threadIdx.x;
+        if (i >= p.n) continue;
+        const QueryRay q = load_query_ray(p.rays, i);
+        const float tm = load_t_max(P.t_max, i);
+        Best b{tm, -1};
+        if (q.valid & (tm > 0.0f)) {
+            unsigned n_flat = 0, n_sph = 0, n_node = 0;
+            if (P.early) occluded_planes(p.scene, tests, q.o, q.d, b);
+            if (__any(b.sg < 0)) {
+                trace_brute<CULL, false, true>(p.scene, groups, tests, rects, frames, boxes, xf, q.o, q.d, -1, b, n_flat,
+                                               n_sph, n_node);
+                if (!P.early) occluded_planes(p.scene, tests, q.o, q.d, b);
+            }
+        }
+        P.out[i] = b.sg >= 0 ? 1 : 0;
+    }
+}
+
+// One visit of a 4-wide node for an any-hit query: wide_visit's four slab tests against the segment's
+// end, without the sorting network (no child is nearer in any sense that matters).  The first hit
+// child in slot order is entered and the other hit children are pushed, to be popped in slot order.
+template <int STACK>
+__device__ __forceinline__ void any_visit(const Node4Q& q, V3 id, V3 oi, float best, int& ref, int& sp,
+                                          const TravStack& stk, bool& pop)
+{
+    const uint32_t ex = __float_as_uint(q.a.w);
+    const float ax = __builtin_amdgcn_ldexpf(id.x, (int)(ex & 255u) - 128);
+    const float ay = __builtin_amdgcn_ldexpf(id.y, (int)((ex >> 8) & 255u) - 128);
+    const float az = __builtin_amdgcn_ldexpf(id.z, (int)((ex >> 16) & 255u) - 128);
+    const float bx = fmaf(q.a.x, id.x, -oi.x), by = fmaf(q.a.y, id.y, -oi.y), bz = fmaf(q.a.z, id.z, -oi.z);
+    const uint32_t lx = __float_as_uint(q.b.x), hx = __float_as_uint(q.b.y);
+    const uint32_t ly = __float_as_uint(q.b.z), hy = __float_as_uint(q.b.w);
+    const uint32_t lz = __float_as_uint(q.c.x), hz = __float_as_uint(q.c.y);
+    const bool px = id.x >= 0.0f, py = id.y >= 0.0f, pz = id.z >= 0.0f; // near / far planes by the direction's sign
+    const uint32_t nx = px ? lx : hx, fx = px ? hx : lx;
+    const uint32_t ny = py ? ly : hy, fy = py ? hy : ly;
+    const uint32_t nz = pz ? lz : hz, fz = pz ? hz : lz;
+    const int nc = __float_as_int(q.d.z);
+    const int r0 = __float_as_int(q.c.z), r1 = __float_as_int(q.c.w), r2 = __float_as_int(q.d.x), r3 = __float_as_int(q.d.y);
+    const float tmax_best = best * 1.00000024f;
+    bool h0, h1, h2, h3;
+#define RT_ANY_CHILD(K, H)                                                                                        \
+    {                                                                                                             \
+        const float tmin = fmaxf(fmaxf(fmaxf(fmaf(ubyte(nx, K), ax, bx), fmaf(ubyte(ny, K), ay, by)),              \
+                                       fmaf(ubyte(nz, K), az, bz)), 0.0f);                                         \
+        const float tmax = fminf(fminf(fmaf(ubyte(fx, K), ax, bx), fmaf(ubyte(fy, K), ay, by)),                   \
+                                 fmaf(ubyte(fz, K), az, bz));                                                      \
+        H = (K < nc) & (tmin <= fminf(tmax * 1.00000024f, tmax_best));                                            \
+    } // the same test as RT_WIDE_CHILD (wide_visit)
+    RT_ANY_CHILD(0, h0)
+    RT_ANY_CHILD(1, h1)
+    RT_ANY_CHILD(2, h2)
+    RT_ANY_CHILD(3, h3)
+#undef RT_ANY_CHILD
+    if (h0 | h1 | h2 | h3) {
+        if (h3 & (h0 | h1 | h2)) push<STACK>(stk, sp, r3);
+        if (h2 & (h0 | h1)) push<STACK>(stk, sp, r2);
+        if (h1 & h0) push<STACK>(stk, sp, r1);
+        ref = h0 ? r0 : h1 ? r1 : h2 ? r2 : r3;
+        pop = false;
+    }
+}
+
+// The wide BVH: query_bvh_kernel's speculative loop.  A lane's query ends the moment a leaf step
+// gives it a hit, and the lane takes its next ray at the next ballot.  The records outside the tree
+// (the outer group and the planes) are tested when the ray is loaded (P.early) or when the tree gave
+// no hit.  A visit pushes at most (children - 1) entries per level, as wide_visit does, so the host's
+// bound on the stack depth holds for any order of descent.
+template <int STACK>
+__global__ void __launch_bounds__(256, RT_BVH_WAVES) occluded_bvh_kernel(OccludedParams P)
+{
+    __shared__ int stack_mem[STACK * 256];
+    const QueryParams& p = P.q;
+    const TravStack stk = make_stack(stack_mem, p.stack_ovf);
+    const int lane = threadIdx.x & 63;
+    const RT_AS_CONST TestRec* tests = (const RT_AS_CONST TestRec*)p.tests;
+    const RT_AS_CONST float4* rows = (const RT_AS_CONST float4*)p.rows;
+    const RT_AS_CONST Node4Q* nodes4 = (const RT_AS_CONST Node4Q*)p.nodes4;
+    const RT_AS_CONST XformF* xf = (const RT_AS_CONST XformF*)p.xf;
+    bool trav = false, more = false, exhausted = false;
+    int ref = 0, sp = 0, pend = -1;
+    unsigned n_tri = 0, n_sph = 0;
+    unsigned idx = 0, pool_next = 0, pool_end = 0; // the wave's pool of ray indices (uniform)
+    V3 o{0, 0, 0}, d{0, 0, 0}, id{0, 0, 0}, oi{0, 0, 0};
+    Best b{__builtin_huge_valf(), -1};
+    auto outside = [&]() { // the records outside the tree
+        if (p.scene.n_groups > 0)
+            test_outer<false>((const RT_AS_CONST GroupRec*)p.groups, (const RT_AS_CONST RectRec*)p.rects,
+                              (const RT_AS_CONST BoxRec*)p.frames, o, d, -1, b, n_tri);
+        occluded_planes(p.scene, tests, o, d, b);
+    };
+    while (true) {
+        const bool need = !trav && !exhausted;
+        const unsigned long long m = __ballot(need);
+        if (m) { // lanes without a query take the next rays (one atomic per 256 rays per wave)
+            const unsigned kk = (unsigned)__popcll(m), avail = pool_end - pool_next;
+            unsigned fresh = 0;
+            if (kk > avail) {
+                if (lane == 0) fresh = atomicAdd(p.counter, 256u);
+                fresh = __builtin_amdgcn_readfirstlane(fresh);
+            }
+            if (need) {
+                const unsigned r = (unsigned)__popcll(m & ((1ull << lane) - 1ull));
+                idx = r < avail ? pool_next + r : fresh + (r - avail);
+                if (idx >= p.n) {
+                    exhausted = true;
+                } else {
+                    const QueryRay q = load_query_ray(p.rays, idx);
+                    const float tm = load_t_max(P.t_max, idx);
+                    b = Best{tm, -1};
+                    bool open = q.valid & (tm > 0.0f);
+                    if (open) {
+                        o = q.o;
+                        d = q.d;
+                        if (P.early) {
+                            outside();
+                            open = b.sg < 0;
+                        }
+                    }
+                    if (!open) { // answered; the lane takes another ray at the next refill
+                        P.out[idx] = b.sg >= 0 ? 1 : 0;
+                    } else {
+                        id = v3(slab_rcp(d.x), slab_rcp(d.y), slab_rcp(d.z));
+                        oi = o * id;
+                        ref = p.root4;
+                        sp = 0;
+                        pend = -1;
+                        more = p.n_nodes4 > 0; // (no tree at all: only planes, and the query ends at once)
+                        if (ref < 0) {
+                            pend = ~ref;
+                            more = false;
+                        }
+                        trav = true;
+                    }
+                }
+            }
+            if (kk > avail) {
+                pool_next = fresh + (kk - avail);
+                pool_end = fresh + 256u;
+            } else {
+                pool_next += kk;
+            }
+        }
+        if (!__any(trav)) {
+            if (__any(!exhausted)) continue; // only answered rays this round: refill again
+            break;
+        }
+        const bool can_node = trav && more && ref >= 0;
+        const bool blocked = trav && pend >= 0 && !can_node;
+        const bool leaf_step = __ballot(can_node) == 0 || __popcll(__ballot(blocked)) >= p.spec;
+        if (trav) {
+            if (leaf_step) {
+                if (pend >= 0) {
+                    test_leaf<false>(tests, rows, xf, pend, o, d, -1, b, n_tri, n_sph);
+                    pend = leaf_advance(pend, RT_SPEC_PRIMS);
+                    if (b.sg >= 0) { // the answer: the rest of the leaf and of the tree is not looked at
+                        pend = -1;
+                        more = false;
+                    }
+                }
+            } else if (can_node) {
+                bool pop = true;
+                const Node4Q node = nodes4[ref];
+                any_visit<STACK>(node, id, oi, b.t, ref, sp, stk, pop);
+                if (pop) {
+                    if (sp > 0) ref = pop_ref<STACK>(stk, sp);
+                    else more = false;
+                }
+            }
+            if (more && ref < 0 && pend < 0) {
+                pend = ~ref;
+                if (sp > 0) ref = pop_ref<STACK>(stk, sp);
+                else more = false;
+            }
+            if (!more && pend < 0) { // the query ended
+                trav = false;
+                if (!P.early && b.sg < 0) outside();
+                P.out[idx] = b.sg >= 0 ? 1 : 0;
+            }
+        }
+    }
+}
+
 // plane: element stride between the R, G and B planes of sum (>= w*h; a gather slot may be taller
 // than the band set written into it)
 __global__ void accumulate_kernel(PathParams p, double* sum, uint32_t* samples, uint32_t* misses, size_t plane)
@@ -2654,6 +2878,29 @@ int query_blocks_per_cu(int kernel)
 hipError_t launch_query(const QueryParams& p, int kernel, int grid_blocks, hipStream_t stream)
 {
     hipLaunchKernelGGL(pick_query(kernel), dim3(grid_blocks), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+using OccludedKernel = void (*)(OccludedParams);
+OccludedKernel pick_occluded(int kernel)
+{
+    if (kernel == 3) return occluded_bvh_kernel<RT_WIDE_STACK>;
+    return kernel == 1 ? occluded_brute_kernel<true> : occluded_brute_kernel<false>;
+}
+
+int occluded_blocks_per_cu(int kernel)
+{
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(pick_occluded(kernel)), 256, 0) !=
+            hipSuccess ||
+        n < 1)
+        n = 1;
+    return n;
+}
+
+hipError_t launch_occluded(const OccludedParams& p, int kernel, int grid_blocks, hipStream_t stream)
+{
+    hipLaunchKernelGGL(pick_occluded(kernel), dim3(grid_blocks), dim3(256), 0, stream, p);
     return hipGetLastError();
 }
 

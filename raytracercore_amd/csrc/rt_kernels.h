@@ -172,6 +172,21 @@ hipError_t launch_query(const QueryParams& p, int kernel, int grid_blocks, hipSt
 // RT_QUERY_EXACT (kernels_exact.hip): the fp64 reference query, one ray per lane; prim_id -2 where
 // the reference BVH is deeper than the kernel's traversal stack.
 hipError_t launch_query_exact(const DevScene& s, const rt_ray* d_rays, unsigned n, rt_hit* d_hits, hipStream_t stream);
+// rt_occluded_rays: the scene and the rays as rt_query_rays' kernels take them (q.hits unused), the
+// segments' ends and one answer byte per ray.
+struct OccludedParams {
+    QueryParams q;
+    const double* t_max;        // per ray, or null: +inf for every ray
+    unsigned char* out;         // 0 / 1 per ray (RT_QUERY_EXACT: 255 on a traversal-stack overflow)
+    int early;                  // 1: the planes (BVH: and the outer records) are tested before the other records,
+                                // 0: after them (BVH: only when the tree gave no hit)
+};
+// RT_QUERY_FAST: kernel numbering, grids and blocks per CU as launch_query / query_blocks_per_cu.
+int occluded_blocks_per_cu(int kernel);
+hipError_t launch_occluded(const OccludedParams& p, int kernel, int grid_blocks, hipStream_t stream);
+// RT_QUERY_EXACT (kernels_exact.hip): ref_raytrace_hit's distance against t_max in fp64, one ray per lane.
+hipError_t launch_occluded_exact(const DevScene& s, const rt_ray* d_rays, const double* d_t_max, unsigned n,
+                                 unsigned char* d_out, hipStream_t stream);
 // Sets p.scene and the record pointers of the given kernel variant's slot order.
 void fill_launch(const DevScene& s, int variant, PathParams& p);
 

@@ -183,6 +183,9 @@ struct rt_scene {
     DevBuf<rt_ray> query_rays;
     DevBuf<rt_hit> query_hits;
     std::array<hipEvent_t, 2> query_up_ev{};
+    // rt_occluded_rays: two chunks of segment ends and of answer bytes (its rays share query_rays and query_up_ev)
+    DevBuf<double> occluded_t_max;
+    DevBuf<unsigned char> occluded_out;
     // rt_render_rays: two chunks of per-ray records (its rays share query_rays and query_up_ev), and
     // the blocks per CU of the RAYS instance of `rays_variant`
     DevBuf<TileRec> render_rays_recs;

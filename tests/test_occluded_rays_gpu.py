@@ -1,0 +1,407 @@
+"""rt_occluded_rays on the device: any-hit visibility for caller-supplied segments, ray by ray.
+
+O1 holds RT_QUERY_EXACT to the CPU oracle's Scene.RayTrace with the strict `<` and the bit after it.
+O2 holds RT_QUERY_FAST -- the any-hit kernels in every traversal mode and with both BVH builders -- to the
+oracle on every ray whose answer neither the fp32 rounding of the ray nor that of the distance can
+change.  O3 holds it to the closest-hit kernels of rt_query_rays, whose answer it must be.  O4 - O6: order,
+sizes, chunks, streams, degenerate input and what a call must leave alone.  O7: tools/bake_ao.py.
+
+The rays, scenes and the robust / well classification are those of tests/test_query_rays_gpu.py (copied:
+that file stays as it is): 4096 unit directions drawn from a normal distribution with seed 7, origins along
+camera 0's line of sight.  A ray is *robust* if the oracle returns the same ID for it and for the four
+rays normalize(d +- 1e-3 a), normalize(d +- 1e-3 b), a and b orthonormal to d; a robust hit is
+*well-conditioned* if across those four the oracle's distance moves by less than 1 % of max(t, 1).
+"""
+import ctypes as C
+import functools
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from oracle.oracle import OracleScene
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+N_RAYS = 4096
+
+PLANE_SPHERE = ("size 16 12\nambient color .2 .3 .4\ncamera 0 -4 3, 0 0 0, 0 0 1, 60\ndiffuse .5 .5 .5\nplane 0 0 0 1\n"
+                "sphere 0 0 1 .5\n")
+
+SCENE_NAMES = ("bounce", "die", "mesh41", "mesh71", "plane_sphere", "soup300")
+
+# the (scene, traversal mode, builder) cases of test_query_rays_gpu.py's G3
+CASES = [
+    ("bounce", "BRUTE", None), ("bounce", "GROUPED", None), ("bounce", "BVH", None),
+    ("die", "BRUTE", None), ("die", "GROUPED", None), ("die", "BVH", None),
+    ("mesh41", "GROUPED", None), ("mesh41", "BVH", "HOST"),
+    ("mesh71", "BVH", "HOST"), ("mesh71", "BVH", "GPU"),
+    ("plane_sphere", "BRUTE", None), ("plane_sphere", "BVH", None),
+    ("soup300", "BRUTE", None), ("soup300", "BVH", None),
+]
+
+INF = float("inf")
+F_EXACT = (0.5, 1.0, None, 2.0)  # None: the fp64 value after 1.0 * t
+F_FAST = (0.5, 0.9, 1.1, 2.0)    # 10 % off the hit: ~2000 x the fp32 distance bar 5.3e-5 of G3
+T_MISS = (1.0, 100.0, INF)
+
+
+@functools.lru_cache(maxsize=None)
+def _scene(name):
+    import raytracercore_amd as rc
+    from raytracercore_amd.scenes import mesh_scene_text, soup_scene_text
+
+    if name in ("bounce", "die"):
+        return rc.SceneLoader.from_file(rc.scene_path(name + ".txt"))
+    text = {"mesh41": lambda: mesh_scene_text(41, 41), "mesh71": lambda: mesh_scene_text(71, 41),
+            "plane_sphere": lambda: PLANE_SPHERE, "soup300": lambda: soup_scene_text(300, 3)}[name]()
+    return rc.SceneLoader.from_text(text)
+
+
+def _oracle(name):
+    import raytracercore_amd as rc
+
+    scene = _scene(name)
+    return OracleScene.from_abi(rc.rt_scene_params.from_buffer_copy(scene.params), list(scene.prims), list(scene.cameras))
+
+
+def _trace(orc, o, d):
+    ids, ts = np.empty(len(o), np.int32), np.empty(len(o), np.float64)
+    for i in range(len(o)):
+        ids[i], ts[i] = orc.raytrace((o[i, 0], o[i, 1], o[i, 2], 1.0), (d[i, 0], d[i, 1], d[i, 2], 0.0))
+    return ids, ts
+
+
+@functools.lru_cache(maxsize=None)
+def _rays(name):
+    """The scene's rays and the oracle's answers, computed once and shared (read-only)."""
+    cam = _scene(name).cameras[0]
+    rng = np.random.default_rng(7)
+    n = N_RAYS
+    d = rng.normal(size=(n, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    pos = np.array([cam.position.x, cam.position.y, cam.position.z])
+    look = np.array([cam.look_at.x, cam.look_at.y, cam.look_at.z])
+    o = pos + rng.uniform(0, .75, (n, 1)) * (look - pos)
+    orc = _oracle(name)
+    ids, ts = _trace(orc, o, d)
+    e = np.eye(3)[np.argmin(np.abs(d), axis=1)]
+    a = np.cross(d, e)
+    a /= np.linalg.norm(a, axis=1, keepdims=True)
+    b = np.cross(d, a)
+    robust = np.ones(n, bool)
+    moved = np.zeros(n)
+    for v in (a, -a, b, -b):
+        dp = d + 1e-3 * v
+        dp /= np.linalg.norm(dp, axis=1, keepdims=True)
+        ids_p, ts_p = _trace(orc, o, dp)
+        robust &= ids_p == ids
+        moved = np.maximum(moved, np.abs(ts_p - ts))
+    hit = ids >= 0
+    well = robust & hit & (moved < 0.01 * np.maximum(ts, 1.0))
+    # the test set cannot hollow itself out
+    assert robust.mean() >= 0.95, (name, robust.mean())
+    assert well.sum() >= 0.85 * (robust & hit).sum(), (name, well.sum(), (robust & hit).sum())
+    for arr in (o, d, ids, ts, robust, well):
+        arr.setflags(write=False)
+    return dict(o=o, d=d, ids=ids, t=ts, robust=robust, well=well)
+
+
+def _cycle(mask, values):
+    """values[k % len] for the k-th True of mask (fp64; 0 elsewhere)."""
+    out = np.zeros(len(mask))
+    out[mask] = np.asarray(values, np.float64)[np.arange(int(mask.sum())) % len(values)]
+    return out
+
+
+def _t_max(hit_mask, miss_mask, t, factors):
+    """The issue's segment ends: f * t with f cycling over `factors` on the hits of hit_mask (None: the
+    fp64 value after 1.0 * t), T_MISS cycling on the misses of miss_mask, +inf elsewhere."""
+    tm = np.full(len(t), INF)
+    k = np.arange(int(hit_mask.sum())) % len(factors)
+    th = t[hit_mask]
+    vals = np.empty(len(th))
+    for j, f in enumerate(factors):
+        sel = k == j
+        vals[sel] = np.nextafter(1.0 * th[sel], INF) if f is None else f * th[sel]
+    tm[hit_mask] = vals
+    tm[miss_mask] = _cycle(miss_mask, T_MISS)[miss_mask]
+    return tm
+
+
+def _gpu(rc, name, mode="AUTO", builder=None, size=None):
+    return rc.GpuRaytracer(_scene(name), 0, size=size, traversal=getattr(rc, "RT_TRAVERSAL_" + mode),
+                           builder=None if builder is None else getattr(rc, "RT_BVH_BUILDER_" + builder))
+
+
+def _bytes_ok(occ):
+    assert occ.dtype == np.bool_
+    assert np.isin(occ.view(np.uint8), (0, 1)).all()
+
+
+# ---------------------------------------------------------------- O1: EXACT is the oracle
+@pytest.mark.parametrize("name", SCENE_NAMES)
+def test_o1_exact_equals_the_oracle(rc, name):
+    """Every ray, robust or not: t_max at half, exactly at, one bit after and twice the oracle's distance
+    on its hits, 1 / 100 / +inf on its misses; the answer is id >= 0 and t < t_max in fp64."""
+    R = _rays(name)
+    hit = R["ids"] >= 0
+    tm = _t_max(hit, ~hit, R["t"], F_EXACT)
+    want = hit & (R["t"] < tm)
+    gpu = _gpu(rc, name)
+    got = gpu.occluded_rays(R["o"], R["d"], tm, exact=True)
+    gpu.close()
+    assert got.shape == (N_RAYS,)
+    _bytes_ok(got)
+    wrong = np.flatnonzero(got != want)
+    assert wrong.size == 0, (wrong[:8], tm[wrong[:8]], R["t"][wrong[:8]])
+    k = np.arange(int(hit.sum())) % 4
+    assert not got[hit][k == 1].any() and got[hit][k == 2].all()  # the strict `<` and the bit after it
+    assert not got[~hit].any() and hit.sum() > N_RAYS // 4
+
+
+# ---------------------------------------------------------------- O2: FAST against the oracle
+@pytest.mark.parametrize("name,mode,builder", CASES)
+def test_o2_fast_against_the_oracle(rc, name, mode, builder):
+    """Every well-conditioned robust hit with t_max 10 % or more off the oracle's distance, every robust
+    miss with t_max 1 / 100 / +inf: the any-hit kernels give the oracle's answer."""
+    R = _rays(name)
+    hit = R["ids"] >= 0
+    well, rmiss = R["well"], R["robust"] & ~hit
+    tm = _t_max(well, rmiss, R["t"], F_FAST)
+    want = hit & (R["t"] < tm)
+    gpu = _gpu(rc, name, mode, builder)
+    assert gpu.info().traversal == getattr(rc, "RT_TRAVERSAL_" + mode)
+    if name == "mesh71":
+        assert gpu.info().bvh_builder == getattr(rc, "RT_BVH_BUILDER_" + builder)
+    got = gpu.occluded_rays(R["o"], R["d"], tm)
+    gpu.close()
+    _bytes_ok(got)
+    sel = well | rmiss
+    wrong = np.flatnonzero(sel & (got != want))
+    print(f"O2 {name} {mode} {builder}: selected {sel.sum()} occluded {want[sel].sum()} free {(~want[sel]).sum()} "
+          f"mismatches {wrong.size}")
+    assert wrong.size == 0, (wrong[:8], tm[wrong[:8]], R["t"][wrong[:8]], R["ids"][wrong[:8]])
+    assert want[sel].sum() >= N_RAYS // 8 and (~want[sel]).sum() >= N_RAYS // 8
+
+
+# ---------------------------------------------------------------- O3: FAST is the closest-hit kernels' answer
+@pytest.mark.parametrize("name,mode,builder", CASES)
+def test_o3_fast_is_the_closest_hit_answer(rc, name, mode, builder):
+    """t_max = f * (fp32 distance of rt_query_rays FAST), f cycling over 0.5 / 0.9 / 1.1 / 2, +inf on its
+    misses: occluded == (prim_id >= 0 and distance < (float)t_max) on every ray.  On bounce in BRUTE (the
+    flat order: no box is culled) the edge itself: t_max == distance gives 0, the next fp32 gives 1."""
+    R = _rays(name)
+    gpu = _gpu(rc, name, mode, builder)
+    hits = gpu.query_rays(R["o"], R["d"])
+    hit = hits["prim_id"] >= 0
+    dist = hits["distance"]
+    assert np.array_equal(dist, dist.astype(np.float32).astype(np.float64))
+    tm = _t_max(hit, np.zeros(N_RAYS, bool), dist, F_FAST)
+    got = gpu.occluded_rays(R["o"], R["d"], tm)
+    want = hit & (dist < tm.astype(np.float32).astype(np.float64))
+    wrong = np.flatnonzero(got != want)
+    assert wrong.size == 0, (wrong[:8], tm[wrong[:8]], dist[wrong[:8]])
+    assert want.sum() > N_RAYS // 16 and (hit & ~want).sum() > N_RAYS // 16
+    assert np.array_equal(gpu.occluded_rays(R["o"], R["d"]), hit)  # unbounded: "does this ray hit anything"
+    if (name, mode) == ("bounce", "BRUTE"):
+        at = gpu.occluded_rays(R["o"], R["d"], np.where(hit, dist, INF))
+        after = gpu.occluded_rays(R["o"], R["d"], np.where(hit, np.nextafter(dist.astype(np.float32), np.float32(INF)), INF))
+        assert not at[hit].any() and after[hit].all()
+        assert not at[~hit].any() and not after[~hit].any()
+    gpu.close()
+
+
+# ---------------------------------------------------------------- O4: order, sizes, chunks, streams
+O4_CASES = [("mesh41", "BVH"), ("die", "GROUPED")]
+
+
+@pytest.fixture(scope="module", params=O4_CASES, ids=lambda c: "-".join(c))
+def o4(rc, request):
+    name, mode = request.param
+    gpu = _gpu(rc, name, mode)
+    R = _rays(name)
+    hit = R["ids"] >= 0
+    tm = _t_max(hit, ~hit, R["t"], F_FAST)
+    yield gpu, R, tm
+    gpu.close()
+
+
+def test_o4_order_sizes_and_chunks(rc, o4):
+    """The BVH kernel deals rays to lanes dynamically and the brute-force kernels leave a wave's loop
+    together: the answers still follow the rays' order, for every n, however the host entry cuts them."""
+    gpu, R, tm = o4
+    o, d = R["o"], R["d"]
+    for exact in (False, True):
+        full = gpu.occluded_rays(o, d, tm, exact=exact)
+        assert full.any() and not full.all()
+        perm = np.random.default_rng(1).permutation(N_RAYS)
+        assert np.array_equal(gpu.occluded_rays(o[perm], d[perm], tm[perm], exact=exact), full[perm])
+        for n in (1, 63, 64, 65, 257, 1000):
+            assert np.array_equal(gpu.occluded_rays(o[:n], d[:n], tm[:n], exact=exact), full[:n]), n
+        os.environ["RTCORE_QUERY_CHUNK"] = "256"
+        try:
+            assert np.array_equal(gpu.occluded_rays(o, d, tm, exact=exact), full)
+            assert np.array_equal(gpu.occluded_rays(o[:1000], d[:1000], exact=exact),
+                                  gpu.occluded_rays(o[:1000], d[:1000], np.full(1000, INF), exact=exact))
+        finally:
+            del os.environ["RTCORE_QUERY_CHUNK"]
+        none = gpu.occluded_rays(o, d, None, exact=exact)
+        assert np.array_equal(none, gpu.occluded_rays(o, d, np.full(N_RAYS, INF), exact=exact))
+        assert np.array_equal(none, gpu.occluded_rays(o, d, INF, exact=exact))
+        assert (none | ~full).all()  # a longer segment hides no less
+    # shaped input, shaped output
+    grid = gpu.occluded_rays(rc._pack_rays(o, d).reshape(64, 64), None, tm.reshape(64, 64))
+    assert grid.shape == (64, 64) and np.array_equal(grid.reshape(-1), gpu.occluded_rays(o, d, tm))
+    empty = gpu.occluded_rays(np.zeros((0, 3)), np.zeros((0, 3)), np.zeros(0))
+    assert empty.shape == (0,) and empty.dtype == np.bool_
+    assert gpu.lib.rt_occluded_rays(gpu.handle, rc.RT_QUERY_FAST, None, None, 0, None) == 0
+    assert gpu.lib.rt_occluded_rays_device(gpu.handle, rc.RT_QUERY_EXACT, None, None, 0, None, None) == 0
+
+
+def test_o4_device_entry_on_a_side_stream(rc, o4):
+    """rt_occluded_rays_device on a torch side stream, given as its raw pointer, equals the host entry in
+    both modes, with and without t_max; every byte of the prefilled output is rewritten with 0 or 1."""
+    import torch
+
+    gpu, R, tm = o4
+    n = 1000
+    rays = rc._pack_rays(R["o"][:n], R["d"][:n])
+    d_rays = torch.from_numpy(rays.view(np.uint8).copy()).cuda()
+    d_tm = torch.from_numpy(tm[:n].copy()).cuda()
+    side = torch.cuda.Stream()
+    for exact in (False, True):
+        for bounded in (True, False):
+            d_out = torch.full((n + 8,), 0xAB, dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            gpu.occluded_rays_device(d_rays.data_ptr(), d_tm.data_ptr() if bounded else 0, n, d_out.data_ptr(), exact=exact,
+                                     stream=side.cuda_stream)
+            side.synchronize()
+            got = d_out.cpu().numpy()
+            assert (got[n:] == 0xAB).all()  # nothing past the n answers
+            assert np.isin(got[:n], (0, 1)).all()
+            want = gpu.occluded_rays(R["o"][:n], R["d"][:n], tm[:n] if bounded else None, exact=exact)
+            assert np.array_equal(got[:n].astype(bool), want), (exact, bounded)
+
+
+# ---------------------------------------------------------------- O5: degenerate input
+@pytest.mark.parametrize("mode", ["BRUTE", "GROUPED", "BVH"])
+def test_o5_degenerate_rays_and_segments(rc, mode):
+    """NaN origin, infinite direction, zero direction, NaN direction, and t_max NaN, 0, -1, -0.0 and 1e-50:
+    0 in both query modes, and the rays around them are answered as if they were not there."""
+    R = _rays("bounce")
+    gpu = _gpu(rc, "bounce", mode)
+    o, d = R["o"][:70].copy(), R["d"][:70].copy()
+    tm = np.where(np.arange(70) % 2 == 0, INF, 2.0 * np.maximum(R["t"][:70], 1.0))
+    ref_fast, ref_exact = gpu.occluded_rays(o, d, tm), gpu.occluded_rays(o, d, tm, exact=True)
+    bad_rays = [3, 17, 64, 69]
+    bad_t = {5: np.nan, 20: 0.0, 33: -1.0, 40: -0.0, 66: 1e-50}
+    o[3, 1] = np.nan
+    d[17, 0] = np.inf
+    d[64] = 0.0
+    d[69, 2] = np.nan
+    for i, v in bad_t.items():
+        tm[i] = v
+    bad = bad_rays + list(bad_t)
+    keep = np.setdiff1d(np.arange(70), bad)
+    for exact, ref in ((False, ref_fast), (True, ref_exact)):
+        got = gpu.occluded_rays(o, d, tm, exact=exact)
+        _bytes_ok(got)
+        assert not got[bad].any()
+        assert np.array_equal(got[keep], ref[keep])
+        assert ref[bad_rays].any() and ref[list(bad_t)].any()  # some of them were occluded before
+        assert ref[keep].any() and not ref[keep].all()
+        # bad rays without t_max as well
+        assert not gpu.occluded_rays(o, d, None, exact=exact)[bad_rays].any()
+    gpu.close()
+
+
+# ---------------------------------------------------------------- O6: manners
+def _rc_of(lib, *args):
+    rc_ = lib.rt_occluded_rays(*args)
+    buf = C.create_string_buffer(512)
+    lib.rt_last_error(buf, 512)
+    return rc_, buf.value.decode()
+
+
+def test_o6_argument_and_state_errors(rc):
+    gpu = _gpu(rc, "mesh41", "BVH")
+    lib, h = gpu.lib, gpu.handle
+    rays, tm, out = np.zeros(4, rc.RAY_DTYPE), np.ones(4), np.full(4, 0xAB, np.uint8)
+    pr, pt, po = (a.ctypes.data_as(C.c_void_p) for a in (rays, tm, out))
+    assert _rc_of(lib, h, 0, None, pt, 4, po)[0] == -1
+    assert _rc_of(lib, h, 0, pr, pt, 4, None)[0] == -1
+    assert _rc_of(lib, h, 0, pr, pt, -1, po)[0] == -1
+    code, msg = _rc_of(lib, h, 2, pr, pt, 4, po)
+    assert code == -1 and "mode" in msg and "rt_occluded_rays" in msg
+    assert lib.rt_occluded_rays_device(h, 0, None, None, 4, None, None) == -1
+    assert lib.rt_occluded_rays_device(h, 0, pr, pt, 4, None, None) == -1
+    assert lib.rt_occluded_rays_device(h, -1, pr, pt, 4, po, None) == -1
+    assert (out == 0xAB).all()
+    gpu.close()
+    # FAST on a BVH2 scene: RT_ERR_STATE, the message names BVH; EXACT works there
+    gpu = _gpu(rc, "bounce", "BVH2")
+    code, msg = _rc_of(gpu.lib, gpu.handle, 0, pr, pt, 4, po)
+    assert code == -7 and "BVH" in msg and "rt_occluded_rays" in msg
+    assert gpu.lib.rt_occluded_rays_device(gpu.handle, 0, pr, pt, 4, po, None) == -7
+    assert (out == 0xAB).all()
+    R = _rays("bounce")
+    assert np.array_equal(gpu.occluded_rays(R["o"][:64], R["d"][:64], exact=True), R["ids"][:64] >= 0)
+    gpu.close()
+
+
+def test_o6_a_call_leaves_the_renderer_alone(rc):
+    """A render after occlusion calls equals the same render before them bit for bit; the counters of
+    rt_scene_get_stats and the rt_kernel_times ring are what they were."""
+    R = _rays("bounce")
+    gpu = _gpu(rc, "bounce", "BVH", size=(128, 128))
+    before = gpu.render_tile(40, 40, 24, 16, 8, seed=3)
+    gpu.render_tile(0, 0, 16, 16, 2, seed=4)
+    times = gpu.kernel_times(2)
+    gpu.set_stats(True)
+    gpu.render_tile(0, 0, 16, 16, 2, seed=4)
+    assert sum(gpu.get_stats().values()) > 0  # (read and zeroed)
+    launches = gpu.kernel_times(3)
+    for exact in (False, True):
+        for tm in (None, 1.0):
+            gpu.occluded_rays(R["o"], R["d"], tm, exact=exact)
+    assert gpu.kernel_times(3) == launches
+    assert sum(gpu.get_stats().values()) == 0
+    gpu.set_stats(False)
+    assert launches[:2] == times
+    after = gpu.render_tile(40, 40, 24, 16, 8, seed=3)
+    for a, b in zip(before[:3], after[:3]):
+        assert np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
+    assert before[3] == after[3]
+    gpu.close()
+
+
+# ---------------------------------------------------------------- O7: the tool
+def test_o7_bake_ao_equals_the_closest_hit_image(rc):
+    """tools/bake_ao.py's bake_ao on bounce in BRUTE at 48x36, K = 16, R = 1: value for value the image
+    computed from rt_query_rays distances < R on the same rays; neither all 0 nor all 1."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        import bake_ao
+    finally:
+        sys.path.pop(0)
+    gpu = _gpu(rc, "bounce", "BRUTE", size=(48, 36))
+    n_rays = []
+
+    def by_closest_hit(o, d, t_max):
+        n_rays.append(len(o))
+        h = gpu.query_rays(o, d)
+        return (h["prim_id"] >= 0) & (h["distance"] < t_max)
+
+    ao = bake_ao.bake_ao(gpu, 16, 1.0, seed=5)
+    ref = bake_ao.bake_ao(gpu, 16, 1.0, seed=5, occluded=by_closest_hit)
+    ids = gpu.query_rays(gpu.camera_rays())["prim_id"]  # [x, y]
+    gpu.close()
+    assert ao.shape == (36, 48) and ao.dtype == np.float32
+    assert np.array_equal(ao, ref)
+    assert n_rays == [16 * int((ids >= 0).sum())]
+    assert (ao[ids.T < 0] == 1).all() and (ids < 0).any()
+    assert ao.min() >= 0 and ao.max() == 1 and 0 < (ao < 1).sum() < ao.size
+    assert np.array_equal(ao * 16, np.rint(ao * 16))  # multiples of 1 / K

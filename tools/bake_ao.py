@@ -1,0 +1,118 @@
+"""Ambient occlusion of what camera 0 sees: for the primary hit of every integer pixel, the share of K
+cosine-distributed directions about the hit's normal along which nothing lies within a radius R.
+
+usage: python tools/bake_ao.py SCENE [--width W] [--rays K] [--radius R] [--seed S]
+                               [--traversal MODE] [--out PREFIX]
+
+SCENE is a scene file (or the name of one shipped in tests/golden/scenes).  The steps: camera_rays (the
+rays rt_primary_ids traces), query_rays (RT_QUERY_FAST) for the hits, K directions per hit from a
+generator seeded with S, then occluded_rays (rt_occluded_rays, RT_QUERY_FAST) with t_max = R from the hit
+position moved AO_EPSILON * max(1, |position|_inf) along the normal, off its own surface.  AO = 1 - occluded
+/ K; a primary miss, and a hit whose normal is NaN (Triangle.GetNormal's quirk inside a vertex-normal
+triangle), get AO 1.  The image keeps the scene's aspect ratio at width W.  Writes PREFIX.npy (AO as
+float32 [H, W]) and PREFIX.ppm (binary P6, grey).
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+AO_EPSILON = 1e-4  # origin offset along the normal, relative to max(1, |position|_inf): ~800 fp32 ulps
+
+
+def ao_directions(normals, k: int, seed: int) -> np.ndarray:
+    """k cosine-distributed unit directions about each of the (n, 3) unit normals, as (n, k, 3) fp64:
+    Malley's method (a uniform disc sample lifted to the hemisphere) in a frame built from the
+    coordinate axis the normal is least aligned with.  The same seed gives the same directions; the
+    height above the tangent plane is sqrt(1 - u) with u in [0, 1), so every direction has a
+    positive component along its normal."""
+    n = np.asarray(normals, np.float64).reshape(-1, 3)
+    rng = np.random.default_rng(seed)
+    u = rng.random((n.shape[0], k))
+    phi = 2.0 * np.pi * rng.random((n.shape[0], k))
+    e = np.eye(3)[np.argmin(np.abs(n), axis=1)]
+    a = np.cross(n, e)
+    a /= np.linalg.norm(a, axis=1, keepdims=True)
+    b = np.cross(n, a)
+    r, z = np.sqrt(u), np.sqrt(1.0 - u)
+    d = (r * np.cos(phi))[..., None] * a[:, None, :] + (r * np.sin(phi))[..., None] * b[:, None, :] + z[..., None] * n[:, None, :]
+    return d / np.linalg.norm(d, axis=-1, keepdims=True)
+
+
+def ao_rays(hits, k: int, seed: int):
+    """The occlusion rays of a HIT_DTYPE array (any shape): (mask, origins, directions) with mask the
+    hits that get rays (a hit with a finite normal), origins (m * k, 3) and directions (m * k, 3), the
+    k rays of a hit next to each other."""
+    h = np.asarray(hits).reshape(-1)
+    nrm = h["normal"].astype(np.float64)
+    mask = (h["prim_id"] >= 0) & np.isfinite(nrm).all(axis=1)
+    nrm = nrm[mask]
+    nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+    pos = h["position"][mask].astype(np.float64)
+    off = AO_EPSILON * np.maximum(1.0, np.max(np.abs(pos), axis=1, keepdims=True))
+    d = ao_directions(nrm, k, seed)
+    o = np.repeat(pos + off * nrm, k, axis=0)
+    return mask.reshape(np.shape(hits)), o, d.reshape(-1, 3)
+
+
+def bake_ao(gpu, k: int, radius: float, seed: int = 0, occluded=None) -> np.ndarray:
+    """The AO image of gpu's camera and frame size as float32 [H, W].  occluded(origins, directions,
+    t_max) -> bool array answers the occlusion rays; default gpu.occluded_rays (RT_QUERY_FAST)."""
+    if occluded is None:
+        occluded = gpu.occluded_rays
+    hits = gpu.query_rays(gpu.camera_rays())  # [x, y]
+    mask, o, d = ao_rays(hits, k, seed)
+    ao = np.ones(hits.shape, np.float32)
+    if len(o):
+        occ = np.asarray(occluded(o, d, np.full(len(o), float(radius))), bool).reshape(-1, k)
+        ao[mask] = (1.0 - occ.sum(axis=1) / float(k)).astype(np.float32)
+    return np.ascontiguousarray(ao.T)
+
+
+def write_ppm(path: str, ao: np.ndarray) -> None:
+    """AO [H, W] in [0, 1] as a grey binary PPM."""
+    g = np.clip(np.rint(ao * 255.0), 0, 255).astype(np.uint8)
+    with open(path, "wb") as f:
+        f.write(f"P6\n{ao.shape[1]} {ao.shape[0]}\n255\n".encode())
+        f.write(np.repeat(g[..., None], 3, axis=-1).tobytes())
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("scene")
+    ap.add_argument("--width", type=int, default=512)
+    ap.add_argument("--rays", type=int, default=16)
+    ap.add_argument("--radius", type=float, default=1.0)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--traversal", default="AUTO", choices=["AUTO", "BRUTE", "GROUPED", "BVH"])
+    ap.add_argument("--out", default="ao")
+    a = ap.parse_args(argv)
+    if a.width < 1 or a.rays < 1 or not a.radius > 0:
+        ap.error("--width and --rays must be >= 1, --radius > 0")
+
+    import raytracercore_amd as rc
+
+    path = a.scene if os.path.exists(a.scene) else rc.scene_path(a.scene)
+    scene = rc.SceneLoader.from_file(path)
+    height = max(1, round(a.width * scene.params.height / max(1, scene.params.width)))
+    gpu = rc.GpuRaytracer(scene, 0, size=(a.width, height), traversal=getattr(rc, "RT_TRAVERSAL_" + a.traversal))
+    try:
+        ao = bake_ao(gpu, a.rays, a.radius, a.seed)
+    finally:
+        gpu.close()
+    np.save(a.out + ".npy", ao)
+    write_ppm(a.out + ".ppm", ao)
+    print(f"{os.path.basename(path)} AO {a.width}x{height}: {a.rays} rays of radius {a.radius} per hit, "
+          f"mean {float(ao.mean()):.4f}, {int((ao < 1).sum())} pixels occluded -> {a.out}.npy, {a.out}.ppm")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
