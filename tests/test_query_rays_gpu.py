@@ -94,17 +94,22 @@ def _trace(orc, o, d):
     return ids, ts
 
 
-@functools.lru_cache(maxsize=None)
-def _rays(name):
-    """The scene's rays and the oracle's answers, computed once and shared (read-only)."""
-    cam = _scene(name).cameras[0]
+def _line_of_sight_rays(cam, n=N_RAYS):
+    """The generator: n unit directions from a normal distribution, origins along the camera's line of sight."""
     rng = np.random.default_rng(7)
-    n = N_RAYS
     d = rng.normal(size=(n, 3))
     d /= np.linalg.norm(d, axis=1, keepdims=True)
     pos = np.array([cam.position.x, cam.position.y, cam.position.z])
     look = np.array([cam.look_at.x, cam.look_at.y, cam.look_at.z])
     o = pos + rng.uniform(0, .75, (n, 1)) * (look - pos)
+    return o, d
+
+
+@functools.lru_cache(maxsize=None)
+def _rays(name):
+    """The scene's rays and the oracle's answers, computed once and shared (read-only)."""
+    n = N_RAYS
+    o, d = _line_of_sight_rays(_scene(name).cameras[0], n)
     orc = _oracle(name)
     ids, ts = _trace(orc, o, d)
     # a, b orthonormal to d: a from the coordinate axis d is least aligned with
