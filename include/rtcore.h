@@ -252,6 +252,14 @@ int rt_debug_brute_layout(const rt_prim* prims, int32_t n_prims, int32_t* out, i
    also deals the empty chunk slots (A/B). */
 int rt_debug_item_order(int32_t w, int32_t h, int32_t spp, int32_t chunks, int32_t pool, int32_t band,
                         int32_t band_stride, int32_t band_offset, uint32_t* out, int64_t cap_words, int32_t* info);
+/* Host only (no device needed): the scene bound of these primitives -- the padded fp32 box over every
+   primitive but the planes that the flat brute-force path kernel tests a wave of camera rays against, to
+   skip the query of a wave that looks past the scene (RTCORE_SCENE_BOUND=0 turns the skip off).
+   lo[3], hi[3]: the box; info (optional) gets {limit, pad}: origins with |x| + |y| + |z| above limit
+   are not tested (they count as meeting the box), pad is what was added on every side.  Returns 0,
+   1 when there is nothing to bound (an empty bound: no ray meets it), 2 when an extent is not finite
+   (no skip for the scene), or a negative rt_status. */
+int rt_debug_scene_bound(const rt_prim* prims, int32_t n_prims, float* lo, float* hi, float* info);
 /* Measurement of a wavefront split's traversal stage.  rt_debug_ray_log: while
    the next instrumented launch of a BVH kernel runs (rt_scene_set_stats; one launch only, then
    logging is off again), the kernel appends every finished query

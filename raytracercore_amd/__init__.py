@@ -255,6 +255,7 @@ def load_library(path: str = "") -> C.CDLL:
         "rt_ref_bvh_export": (C.c_int, [P(rt_prim), C.c_int32, P(C.c_int32), P(C.c_double), P(C.c_int32),
                                         P(C.c_int32)]),
         "rt_debug_item_order": (C.c_int, [C.c_int32] * 8 + [P(C.c_uint32), C.c_int64, P(C.c_int32)]),
+        "rt_debug_scene_bound": (C.c_int, [P(rt_prim), C.c_int32, P(C.c_float), P(C.c_float), P(C.c_float)]),
         "rt_debug_ray_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
         "rt_debug_vn_rehit": (C.c_int, [P(C.c_double), P(C.c_double), P(C.c_double), C.c_int32, C.c_double,
                                         C.c_double, P(C.c_float), P(C.c_int32), P(C.c_double), P(C.c_double)]),
@@ -383,6 +384,21 @@ def item_order(w: int, h: int, spp: int, chunks: int = 0, pool: int = 0,
     if n2 < 0:
         _check(n2)
     return out[:n], dict(zip(("n_chunks", "chunk", "pool", "n_split"), (int(v) for v in info)))
+
+
+def scene_bound(prims: Sequence[rt_prim]) -> dict:
+    """rt_debug_scene_bound (host code, no GPU): the padded fp32 box over every primitive but the planes
+    that the flat brute-force path kernel tests camera rays against -- lo, hi (float32[3]), limit (origins
+    with |x| + |y| + |z| above it are not tested), pad, and state: 0 a box, 1 empty, 2 no skip."""
+    lib = load_library()
+    n = len(prims)
+    arr = (rt_prim * max(1, n))(*prims)
+    lo, hi, info = (C.c_float * 3)(), (C.c_float * 3)(), (C.c_float * 2)()
+    state = lib.rt_debug_scene_bound(arr, n, lo, hi, info)
+    if state < 0:
+        _check(state)
+    return {"lo": np.array(lo, np.float32), "hi": np.array(hi, np.float32), "limit": np.float32(info[0]),
+            "pad": np.float32(info[1]), "state": int(state)}
 
 
 def ref_bvh_export(prims: Sequence[rt_prim]) -> Tuple[np.ndarray, np.ndarray, int, int]:

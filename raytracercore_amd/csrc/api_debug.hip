@@ -127,6 +127,7 @@ int rt_debug_jit_header(const rt_scene_params* params, const rt_prim* prims, int
     ps.ambient_r = (float)a.r;
     ps.ambient_g = (float)a.g;
     ps.ambient_b = (float)a.b;
+    set_scene_bound(ps, make_scene_bound(H));
     CameraD camd;
     CameraF camf;
     camera_init(*camera, params->width, params->height, camd, camf);
@@ -456,6 +457,30 @@ int rt_debug_item_order(int32_t w, int32_t h, int32_t spp, int32_t chunks, int32
         return RT_ERR_ARG;
     }
     return (int)n;
+}
+
+// Host only: the scene bound rt_scene_create would give the brute-force path kernels for these primitives.
+int rt_debug_scene_bound(const rt_prim* prims, int32_t n_prims, float* lo, float* hi, float* info)
+{
+    if (n_prims < 0 || (n_prims > 0 && !prims) || !lo || !hi) {
+        set_error("rt_debug_scene_bound: bad argument");
+        return RT_ERR_ARG;
+    }
+    for (int i = 0; i < n_prims; i++)
+        if (prims[i].kind < 0 || prims[i].kind > 2) {
+            set_error("rt_debug_scene_bound: unknown primitive kind at index " + std::to_string(i));
+            return RT_ERR_ARG;
+        }
+    const SceneBound b = make_scene_bound(prepare_prims(prims, n_prims));
+    for (int k = 0; k < 3; k++) {
+        lo[k] = b.lo[k];
+        hi[k] = b.hi[k];
+    }
+    if (info) {
+        info[0] = b.limit;
+        info[1] = b.pad;
+    }
+    return b.empty ? 1 : (b.limit < 0.0f ? 2 : 0);
 }
 
 int rt_parse_scene(const char* text, rt_scene_params* params, rt_prim* prims, int32_t* n_prims, rt_camera* cameras,

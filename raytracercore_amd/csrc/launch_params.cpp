@@ -144,6 +144,12 @@ PathParams make_params_for(int kernel, int chunks_over, int pool_over, int x0, i
     // Holding lanes back in the middle of a pool as well (until 4 .. 32 wait) lost 5-19 %.
     p.batch = kernel < 2 ? 64 : 0;
     if (const char* e = getenv("RTCORE_ITEM_BATCH")) p.batch = std::max(0, std::min(64, atoi(e)));
+    // Flat brute-force kernel: a wave whose live lanes all hold camera rays tests them against the scene
+    // bound (PathScene::bound_lo / _hi) and skips the query when none meets it (path_body).  The result
+    // is the same either way; RTCORE_SCENE_BOUND=0 turns the skip off (same-call A/B, identity tests).
+    // Kernel ms, one call, three rounds: C2 16.01-16.05 -> 14.97-15.00.
+    p.scene_bound = 1;
+    if (const char* e = getenv("RTCORE_SCENE_BOUND")) p.scene_bound = atoi(e) != 0 ? 1 : 0;
     // BVH kernels: the shading phase runs once 28 lanes wait; a leaf step once 12 lanes are blocked
     // on a pending leaf.  Round 5, C4 with the walls as outer records (profiles/r05/c4_outer_sweep.log):
     // refill 24 / 28 / 32 at spec 16: 44.0 / 43.6 / 43.6 ms; spec 12 / 16 / 20 at refill 24: 43.8 /

@@ -191,7 +191,30 @@ struct PathScene {
     int32_t ambient_miss;
     float air_ior;
     float ambient_r, ambient_g, ambient_b;
+    // The scene bound (SceneBound, scene_records.h): a padded box over every primitive but the planes,
+    // which the flat brute-force path kernel tests once per wave of camera rays (path_body).
+    float bound_lo[3];
+    float bound_limit;           // origins with |o.x| + |o.y| + |o.z| above it count as meeting the box; < 0: no skip
+    float bound_hi[3];
+    int32_t bound_empty;         // 1: nothing to bound (planes only, or no primitive): no ray meets it
 };
+
+// The scene bound as the host builds it (make_scene_bound, scene_records.cpp).
+struct SceneBound {
+    float lo[3], hi[3]; // padded, fp32, rounded outward
+    float limit;        // PathScene::bound_limit
+    float pad;          // what was added on every side (reported by rt_debug_scene_bound)
+    int32_t empty;
+};
+inline void set_scene_bound(PathScene& ps, const SceneBound& b)
+{
+    for (int k = 0; k < 3; k++) {
+        ps.bound_lo[k] = b.lo[k];
+        ps.bound_hi[k] = b.hi[k];
+    }
+    ps.bound_limit = b.limit;
+    ps.bound_empty = b.empty;
+}
 
 // Child reference in a NodeF: >= 0 internal node index, < 0 leaf = ~code, where code is
 //   generic leaf: first << 3 | (count - 1)            (first < 2^27; 64-B TestRecs, kind and flags per record)
@@ -364,6 +387,7 @@ struct DevScene {
     float air_ior;
     float3 ambient;
     int32_t ambient_miss;
+    SceneBound bound;           // over the primitives of the brute-force orders (not the planes)
 };
 
 } // namespace rtc

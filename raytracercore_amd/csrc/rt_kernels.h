@@ -94,8 +94,10 @@ struct PathParams {
     const double2* ray_list;    // four 16-B rows per ray (origin xy, origin zw, direction xy, direction zw)
     unsigned int n_rays;        // rays of the launch (the items of the last block past it stay closed)
     unsigned long long stream_base;
+    int scene_bound;            // flat brute-force kernel: 1 = a wave of camera rays that all miss the scene bound
+                                // skips its query (RTCORE_SCENE_BOUND, make_params_for)
 };
-constexpr int kRecRows = 6;     // sizeof(rt_debug_ray) / 16
+constexpr int kRecRows = 6;    // sizeof(rt_debug_ray) / 16
 
 // Ticket t of item range g -> the items it covers, [first, first + len) in the item numbering
 // ((block << log2_chunks) + chunk) * 64 + pixel: chunks of one 8x8 block next to each other, none

@@ -931,6 +931,90 @@ uint32_t scene_facts(const std::vector<HostPrim>& H)
     return facts;
 }
 
+// The scene bound: one world-space box over every primitive of the brute-force orders but the planes,
+// which path_body tests once per wave of camera rays (scene_meets, kernels_path.hip) to skip the whole
+// query of a wave that looks past the scene.  Triangles and parallelograms (frame rectangles and
+// boxes among them: the loader bakes their vertices into world space) from their vertices, a sphere
+// from centre +- r, a transformed sphere from the exact box of its ellipsoid: the world point of the
+// object-space point q is MatrixToObject * q, so on world axis k the ellipsoid spans
+// (MatrixToObject * centre)_k +- r |row k of its 3x3 part|.  All in fp64, rounded outward to fp32.
+//
+// The pad.  The kernel's predicate is the fp32 slab test t = fma(plane, id, -(o * id)) with id =
+// slab_rcp_lean(d): id is 1 / d within one ulp (2^-23 relative, a scale of that axis's distances), the
+// product o * id and the fma round once each (2^-24 relative).  Set against the exact distance of the
+// plane along the ray, and brought back to position space (times |d|), a slab end is off by at most
+//   2^-23 |plane - o| + 2^-24 (|o| + |plane - o|) <= 2^-22 (2 |o| + M),  M = the largest |coordinate| of the box,
+// so it grows with the origin's distance from zero, not only with the box's extent.  The primitive
+// tests are fp32 too and accept points as far outside their primitive as a few 2^-24 |o| (the
+// triangle's (u, v), the sphere's perpendicular l = oc - (oc . d) d).  The predicate serves origins
+// with |o.x| + |o.y| + |o.z| <= limit = 1024 M, and the box is padded on every side by
+//   pad = 2^-18 (limit + M):
+// 8 times the slab's own bound at the limit (2^-21 (limit + M)), the rest for the primitive tests'
+// error.  For bounce.txt (M = 2) that is 0.0078 on a 4 x 4 x 2 room.  An origin past the limit
+// counts as meeting the box, as does a ray with a NaN or an infinity in it.
+// No bounded primitive: an empty bound, which no ray meets.  A NaN or infinite extent: limit = -1,
+// so every origin is past it and the skip is off for the scene.
+SceneBound make_scene_bound(const std::vector<HostPrim>& H)
+{
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    bool any = false, bad = false;
+    auto grow = [&](int k, double a, double b) {
+        if (!(std::isfinite(a) && std::isfinite(b))) bad = true;
+        lo[k] = std::min(lo[k], a);
+        hi[k] = std::max(hi[k], b);
+    };
+    for (const HostPrim& p : H) {
+        if (p.kind == RT_PRIM_TRIANGLE) {
+            const Vec4d v3 = add(add(p.v[0], p.e01), p.e02); // a parallelogram's fourth vertex
+            const int nv = (p.flags & F_MIRROR) ? 4 : 3;
+            for (int j = 0; j < nv; j++) {
+                const Vec4d& v = j < 3 ? p.v[j] : v3;
+                const double c[3] = {v.x, v.y, v.z};
+                for (int k = 0; k < 3; k++) grow(k, c[k], c[k]);
+            }
+        } else if (p.kind == RT_PRIM_SPHERE) {
+            const double c[3] = {p.center.x, p.center.y, p.center.z};
+            for (int k = 0; k < 3; k++) {
+                double mid = c[k], half = std::fabs(p.radius);
+                if (p.flags & F_TRANSFORMED) {
+                    const double* m = p.to_obj + 4 * k;
+                    mid = m[0] * c[0] + m[1] * c[1] + m[2] * c[2] + m[3];
+                    half = std::fabs(p.radius) * std::sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]);
+                }
+                // (the fp64 rounding of mid and half is 2^-52 relative: far inside the pad)
+                grow(k, mid - half, mid + half);
+            }
+        } else {
+            continue;
+        }
+        any = true;
+    }
+    SceneBound b{};
+    if (!any) {
+        b.empty = 1;
+        b.limit = INFINITY;
+        return b;
+    }
+    double M = 0.0;
+    for (int k = 0; k < 3; k++) M = std::max(M, std::max(std::fabs(lo[k]), std::fabs(hi[k])));
+    const double limit = 1024.0 * M, pad = std::ldexp(limit + M, -18);
+    if (bad || !std::isfinite(M) || !((float)(limit + M + pad) < INFINITY)) {
+        b.limit = -1.0f; // the skip is off
+        return b;
+    }
+    for (int k = 0; k < 3; k++) {
+        const double a = lo[k] - pad, c = hi[k] + pad;
+        b.lo[k] = (float)a;
+        if ((double)b.lo[k] > a) b.lo[k] = std::nextafterf(b.lo[k], -INFINITY);
+        b.hi[k] = (float)c;
+        if ((double)b.hi[k] < c) b.hi[k] = std::nextafterf(b.hi[k], INFINITY);
+    }
+    b.limit = (float)limit;
+    if ((double)b.limit > limit) b.limit = std::nextafterf(b.limit, 0.0f); // never above what the pad covers
+    b.pad = (float)pad;
+    return b;
+}
+
 // Which axis-aligned rectangles become outer records.  Only large ones pay: a wall whose box
 // overlaps the whole scene sits near the root of any tree, while a small cube face is cheap inside
 // it and would cost every query a test outside it (test_outer is linear in the group).  So a

@@ -84,6 +84,8 @@ MatTable make_materials(const std::vector<HostPrim>& H, double air_ior);
 std::vector<GroupRec> groups_nearest_first(const std::vector<GroupRec>& g, const CameraD& cam);
 XformF make_xformf(const HostPrim& p);
 uint32_t scene_facts(const std::vector<HostPrim>& H); // FACT_*
+// The padded box over every primitive but the planes, and the origin limit its pad covers.
+SceneBound make_scene_bound(const std::vector<HostPrim>& H);
 // Which axis-aligned rectangles become outer records (out: per primitive, or empty for none).
 void select_outer(const std::vector<HostPrim>& H, std::vector<char>& out);
 

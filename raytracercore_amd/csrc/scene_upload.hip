@@ -372,6 +372,7 @@ int upload_scene(rt_scene* s)
     const rt_color& a = s->params.ambient;
     d.ambient = make_float3((float)a.r, (float)a.g, (float)a.b);
     d.ambient_miss = (a.r == -1 && a.g == -1 && a.b == -1) ? 1 : 0; // AmbientRGB == Placeholder
+    d.bound = make_scene_bound(H);
     return RT_OK;
 }
 

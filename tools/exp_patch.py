@@ -19,8 +19,9 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "raytracercore_amd", "csrc")
 
-TRACE_CALL = ("            trace_brute<CULL, STATS>(sc, groups, tests, rects, frames, boxes, xf, S.o, S.d, S.prev, b, cnt.tris,\n"
-              "                                     cnt.sphs, cnt.nodes);\n")
+TRACE_CALL = ("            if (query)\n"
+              "                trace_brute<CULL, STATS>(sc, groups, tests, rects, frames, boxes, xf, S.o, S.d, S.prev, b, cnt.tris,\n"
+              "                                         cnt.sphs, cnt.nodes);\n")
 BOUNCE_CALL = "            bounce<VN, false, false, STATS>(L, S, sc, R, vnormals, tests, pq->prims_d, b, *pq);\n"
 RAYS_LINE = "        wave_rays += (unsigned)__popcll(__ballot(L.live)); // one Scene.RayTrace per live lane\n"
 
