@@ -189,6 +189,17 @@ __device__ __forceinline__ void hit_plane(const TestRec& R, int slot, V3 o, V3 d
     b.sg = ok ? pack_sg(slot, gin) : b.sg;
 }
 
+// The planes of a scene: the records that follow the other primitives (n_bvh of them) in every slot order.
+template <class SceneT, class TestP>
+__device__ __forceinline__ void test_planes(const SceneT& s, TestP tests, V3 o, V3 d, int prev, Best& b)
+{
+    const int pln0 = s.n_bvh;
+    for (int k = pln0; k < pln0 + s.n_pln; k++) {
+        const TestRec tr = tests[k];
+        hit_plane<true>(tr, k, o, d, prev, b);
+    }
+}
+
 // Axis-aligned rectangle on plane `AXIS` (RectRec): the same hit as the Mirror parallelogram
 // test (u, v in [0, 1]^2) with the extents in world units.  id = 1 / d, oi = o / d.  The side
 // of the hit (Inside) is not tracked here: the shading step recomputes it from the normal.
@@ -604,6 +615,83 @@ __device__ __forceinline__ void wide_visit(const Node4Q& q, V3 id, V3 oi, float 
         if (d2 < inf) push<STACK>(stk, sp, r2);
         if (d1 < inf) push<STACK>(stk, sp, r1);
         ref = r0;
+        pop = false;
+    }
+}
+
+// One visit of a 4-wide node for an any-hit query: wide_visit's four slab tests against the segment's
+// end, without the sorting network (no child is nearer in any sense that matters).  The first hit
+// child in slot order is entered and the other hit children are pushed, to be popped in slot order.
+template <int STACK>
+__device__ __forceinline__ void any_visit(const Node4Q& q, V3 id, V3 oi, float best, int& ref, int& sp,
+                                          const TravStack& stk, bool& pop)
+{
+    const uint32_t ex = __float_as_uint(q.a.w);
+    const float ax = __builtin_amdgcn_ldexpf(id.x, (int)(ex & 255u) - 128);
+    const float ay = __builtin_amdgcn_ldexpf(id.y, (int)((ex >> 8) & 255u) - 128);
+    const float az = __builtin_amdgcn_ldexpf(id.z, (int)((ex >> 16) & 255u) - 128);
+    const float bx = fmaf(q.a.x, id.x, -oi.x), by = fmaf(q.a.y, id.y, -oi.y), bz = fmaf(q.a.z, id.z, -oi.z);
+    const uint32_t lx = __float_as_uint(q.b.x), hx = __float_as_uint(q.b.y);
+    const uint32_t ly = __float_as_uint(q.b.z), hy = __float_as_uint(q.b.w);
+    const uint32_t lz = __float_as_uint(q.c.x), hz = __float_as_uint(q.c.y);
+    const bool px = id.x >= 0.0f, py = id.y >= 0.0f, pz = id.z >= 0.0f; // near / far planes by the direction's sign
+    const uint32_t nx = px ? lx : hx, fx = px ? hx : lx;
+    const uint32_t ny = py ? ly : hy, fy = py ? hy : ly;
+    const uint32_t nz = pz ? lz : hz, fz = pz ? hz : lz;
+    const int nc = __float_as_int(q.d.z);
+    const int r0 = __float_as_int(q.c.z), r1 = __float_as_int(q.c.w), r2 = __float_as_int(q.d.x), r3 = __float_as_int(q.d.y);
+    const float tmax_best = best * 1.00000024f;
+    bool h0, h1, h2, h3;
+#define RT_ANY_CHILD(K, H)                                                                                        \
+    {                                                                                                             \
+        const float tmin = fmaxf(fmaxf(fmaxf(fmaf(ubyte(nx, K), ax, bx), fmaf(ubyte(ny, K), ay, by)),              \
+                                       fmaf(ubyte(nz, K), az, bz)), 0.0f);                                         \
+        const float tmax = fminf(fminf(fmaf(ubyte(fx, K), ax, bx), fmaf(ubyte(fy, K), ay, by)),                   \
+                                 fmaf(ubyte(fz, K), az, bz));                                                      \
+        H = (K < nc) & (tmin <= fminf(tmax * 1.00000024f, tmax_best));                                            \
+    } // the same test as RT_WIDE_CHILD (wide_visit)
+    RT_ANY_CHILD(0, h0)
+    RT_ANY_CHILD(1, h1)
+    RT_ANY_CHILD(2, h2)
+    RT_ANY_CHILD(3, h3)
+#undef RT_ANY_CHILD
+    if (h0 | h1 | h2 | h3) {
+        if (h3 & (h0 | h1 | h2)) push<STACK>(stk, sp, r3);
+        if (h2 & (h0 | h1)) push<STACK>(stk, sp, r2);
+        if (h1 & h0) push<STACK>(stk, sp, r1);
+        ref = h0 ? r0 : h1 ? r1 : h2 ? r2 : r3;
+        pop = false;
+    }
+}
+
+// A hot node read from LDS, its rows through a pointer typed by the address space (as TravStack's):
+// as a copy from a plain pointer the compiler merged this read with the read from global memory on
+// the other side of the choice (walk_step's fetch) into flat loads through a selected pointer.
+typedef float F4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) F4 LdsF4;
+__device__ __forceinline__ Node4Q lds_node(const LdsF4* rows, int i)
+{
+    const F4 a = rows[4 * i], b = rows[4 * i + 1], c = rows[4 * i + 2], d = rows[4 * i + 3];
+    return Node4Q{make_float4(a.x, a.y, a.z, a.w), make_float4(b.x, b.y, b.z, b.w), make_float4(c.x, c.y, c.z, c.w),
+                  make_float4(d.x, d.y, d.z, d.w)};
+}
+
+// One visit of a BVH2 node, to wide_visit's contract: the nearer hit child next, the other pushed.
+template <int STACK>
+__device__ __forceinline__ void bvh2_visit(const NodeF& n, V3 id, V3 oi, float best, int& ref, int& sp,
+                                           const TravStack& stk, bool& pop)
+{
+    float tl, tr;
+    const bool hl = slab(n.lmin, n.lmax, oi, id, best, tl);
+    const bool hr = slab(n.rmin, n.rmax, oi, id, best, tr);
+    const int cl = __float_as_int(n.lmin.w), cr = __float_as_int(n.rmin.w);
+    if (hl && hr) {
+        const bool lf = tl <= tr;
+        push<STACK>(stk, sp, lf ? cr : cl);
+        ref = lf ? cl : cr;
+        pop = false;
+    } else if (hl | hr) {
+        ref = hl ? cl : cr;
         pop = false;
     }
 }
@@ -1046,11 +1134,8 @@ __device__ __forceinline__ int shade(const SceneT& s, const PrimF* __restrict__ 
 #ifndef RT_WIDE_STACK
 #define RT_WIDE_STACK 16 // LDS entries of the wide BVH kernel's traversal stack (then global overflow): 7 blocks per CU
 #endif
-#ifndef RT_BVH_SPEC
-#define RT_BVH_SPEC 1 // speculative BVH traversal with wave-wide leaf steps (p.spec); 0: the mixed-step loop (C4 69.8 -> 62.1 ms)
-#endif
 #ifndef RT_SPEC_PRIMS
-#define RT_SPEC_PRIMS 2 // leaf primitives per leaf step, both traversal loops (<= kTestSpares + 1)
+#define RT_SPEC_PRIMS 2 // leaf primitives per leaf step (<= kTestSpares + 1)
 #endif
 #ifndef RT_BVH_WAVES
 #define RT_BVH_WAVES 7 // the same for the BVH kernels (C4: 4 waves with a 40-entry LDS stack 80.7 ms, 5 waves with 24 entries
@@ -1562,11 +1647,7 @@ __device__ __forceinline__ void path_body(const CameraF* __restrict__ camp, cons
             if (query)
                 trace_brute<CULL, STATS>(sc, groups, tests, rects, frames, boxes, xf, S.o, S.d, S.prev, b, cnt.tris,
                                          cnt.sphs, cnt.nodes);
-            const int pln0 = sc.n_bvh;
-            for (int i = pln0; i < pln0 + sc.n_pln; i++) {
-                const TestRec tr = tests[i];
-                hit_plane<true>(tr, i, S.o, S.d, S.prev, b);
-            }
+            test_planes(sc, tests, S.o, S.d, S.prev, b);
             // A NaN direction (a diffuse bounce about GetNormal's NaN normal, only in scenes with
             // vertex-normal triangles) fails the reference's BVH root test (BVH.cs:301-303: far >= 0
             // is false for NaN) and meets nothing.  The brute-force records would not all say so: a
@@ -1670,13 +1751,95 @@ __device__ __forceinline__ void test_leaf(TestP tests, RowP rows, XfP xf, int pe
     }
 }
 
-// BVH megakernel with decoupled traversal.  A loop iteration advances the traversing lanes by
-// one step: with RT_BVH_SPEC a wave-wide node step or leaf step (up to two primitives), lanes
-// keeping a reached leaf pending while they visit further nodes; without it, one node visit or
-// one leaf step per lane.  Lanes whose query finished wait, and the shading / new-sample phase
-// runs only once at least p.refill lanes wait (or none is still traversing).  So one long
-// traversal no longer holds the other 63 lanes of its wave, and the divergent shading code is
-// paid once per batch of finished queries.
+// Speculative traversal (Aila & Laine 2009), the walk of every BVH kernel.  A lane that reaches a
+// leaf keeps it pending and goes on visiting nodes.  Leaf primitives are tested in wave-wide leaf
+// steps, taken once `spec` lanes are blocked (a second leaf reached, or no node left) or no lane can
+// visit a node, so a step is one kind of work for the whole wave instead of both.  Node culling uses
+// the best hit so far (the pending leaf not yet tested): more visits, the same closest hit.  (A lane
+// with a pending leaf always runs ahead; having it wait for the leaf step measured C4 44.5 -> 48.95 ms.)
+struct Walk {
+    bool more; // ref still holds a reference to process (the stack is not exhausted)
+    int ref;   // a node index, or ~leaf code
+    int sp;
+    int pend;  // the pending leaf (leaf_decode), -1 for none
+};
+// tree: the scene has nodes or a root leaf (without either only the planes remain, and the query
+// ends at its first step)
+__device__ __forceinline__ void walk_start(Walk& w, int root, bool tree)
+{
+    w.ref = root;
+    w.sp = 0;
+    w.pend = -1;
+    w.more = tree;
+    if (root < 0) { // the root itself is a leaf
+        w.pend = ~root;
+        w.more = false;
+    }
+}
+struct WalkStep { // (can_node and sp_visit exist only for path_kernel_bvh's STATS counters)
+    bool ended;               // this lane's query ended in this step
+    bool leaf_step, can_node; // the step's kind (wave-uniform); the lane had a node to visit (for the callers' counters)
+    int sp_visit;             // the stack pointer after the lane's visit, before the pop
+};
+// One step of the whole wave; trav: the lane has a query under way.  fetch(ref) loads the node: a
+// Node4Q (WIDTH 4), or a NodeF (WIDTH 2).  ANY: the query wants any hit, and ends with the first one.
+template <int STACK, bool ANY, bool STATS = false, int WIDTH = 4, class FetchT, class TestP, class RowP, class XfP>
+__device__ __forceinline__ WalkStep walk_step(Walk& w, bool trav, int spec, FetchT fetch, V3 id, V3 oi, const TravStack& stk,
+                                              TestP tests, RowP rows, XfP xf, V3 o, V3 d, int prev, Best& b,
+                                              unsigned& n_tri, unsigned& n_sph)
+{
+    WalkStep st;
+    st.can_node = trav && w.more && w.ref >= 0;
+    const bool blocked = trav && w.pend >= 0 && !st.can_node;
+    st.leaf_step = __ballot(st.can_node) == 0 || __popcll(__ballot(blocked)) >= spec; // wave-uniform
+    st.ended = false;
+    st.sp_visit = w.sp;
+    if (trav) {
+        if (st.leaf_step) {
+            if (w.pend >= 0) { // RT_SPEC_PRIMS primitives of the pending leaf, their loads issued together
+                test_leaf<STATS>(tests, rows, xf, w.pend, o, d, prev, b, n_tri, n_sph);
+                w.pend = leaf_advance(w.pend, RT_SPEC_PRIMS);
+                if (ANY && b.sg >= 0) { // the answer: the rest of the leaf and of the tree is not looked at
+                    w.pend = -1;
+                    w.more = false;
+                }
+            }
+        } else if (st.can_node) {
+            bool pop = true;
+            const auto node = fetch(w.ref);
+            if constexpr (WIDTH == 2) bvh2_visit<STACK>(node, id, oi, b.t, w.ref, w.sp, stk, pop);
+            else if constexpr (ANY) any_visit<STACK>(node, id, oi, b.t, w.ref, w.sp, stk, pop);
+            else wide_visit<STACK>(node, id, oi, b.t, w.ref, w.sp, stk, pop);
+            st.sp_visit = w.sp;
+            if (pop) {
+                if (w.sp > 0) w.ref = pop_ref<STACK>(stk, w.sp);
+                else w.more = false;
+            }
+        }
+        // a leaf reference becomes the pending leaf once the previous one is tested, and the
+        // next reference is popped so that traversal goes on past it
+        if (w.more && w.ref < 0 && w.pend < 0) {
+            w.pend = ~w.ref;
+            if (w.sp > 0) w.ref = pop_ref<STACK>(stk, w.sp);
+            else w.more = false;
+        }
+        // The popped reference is complete here, before the caller's stores at the end of a query.  Left
+        // in flight, a register copy of it at the loop's end made the wave wait for those stores as well
+        // (s_waitcnt vmcnt(0) after the hit record: rt_query_rays + 3 % at 7.6 M rays).  Seen with AMD clang
+        // 22.0.0git (ROCm 7.2.0).  To re-check with another compiler: in query_bvh_kernel's ISA, no
+        // s_waitcnt vmcnt(0) between the last global_store_dwordx4 and the loop's branch.
+        asm volatile("" : "+v"(w.ref));
+        st.ended = !w.more && w.pend < 0;
+    }
+    return st;
+}
+
+// BVH megakernel with decoupled traversal.  A loop iteration advances the traversing lanes by one
+// step of the speculative walk (walk_step): a wave-wide node step or leaf step (up to two primitives).
+// Lanes whose query finished wait, and the shading / new-sample phase runs only once at least
+// p.refill lanes wait (or none is still traversing).  So one long traversal no longer holds the
+// other 63 lanes of its wave, and the divergent shading code is paid once per batch of finished
+// queries.
 template <int WIDTH, int STACK, bool LDS, bool STATS, bool VN, bool RAYS = false>
 __global__ void __launch_bounds__(256, WIDTH == 4 ? RT_BVH_WAVES : RT_BVH2_WAVES)
     path_kernel_bvh(PathScene, const CameraF* __restrict__ camp, const PathParams* __restrict__ pp, const TestRec*,
@@ -1693,6 +1856,7 @@ __global__ void __launch_bounds__(256, WIDTH == 4 ? RT_BVH_WAVES : RT_BVH2_WAVES
     const ShadeRecs R = stage_scene<LDS>(P0.scene, P0.prims, P0.mats, P0.xf, lds_scene);
     // hot wide nodes after the staged shading records (dynamic LDS; see path_lds_bytes)
     Node4Q* lds_hot = reinterpret_cast<Node4Q*>(lds_scene + (LDS ? scene_lds_float4s(P0.scene) : 0));
+    const LdsF4* hot_rows = (const LdsF4*)lds_hot;
     if (WIDTH == 4 && P0.scene.n_hot4 > 0) {
         const float4* src = reinterpret_cast<const float4*>(P0.scene.hot4);
         float4* dst = reinterpret_cast<float4*>(lds_hot);
@@ -1710,9 +1874,7 @@ __global__ void __launch_bounds__(256, WIDTH == 4 ? RT_BVH_WAVES : RT_BVH2_WAVES
     unsigned long long wave_rays = 0; // wave-uniform
     // traversal state of the lane's current query
     bool trav = false, done = false;
-    [[maybe_unused]] bool more = false; // RT_BVH_SPEC: ref still holds a reference to process (stack not exhausted)
-    int ref = 0, sp = 0;
-    int pend = -1; // the pending leaf (leaf_decode), -1 for none
+    Walk w{false, 0, 0, -1};
     // 1/d of the query; o/d is recomputed per node visit (three multiplies) instead of being held
     // across the loop (VGPR spills of the C4 kernel 13 -> 2 at 6 waves per SIMD; recomputing 1/d as
     // well, three clamped reciprocals per visit, measured slower: 45.9 -> 46.2 ms)
@@ -1748,6 +1910,8 @@ __global__ void __launch_bounds__(256, WIDTH == 4 ? RT_BVH_WAVES : RT_BVH2_WAVES
                 if (s.n_groups > 0 && !(VN && __builtin_isnan(S.d.x + S.d.y + S.d.z)))
                     test_outer<STATS>((const RT_AS_CONST GroupRec*)pq->groups, (const RT_AS_CONST RectRec*)pq->rects,
                                       (const RT_AS_CONST BoxRec*)pq->frames, S.o, S.d, S.prev, b, cnt.outer);
+                // (test_planes' loop, written out: as a call, the render-rays instance without LDS staging
+                // keeps one more register in scratch, 8 -> 12 B)
                 for (int i = s.n_bvh; i < s.n_bvh + s.n_pln; i++) {
                     const TestRec tr = tests[i];
                     hit_plane<true>(tr, i, S.o, S.d, S.prev, b);
@@ -1768,14 +1932,7 @@ __global__ void __launch_bounds__(256, WIDTH == 4 ? RT_BVH_WAVES : RT_BVH2_WAVES
             }
             refill<true, RAYS>(L, S, p, s, *cp, lane, total);
             if (L.live && !trav) { // start the next query
-                ref = s.root;
-                sp = 0;
-                pend = -1;
-                more = true;
-                if (ref < 0) { // the root itself is a leaf
-                    pend = ~ref;
-                    more = false;
-                }
+                walk_start(w, s.root, true); // (PathScene carries no node count; root is taken as it is)
                 b = query_start<VN>(s, S.prev);
                 trav = true;
             }
@@ -1783,119 +1940,36 @@ __global__ void __launch_bounds__(256, WIDTH == 4 ? RT_BVH_WAVES : RT_BVH2_WAVES
             // are free inside it (the traversing lanes recompute the same values)
             id = v3(slab_rcp(S.d.x), slab_rcp(S.d.y), slab_rcp(S.d.z));
         }
-#if RT_BVH_SPEC
-        // Speculative traversal (Aila & Laine 2009): a lane that reaches a leaf keeps it pending and
-        // goes on visiting nodes.  Leaf primitives are tested in wave-wide leaf steps, taken once
-        // p.spec lanes are blocked (a second leaf reached, or no node left) or no lane can visit a
-        // node, so an iteration is one kind of step instead of both.  Node culling uses the best hit
-        // so far (the pending leaf not yet tested): more visits, the same closest hit.
-#ifndef RT_SPEC_RUNAHEAD
-#define RT_SPEC_RUNAHEAD 1 // 0: a lane with a pending leaf waits for the leaf step instead of visiting on
-#endif
-        const bool can_node = trav && more && ref >= 0 && (RT_SPEC_RUNAHEAD || pend < 0);
-        const bool blocked = trav && pend >= 0 && !can_node;
-        const bool leaf_step = __ballot(can_node) == 0 || __popcll(__ballot(blocked)) >= p.spec; // wave-uniform
+        // One step of the walk.  The top of the wide tree comes from LDS, the rest from global memory,
+        // and o / d is formed here, per visit (see id above).
+        const auto fetch = [&](int ref) {
+            if constexpr (WIDTH == 4) return (ref & RT_HOT_BIT) ? lds_node(hot_rows, ref & ~RT_HOT_BIT) : Node4Q(nodes4[ref]);
+            else return NodeF(nodes[ref]);
+        };
+        [[maybe_unused]] const bool was_trav = trav, had_leaf = trav && w.pend >= 0;
+        [[maybe_unused]] const int sp0 = w.sp;
+        const WalkStep st = walk_step<STACK, false, STATS, WIDTH>(w, trav, p.spec, fetch, id, S.o * id, stk, tests, rows, xf,
+                                                                  S.o, S.d, S.prev, b, cnt.tris, cnt.sphs);
         if (STATS) { // lane slots of this iteration (the BVH kernels reuse the brute-force cycle counters):
                      // testing a leaf | traversing but idle in this step's kind | waiting for the shading phase
-            const unsigned n_trav = (unsigned)__popcll(__ballot(trav));
-            const unsigned n_node = leaf_step ? 0u : (unsigned)__popcll(__ballot(can_node));
-            const unsigned n_leaf = leaf_step ? (unsigned)__popcll(__ballot(trav && pend >= 0)) : 0u;
+            const unsigned n_trav = (unsigned)__popcll(__ballot(was_trav));
+            const unsigned n_node = st.leaf_step ? 0u : (unsigned)__popcll(__ballot(st.can_node));
+            const unsigned n_leaf = st.leaf_step ? (unsigned)__popcll(__ballot(had_leaf)) : 0u;
             cnt.cyc_start += n_leaf;
             cnt.cyc_trace += n_trav - n_node - n_leaf;
-            cnt.cyc_shade += (unsigned)__popcll(__ballot(!trav && (L.active || L.live)));
-        }
-        if (trav) {
-            if (leaf_step) {
-                if (pend >= 0) { // RT_SPEC_PRIMS primitives of the pending leaf, their loads issued together
-                    test_leaf<STATS>(tests, rows, xf, pend, S.o, S.d, S.prev, b, cnt.tris, cnt.sphs);
-                    pend = leaf_advance(pend, RT_SPEC_PRIMS);
-                }
-            } else if (can_node) {
-                bool pop = true;
-                const V3 oi = S.o * id;
+            cnt.cyc_shade += (unsigned)__popcll(__ballot(!was_trav && (L.active || L.live)));
+            if (st.can_node && !st.leaf_step) {
+                cnt.nodes++;
                 if (WIDTH == 4) {
-                    const Node4Q q = (ref & RT_HOT_BIT) ? lds_hot[ref & ~RT_HOT_BIT] : Node4Q(nodes4[ref]);
-                    [[maybe_unused]] const int sp0 = sp;
-                    wide_visit<STACK>(q, id, oi, b.t, ref, sp, stk, pop);
-                    if (STATS) {
-                        cnt.ovf_pushes += (unsigned)max(0, sp - max(sp0, STACK));
-                        cnt.max_sp = max(cnt.max_sp, (unsigned)sp);
-                    }
-                } else {
-                    const NodeF n = nodes[ref];
-                    float tl, tr;
-                    const bool hl = slab(n.lmin, n.lmax, oi, id, b.t, tl);
-                    const bool hr = slab(n.rmin, n.rmax, oi, id, b.t, tr);
-                    const int cl = __float_as_int(n.lmin.w), cr = __float_as_int(n.rmin.w);
-                    if (hl && hr) {
-                        const bool lf = tl <= tr;
-                        push<STACK>(stk, sp, lf ? cr : cl);
-                        ref = lf ? cl : cr;
-                        pop = false;
-                    } else if (hl | hr) {
-                        ref = hl ? cl : cr;
-                        pop = false;
-                    }
+                    cnt.ovf_pushes += (unsigned)max(0, st.sp_visit - max(sp0, STACK));
+                    cnt.max_sp = max(cnt.max_sp, (unsigned)st.sp_visit);
                 }
-                if (STATS) cnt.nodes++;
-                if (pop) {
-                    if (sp > 0) ref = pop_ref<STACK>(stk, sp);
-                    else more = false;
-                }
-            }
-            // a leaf reference becomes the pending leaf once the previous one is tested, and the
-            // next reference is popped so that traversal goes on past it
-            if (more && ref < 0 && pend < 0) {
-                pend = ~ref;
-                if (sp > 0) ref = pop_ref<STACK>(stk, sp);
-                else more = false;
-            }
-            if (!more && pend < 0) {
-                trav = false;
-                done = true;
             }
         }
-#else
-        if (trav) { // one traversal step: one node visit, or one primitive of the current leaf
-            bool pop = true; // child references are node indices or ~leaf codes (any int)
-            if (pend >= 0) { // RT_SPEC_PRIMS primitives, their loads issued together
-                test_leaf<STATS>(tests, rows, xf, pend, S.o, S.d, S.prev, b, cnt.tris, cnt.sphs);
-                pend = leaf_advance(pend, RT_SPEC_PRIMS);
-                pop = pend < 0;
-            } else if (WIDTH == 4) {
-                // the top of the tree comes from LDS, the rest from global memory
-                const Node4Q q = (ref & RT_HOT_BIT) ? lds_hot[ref & ~RT_HOT_BIT] : Node4Q(nodes4[ref]);
-                wide_visit<STACK>(q, id, S.o * id, b.t, ref, sp, stk, pop);
-                if (STATS) cnt.nodes++;
-            } else {
-                const NodeF n = nodes[ref];
-                if (STATS) cnt.nodes++;
-                float tl, tr;
-                const V3 oi = S.o * id;
-                const bool hl = slab(n.lmin, n.lmax, oi, id, b.t, tl);
-                const bool hr = slab(n.rmin, n.rmax, oi, id, b.t, tr);
-                const int cl = __float_as_int(n.lmin.w), cr = __float_as_int(n.rmin.w);
-                if (hl && hr) {
-                    const bool lf = tl <= tr;
-                    push<STACK>(stk, sp, lf ? cr : cl);
-                    ref = lf ? cl : cr;
-                    pop = false;
-                } else if (hl | hr) {
-                    ref = hl ? cl : cr;
-                    pop = false;
-                }
-            }
-            if (pop) {
-                if (sp > 0) {
-                    ref = pop_ref<STACK>(stk, sp);
-                } else {
-                    trav = false;
-                    done = true;
-                }
-            }
-            if (trav && ref < 0 && pend < 0) pend = ~ref; // entering a leaf
+        if (st.ended) {
+            trav = false;
+            done = true;
         }
-#endif
         if (STATS) {
             cnt.iters++;
             if (trav) cnt.q_steps++;
@@ -1909,6 +1983,32 @@ __global__ void __launch_bounds__(256, WIDTH == 4 ? RT_BVH_WAVES : RT_BVH2_WAVES
 }
 
 #ifndef __HIPCC_RTC__ // the host side and the other kernels (not part of a hiprtc build)
+// The wave's pool of ray indices in the ray-list kernels (wave-uniform): one atomicAdd of 256 on
+// the grid's counter whenever the lanes without a query outnumber what is left of the last grant.
+struct RayPool {
+    unsigned next, end;
+};
+// need: the lane has no query; m = __ballot(need), not 0.  Returns the ray index of a lane in need
+// (which may lie past the last ray) and takes the wave's indices out of the pool.
+__device__ __forceinline__ unsigned pool_take(RayPool& pool, bool need, unsigned long long m, int lane, unsigned* counter)
+{
+    const unsigned kk = (unsigned)__popcll(m), avail = pool.end - pool.next;
+    unsigned fresh = 0;
+    if (kk > avail) {
+        if (lane == 0) fresh = atomicAdd(counter, 256u);
+        fresh = __builtin_amdgcn_readfirstlane(fresh);
+    }
+    const unsigned r = (unsigned)__popcll(m & ((1ull << lane) - 1ull));
+    const unsigned idx = r < avail ? pool.next + r : fresh + (r - avail);
+    if (kk > avail) {
+        pool.next = fresh + (kk - avail);
+        pool.end = fresh + 256u;
+    } else {
+        pool.next += kk;
+    }
+    return need ? idx : 0xFFFFFFFFu;
+}
+
 // Trace-only kernel (rt_debug_trace_rays): the wide BVH kernel's speculative traversal over a
 // list of logged queries, with no shading phase and no path state, so that each lane takes the
 // next ray as soon as its query ends.  It measures the traversal stage of a wavefront split
@@ -1923,26 +2023,22 @@ __global__ void __launch_bounds__(256, WAVES) trace_rays_kernel(TraceRaysParams 
     const RT_AS_CONST float4* rows = (const RT_AS_CONST float4*)p.rows;
     const RT_AS_CONST Node4Q* nodes4 = (const RT_AS_CONST Node4Q*)p.nodes4;
     const RT_AS_CONST XformF* xf = (const RT_AS_CONST XformF*)p.xf;
-    bool trav = false, more = false, exhausted = false;
-    int ref = 0, sp = 0, pend = -1, prev = -1;
+    bool trav = false, exhausted = false;
+    Walk w{false, 0, 0, -1};
+    int prev = -1;
     unsigned n_tri = 0, n_sph = 0;
-    unsigned idx = 0, pool_next = 0, pool_end = 0; // the wave's pool of ray indices (uniform)
+    unsigned idx = 0;
+    RayPool pool{0, 0};
     V3 o{0, 0, 0}, d{0, 0, 0}, id{0, 0, 0}, oi{0, 0, 0};
     Best b{__builtin_huge_valf(), -1};
     unsigned long long n_node = 0, n_leaf = 0, n_slots = 0;
     while (true) {
         const bool need = !trav && !exhausted;
         const unsigned long long m = __ballot(need);
-        if (m) { // lanes without a query take the next rays (one atomic per 256 rays per wave)
-            const unsigned kk = (unsigned)__popcll(m), avail = pool_end - pool_next;
-            unsigned fresh = 0;
-            if (kk > avail) {
-                if (lane == 0) fresh = atomicAdd(p.counter, 256u);
-                fresh = __builtin_amdgcn_readfirstlane(fresh);
-            }
+        if (m) { // lanes without a query take the next rays
+            const unsigned take = pool_take(pool, need, m, lane, p.counter);
             if (need) {
-                const unsigned r = (unsigned)__popcll(m & ((1ull << lane) - 1ull));
-                idx = r < avail ? pool_next + r : fresh + (r - avail);
+                idx = take;
                 if (idx >= p.n) {
                     exhausted = true;
                 } else {
@@ -1952,55 +2048,46 @@ __global__ void __launch_bounds__(256, WAVES) trace_rays_kernel(TraceRaysParams 
                     prev = __float_as_int(r0.w);
                     id = v3(slab_rcp(d.x), slab_rcp(d.y), slab_rcp(d.z));
                     oi = o * id;
-                    ref = p.root4;
-                    sp = 0;
-                    pend = -1;
-                    more = true;
-                    if (ref < 0) {
-                        pend = ~ref;
-                        more = false;
-                    }
+                    walk_start(w, p.root4, true); // (rt_debug_trace_rays refuses a scene without wide nodes)
                     b = Best{__builtin_huge_valf(), -1};
                     trav = true;
                 }
             }
-            if (kk > avail) {
-                pool_next = fresh + (kk - avail);
-                pool_end = fresh + 256u;
-            } else {
-                pool_next += kk;
-            }
         }
         if (!__any(trav)) break;
-        const bool can_node = trav && more && ref >= 0;
-        const bool blocked = trav && pend >= 0 && !can_node;
+        // walk_step's closest-hit body, written out: this kernel measures the traversal loop, and as a call
+        // its 8-wave instance (64 VGPRs) held two more values across the loop and spilled o / d (3.59 ->
+        // 4.01 ms; 3.68 ms with o / d formed per visit; profiles/shared_walk).  A change to the step is made
+        // in both places.
+        const bool can_node = trav && w.more && w.ref >= 0;
+        const bool blocked = trav && w.pend >= 0 && !can_node;
         const bool leaf_step = __ballot(can_node) == 0 || __popcll(__ballot(blocked)) >= p.spec;
         if (STATS) {
             n_slots += 64;
-            if (leaf_step) n_leaf += (trav && pend >= 0) ? 1 : 0;
+            if (leaf_step) n_leaf += (trav && w.pend >= 0) ? 1 : 0;
             else n_node += can_node ? 1 : 0;
         }
         if (trav) {
             if (leaf_step) {
-                if (pend >= 0) {
-                    test_leaf<false>(tests, rows, xf, pend, o, d, prev, b, n_tri, n_sph);
-                    pend = leaf_advance(pend, RT_SPEC_PRIMS);
+                if (w.pend >= 0) {
+                    test_leaf<false>(tests, rows, xf, w.pend, o, d, prev, b, n_tri, n_sph);
+                    w.pend = leaf_advance(w.pend, RT_SPEC_PRIMS);
                 }
             } else if (can_node) {
                 bool pop = true;
-                const Node4Q q = nodes4[ref];
-                wide_visit<STACK>(q, id, oi, b.t, ref, sp, stk, pop);
+                const Node4Q q = nodes4[w.ref];
+                wide_visit<STACK>(q, id, oi, b.t, w.ref, w.sp, stk, pop);
                 if (pop) {
-                    if (sp > 0) ref = pop_ref<STACK>(stk, sp);
-                    else more = false;
+                    if (w.sp > 0) w.ref = pop_ref<STACK>(stk, w.sp);
+                    else w.more = false;
                 }
             }
-            if (more && ref < 0 && pend < 0) {
-                pend = ~ref;
-                if (sp > 0) ref = pop_ref<STACK>(stk, sp);
-                else more = false;
+            if (w.more && w.ref < 0 && w.pend < 0) {
+                w.pend = ~w.ref;
+                if (w.sp > 0) w.ref = pop_ref<STACK>(stk, w.sp);
+                else w.more = false;
             }
-            if (!more && pend < 0) {
+            if (!w.more && w.pend < 0) {
                 trav = false;
                 if (p.outer)
                     test_outer<false>((const RT_AS_CONST GroupRec*)p.outer, (const RT_AS_CONST RectRec*)p.outer_rects,
@@ -2112,19 +2199,15 @@ __global__ void __launch_bounds__(256, CULL ? RT_GROUPED_WAVES : RT_PATH_WAVES) 
             unsigned n_flat = 0, n_sph = 0, n_node = 0;
             trace_brute<CULL, false>(p.scene, groups, tests, rects, frames, boxes, xf, q.o, q.d, -1, b, n_flat, n_sph,
                                      n_node);
-            const int pln0 = p.scene.n_bvh;
-            for (int k = pln0; k < pln0 + p.scene.n_pln; k++) {
-                const TestRec tr = tests[k];
-                hit_plane<true>(tr, k, q.o, q.d, -1, b);
-            }
+            test_planes(p.scene, tests, q.o, q.d, -1, b);
         }
         query_hit<false>(p.scene.facts, p.prims, p.xf, vnormals, tests, b, q.o, q.d, p.hits + (size_t)kHitRows * i);
     }
 }
 
-// The wide BVH: trace_rays_kernel's speculative loop (ballot refill, one atomicAdd per 256 rays per
-// wave, LDS stack with the global overflow area), and when a query ends what path_kernel_bvh does
-// then: the outer records, the planes that follow the BVH order, and the hit.
+// The wide BVH: the speculative walk over rays from the wave's pool, as in trace_rays_kernel, and
+// when a query ends what path_kernel_bvh does then: the outer records, the planes that follow the
+// BVH order, and the hit.
 template <int STACK>
 __global__ void __launch_bounds__(256, RT_BVH_WAVES) query_bvh_kernel(QueryParams p)
 {
@@ -2136,25 +2219,21 @@ __global__ void __launch_bounds__(256, RT_BVH_WAVES) query_bvh_kernel(QueryParam
     const RT_AS_CONST Node4Q* nodes4 = (const RT_AS_CONST Node4Q*)p.nodes4;
     const RT_AS_CONST XformF* xf = (const RT_AS_CONST XformF*)p.xf;
     const RT_AS_CONST float4* vnormals = (const RT_AS_CONST float4*)p.vnormals;
-    bool trav = false, more = false, exhausted = false;
-    int ref = 0, sp = 0, pend = -1;
+    const auto fetch = [&](int ref) { return Node4Q(nodes4[ref]); };
+    bool trav = false, exhausted = false;
+    Walk w{false, 0, 0, -1};
     unsigned n_tri = 0, n_sph = 0;
-    unsigned idx = 0, pool_next = 0, pool_end = 0; // the wave's pool of ray indices (uniform)
+    unsigned idx = 0;
+    RayPool pool{0, 0};
     V3 o{0, 0, 0}, d{0, 0, 0}, id{0, 0, 0}, oi{0, 0, 0};
     Best b{__builtin_huge_valf(), -1};
     while (true) {
         const bool need = !trav && !exhausted;
         const unsigned long long m = __ballot(need);
-        if (m) { // lanes without a query take the next rays (one atomic per 256 rays per wave)
-            const unsigned kk = (unsigned)__popcll(m), avail = pool_end - pool_next;
-            unsigned fresh = 0;
-            if (kk > avail) {
-                if (lane == 0) fresh = atomicAdd(p.counter, 256u);
-                fresh = __builtin_amdgcn_readfirstlane(fresh);
-            }
+        if (m) { // lanes without a query take the next rays
+            const unsigned take = pool_take(pool, need, m, lane, p.counter);
             if (need) {
-                const unsigned r = (unsigned)__popcll(m & ((1ull << lane) - 1ull));
-                idx = r < avail ? pool_next + r : fresh + (r - avail);
+                idx = take;
                 if (idx >= p.n) {
                     exhausted = true;
                 } else {
@@ -2166,64 +2245,24 @@ __global__ void __launch_bounds__(256, RT_BVH_WAVES) query_bvh_kernel(QueryParam
                         d = q.d;
                         id = v3(slab_rcp(d.x), slab_rcp(d.y), slab_rcp(d.z));
                         oi = o * id;
-                        ref = p.root4;
-                        sp = 0;
-                        pend = -1;
-                        more = p.n_nodes4 > 0; // (no tree at all: only planes, and the query ends at once)
-                        if (ref < 0) {
-                            pend = ~ref;
-                            more = false;
-                        }
+                        walk_start(w, p.root4, p.n_nodes4 > 0);
                         b = Best{__builtin_huge_valf(), -1};
                         trav = true;
                     }
                 }
-            }
-            if (kk > avail) {
-                pool_next = fresh + (kk - avail);
-                pool_end = fresh + 256u;
-            } else {
-                pool_next += kk;
             }
         }
         if (!__any(trav)) {
             if (__any(!exhausted)) continue; // only invalid rays this round: refill again
             break;
         }
-        const bool can_node = trav && more && ref >= 0;
-        const bool blocked = trav && pend >= 0 && !can_node;
-        const bool leaf_step = __ballot(can_node) == 0 || __popcll(__ballot(blocked)) >= p.spec;
-        if (trav) {
-            if (leaf_step) {
-                if (pend >= 0) {
-                    test_leaf<false>(tests, rows, xf, pend, o, d, -1, b, n_tri, n_sph);
-                    pend = leaf_advance(pend, RT_SPEC_PRIMS);
-                }
-            } else if (can_node) {
-                bool pop = true;
-                const Node4Q node = nodes4[ref];
-                wide_visit<STACK>(node, id, oi, b.t, ref, sp, stk, pop);
-                if (pop) {
-                    if (sp > 0) ref = pop_ref<STACK>(stk, sp);
-                    else more = false;
-                }
-            }
-            if (more && ref < 0 && pend < 0) {
-                pend = ~ref;
-                if (sp > 0) ref = pop_ref<STACK>(stk, sp);
-                else more = false;
-            }
-            if (!more && pend < 0) { // the query ended: the records outside the tree, then its Hit
-                trav = false;
-                if (p.scene.n_groups > 0)
-                    test_outer<false>((const RT_AS_CONST GroupRec*)p.groups, (const RT_AS_CONST RectRec*)p.rects,
-                                      (const RT_AS_CONST BoxRec*)p.frames, o, d, -1, b, n_tri);
-                for (int k = p.scene.n_bvh; k < p.scene.n_bvh + p.scene.n_pln; k++) {
-                    const TestRec tr = tests[k];
-                    hit_plane<true>(tr, k, o, d, -1, b);
-                }
-                query_hit<true>(p.scene.facts, p.prims, p.xf, vnormals, tests, b, o, d, p.hits + (size_t)kHitRows * idx);
-            }
+        if (walk_step<STACK, false>(w, trav, p.spec, fetch, id, oi, stk, tests, rows, xf, o, d, -1, b, n_tri, n_sph).ended) {
+            trav = false; // the records outside the tree, then the query's Hit
+            if (p.scene.n_groups > 0)
+                test_outer<false>((const RT_AS_CONST GroupRec*)p.groups, (const RT_AS_CONST RectRec*)p.rects,
+                                  (const RT_AS_CONST BoxRec*)p.frames, o, d, -1, b, n_tri);
+            test_planes(p.scene, tests, o, d, -1, b);
+            query_hit<true>(p.scene.facts, p.prims, p.xf, vnormals, tests, b, o, d, p.hits + (size_t)kHitRows * idx);
         }
     }
 }
@@ -2238,15 +2277,6 @@ __global__ void __launch_bounds__(256, RT_BVH_WAVES) query_bvh_kernel(QueryParam
 __device__ __forceinline__ float load_t_max(const double* __restrict__ t_max, unsigned i)
 {
     return t_max ? (float)t_max[i] : __builtin_huge_valf();
-}
-
-template <class TestP>
-__device__ __forceinline__ void occluded_planes(const PathScene& s, TestP tests, V3 o, V3 d, Best& b)
-{
-    for (int k = s.n_bvh; k < s.n_bvh + s.n_pln; k++) {
-        const TestRec tr = tests[k];
-        hit_plane<true>(tr, k, o, d, -1, b);
-    }
 }
 
 // Brute force (CULL: the grouped order): query_brute_kernel's loop around trace_brute's any-hit form.
@@ -2268,64 +2298,19 @@ __global__ void __launch_bounds__(256, CULL ? RT_GROUPED_WAVES : RT_PATH_WAVES) 
         Best b{tm, -1};
         if (q.valid & (tm > 0.0f)) {
             unsigned n_flat = 0, n_sph = 0, n_node = 0;
-            if (P.early) occluded_planes(p.scene, tests, q.o, q.d, b);
+            if (P.early) test_planes(p.scene, tests, q.o, q.d, -1, b);
             if (__any(b.sg < 0)) {
                 trace_brute<CULL, false, true>(p.scene, groups, tests, rects, frames, boxes, xf, q.o, q.d, -1, b, n_flat,
                                                n_sph, n_node);
-                if (!P.early) occluded_planes(p.scene, tests, q.o, q.d, b);
+                if (!P.early) test_planes(p.scene, tests, q.o, q.d, -1, b);
             }
         }
         P.out[i] = b.sg >= 0 ? 1 : 0;
     }
 }
 
-// One visit of a 4-wide node for an any-hit query: wide_visit's four slab tests against the segment's
-// end, without the sorting network (no child is nearer in any sense that matters).  The first hit
-// child in slot order is entered and the other hit children are pushed, to be popped in slot order.
-template <int STACK>
-__device__ __forceinline__ void any_visit(const Node4Q& q, V3 id, V3 oi, float best, int& ref, int& sp,
-                                          const TravStack& stk, bool& pop)
-{
-    const uint32_t ex = __float_as_uint(q.a.w);
-    const float ax = __builtin_amdgcn_ldexpf(id.x, (int)(ex & 255u) - 128);
-    const float ay = __builtin_amdgcn_ldexpf(id.y, (int)((ex >> 8) & 255u) - 128);
-    const float az = __builtin_amdgcn_ldexpf(id.z, (int)((ex >> 16) & 255u) - 128);
-    const float bx = fmaf(q.a.x, id.x, -oi.x), by = fmaf(q.a.y, id.y, -oi.y), bz = fmaf(q.a.z, id.z, -oi.z);
-    const uint32_t lx = __float_as_uint(q.b.x), hx = __float_as_uint(q.b.y);
-    const uint32_t ly = __float_as_uint(q.b.z), hy = __float_as_uint(q.b.w);
-    const uint32_t lz = __float_as_uint(q.c.x), hz = __float_as_uint(q.c.y);
-    const bool px = id.x >= 0.0f, py = id.y >= 0.0f, pz = id.z >= 0.0f; // near / far planes by the direction's sign
-    const uint32_t nx = px ? lx : hx, fx = px ? hx : lx;
-    const uint32_t ny = py ? ly : hy, fy = py ? hy : ly;
-    const uint32_t nz = pz ? lz : hz, fz = pz ? hz : lz;
-    const int nc = __float_as_int(q.d.z);
-    const int r0 = __float_as_int(q.c.z), r1 = __float_as_int(q.c.w), r2 = __float_as_int(q.d.x), r3 = __float_as_int(q.d.y);
-    const float tmax_best = best * 1.00000024f;
-    bool h0, h1, h2, h3;
-#define RT_ANY_CHILD(K, H)                                                                                        \
-    {                                                                                                             \
-        const float tmin = fmaxf(fmaxf(fmaxf(fmaf(ubyte(nx, K), ax, bx), fmaf(ubyte(ny, K), ay, by)),              \
-                                       fmaf(ubyte(nz, K), az, bz)), 0.0f);                                         \
-        const float tmax = fminf(fminf(fmaf(ubyte(fx, K), ax, bx), fmaf(ubyte(fy, K), ay, by)),                   \
-                                 fmaf(ubyte(fz, K), az, bz));                                                      \
-        H = (K < nc) & (tmin <= fminf(tmax * 1.00000024f, tmax_best));                                            \
-    } // the same test as RT_WIDE_CHILD (wide_visit)
-    RT_ANY_CHILD(0, h0)
-    RT_ANY_CHILD(1, h1)
-    RT_ANY_CHILD(2, h2)
-    RT_ANY_CHILD(3, h3)
-#undef RT_ANY_CHILD
-    if (h0 | h1 | h2 | h3) {
-        if (h3 & (h0 | h1 | h2)) push<STACK>(stk, sp, r3);
-        if (h2 & (h0 | h1)) push<STACK>(stk, sp, r2);
-        if (h1 & h0) push<STACK>(stk, sp, r1);
-        ref = h0 ? r0 : h1 ? r1 : h2 ? r2 : r3;
-        pop = false;
-    }
-}
-
-// The wide BVH: query_bvh_kernel's speculative loop.  A lane's query ends the moment a leaf step
-// gives it a hit, and the lane takes its next ray at the next ballot.  The records outside the tree
+// The wide BVH: query_bvh_kernel's loop around the any-hit walk.  A lane's query ends the moment a leaf
+// step gives it a hit, and the lane takes its next ray at the next ballot.  The records outside the tree
 // (the outer group and the planes) are tested when the ray is loaded (P.early) or when the tree gave
 // no hit.  A visit pushes at most (children - 1) entries per level, as wide_visit does, so the host's
 // bound on the stack depth holds for any order of descent.
@@ -2340,31 +2325,27 @@ __global__ void __launch_bounds__(256, RT_BVH_WAVES) occluded_bvh_kernel(Occlude
     const RT_AS_CONST float4* rows = (const RT_AS_CONST float4*)p.rows;
     const RT_AS_CONST Node4Q* nodes4 = (const RT_AS_CONST Node4Q*)p.nodes4;
     const RT_AS_CONST XformF* xf = (const RT_AS_CONST XformF*)p.xf;
-    bool trav = false, more = false, exhausted = false;
-    int ref = 0, sp = 0, pend = -1;
+    const auto fetch = [&](int ref) { return Node4Q(nodes4[ref]); };
+    bool trav = false, exhausted = false;
+    Walk w{false, 0, 0, -1};
     unsigned n_tri = 0, n_sph = 0;
-    unsigned idx = 0, pool_next = 0, pool_end = 0; // the wave's pool of ray indices (uniform)
+    unsigned idx = 0;
+    RayPool pool{0, 0};
     V3 o{0, 0, 0}, d{0, 0, 0}, id{0, 0, 0}, oi{0, 0, 0};
     Best b{__builtin_huge_valf(), -1};
     auto outside = [&]() { // the records outside the tree
         if (p.scene.n_groups > 0)
             test_outer<false>((const RT_AS_CONST GroupRec*)p.groups, (const RT_AS_CONST RectRec*)p.rects,
                               (const RT_AS_CONST BoxRec*)p.frames, o, d, -1, b, n_tri);
-        occluded_planes(p.scene, tests, o, d, b);
+        test_planes(p.scene, tests, o, d, -1, b);
     };
     while (true) {
         const bool need = !trav && !exhausted;
         const unsigned long long m = __ballot(need);
-        if (m) { // lanes without a query take the next rays (one atomic per 256 rays per wave)
-            const unsigned kk = (unsigned)__popcll(m), avail = pool_end - pool_next;
-            unsigned fresh = 0;
-            if (kk > avail) {
-                if (lane == 0) fresh = atomicAdd(p.counter, 256u);
-                fresh = __builtin_amdgcn_readfirstlane(fresh);
-            }
+        if (m) { // lanes without a query take the next rays
+            const unsigned take = pool_take(pool, need, m, lane, p.counter);
             if (need) {
-                const unsigned r = (unsigned)__popcll(m & ((1ull << lane) - 1ull));
-                idx = r < avail ? pool_next + r : fresh + (r - avail);
+                idx = take;
                 if (idx >= p.n) {
                     exhausted = true;
                 } else {
@@ -2385,61 +2366,20 @@ __global__ void __launch_bounds__(256, RT_BVH_WAVES) occluded_bvh_kernel(Occlude
                     } else {
                         id = v3(slab_rcp(d.x), slab_rcp(d.y), slab_rcp(d.z));
                         oi = o * id;
-                        ref = p.root4;
-                        sp = 0;
-                        pend = -1;
-                        more = p.n_nodes4 > 0; // (no tree at all: only planes, and the query ends at once)
-                        if (ref < 0) {
-                            pend = ~ref;
-                            more = false;
-                        }
+                        walk_start(w, p.root4, p.n_nodes4 > 0);
                         trav = true;
                     }
                 }
-            }
-            if (kk > avail) {
-                pool_next = fresh + (kk - avail);
-                pool_end = fresh + 256u;
-            } else {
-                pool_next += kk;
             }
         }
         if (!__any(trav)) {
             if (__any(!exhausted)) continue; // only answered rays this round: refill again
             break;
         }
-        const bool can_node = trav && more && ref >= 0;
-        const bool blocked = trav && pend >= 0 && !can_node;
-        const bool leaf_step = __ballot(can_node) == 0 || __popcll(__ballot(blocked)) >= p.spec;
-        if (trav) {
-            if (leaf_step) {
-                if (pend >= 0) {
-                    test_leaf<false>(tests, rows, xf, pend, o, d, -1, b, n_tri, n_sph);
-                    pend = leaf_advance(pend, RT_SPEC_PRIMS);
-                    if (b.sg >= 0) { // the answer: the rest of the leaf and of the tree is not looked at
-                        pend = -1;
-                        more = false;
-                    }
-                }
-            } else if (can_node) {
-                bool pop = true;
-                const Node4Q node = nodes4[ref];
-                any_visit<STACK>(node, id, oi, b.t, ref, sp, stk, pop);
-                if (pop) {
-                    if (sp > 0) ref = pop_ref<STACK>(stk, sp);
-                    else more = false;
-                }
-            }
-            if (more && ref < 0 && pend < 0) {
-                pend = ~ref;
-                if (sp > 0) ref = pop_ref<STACK>(stk, sp);
-                else more = false;
-            }
-            if (!more && pend < 0) { // the query ended
-                trav = false;
-                if (!P.early && b.sg < 0) outside();
-                P.out[idx] = b.sg >= 0 ? 1 : 0;
-            }
+        if (walk_step<STACK, true>(w, trav, p.spec, fetch, id, oi, stk, tests, rows, xf, o, d, -1, b, n_tri, n_sph).ended) {
+            trav = false;
+            if (!P.early && b.sg < 0) outside();
+            P.out[idx] = b.sg >= 0 ? 1 : 0;
         }
     }
 }
@@ -2764,14 +2704,20 @@ size_t path_dyn_lds(const DevScene& s, int variant)
     return b;
 }
 
-int path_blocks_per_cu(int variant, size_t dyn_lds, bool stats, bool vn, bool rays)
+// Blocks of 256 threads a CU can hold of a kernel, at least 1 (also when the runtime cannot say).
+template <class KernelT>
+int blocks_per_cu(KernelT kernel, size_t dyn_lds = 0)
 {
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(pick(variant, stats, vn, rays)), 256,
-                                                     dyn_lds) != hipSuccess ||
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(kernel), 256, dyn_lds) != hipSuccess ||
         n < 1)
         n = 1;
     return n;
+}
+
+int path_blocks_per_cu(int variant, size_t dyn_lds, bool stats, bool vn, bool rays)
+{
+    return blocks_per_cu(pick(variant, stats, vn, rays), dyn_lds);
 }
 
 void fill_launch(const DevScene& s, int variant, PathParams& p)
@@ -2888,15 +2834,7 @@ TraceKernel pick_trace(int waves, bool stats)
     return stats ? trace_rays_kernel<20, 6, true> : trace_rays_kernel<20, 6, false>;
 }
 
-int trace_rays_blocks_per_cu(int waves)
-{
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(pick_trace(waves, false)), 256, 0) !=
-            hipSuccess ||
-        n < 1)
-        n = 1;
-    return n;
-}
+int trace_rays_blocks_per_cu(int waves) { return blocks_per_cu(pick_trace(waves, false)); }
 
 hipError_t launch_trace_rays(const TraceRaysParams& p, int waves, int grid_blocks, hipStream_t stream)
 {
@@ -2911,15 +2849,7 @@ QueryKernel pick_query(int kernel)
     return kernel == 1 ? query_brute_kernel<true> : query_brute_kernel<false>;
 }
 
-int query_blocks_per_cu(int kernel)
-{
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(pick_query(kernel)), 256, 0) !=
-            hipSuccess ||
-        n < 1)
-        n = 1;
-    return n;
-}
+int query_blocks_per_cu(int kernel) { return blocks_per_cu(pick_query(kernel)); }
 
 hipError_t launch_query(const QueryParams& p, int kernel, int grid_blocks, hipStream_t stream)
 {
@@ -2934,15 +2864,7 @@ OccludedKernel pick_occluded(int kernel)
     return kernel == 1 ? occluded_brute_kernel<true> : occluded_brute_kernel<false>;
 }
 
-int occluded_blocks_per_cu(int kernel)
-{
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(pick_occluded(kernel)), 256, 0) !=
-            hipSuccess ||
-        n < 1)
-        n = 1;
-    return n;
-}
+int occluded_blocks_per_cu(int kernel) { return blocks_per_cu(pick_occluded(kernel)); }
 
 hipError_t launch_occluded(const OccludedParams& p, int kernel, int grid_blocks, hipStream_t stream)
 {

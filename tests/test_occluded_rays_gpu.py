@@ -318,6 +318,46 @@ def test_o5_degenerate_rays_and_segments(rc, mode):
     gpu.close()
 
 
+# which of 300 rays are spoiled, as in test_query_rays_gpu.py's test_g6_refill_rounds_of_invalid_rays_only;
+# "head_t0" spoils the first 200 by t_max = 0 in place of the NaN origin
+O5_SPOILED = {"head": slice(0, 200), "all": slice(0, 300), "tail": slice(170, 300), "head_t0": slice(0, 200)}
+
+
+@pytest.fixture(scope="module")
+def o5_mesh(rc):
+    gpu = _gpu(rc, "mesh41", "BVH")
+    R = _rays("mesh41")
+    hit = R["ids"] >= 0
+    tm = _t_max(hit, ~hit, R["t"], F_FAST)[:300]
+    o, d = R["o"][:300], R["d"][:300]
+    yield gpu, o, d, tm, gpu.occluded_rays(o, d, tm), gpu.occluded_rays(o, d)
+    gpu.close()
+
+
+@pytest.mark.parametrize("case", list(O5_SPOILED))
+def test_o5_refill_rounds_of_answered_rays_only(rc, o5_mesh, case):
+    """The BVH kernel's refill rounds in which every ray a wave draws is answered where it is loaded, so
+    that no lane starts a walk: each spoiled ray is 0 and the other rays' answers are what they were, with
+    and without t_max."""
+    gpu, o, d, tm, ref_tm, ref_inf = o5_mesh
+    o, tm = o.copy(), tm.copy()
+    bad = np.zeros(300, bool)
+    bad[O5_SPOILED[case]] = True
+    if case == "head_t0":
+        tm[bad] = 0.0
+    else:
+        o[bad, 0] = np.nan
+    got = gpu.occluded_rays(o, d, tm)
+    _bytes_ok(got)
+    assert got.shape == (300,) and not got[bad].any()
+    assert np.array_equal(got[~bad], ref_tm[~bad])
+    assert ref_tm[bad].any() and ref_inf[bad].any()  # some of the spoiled rays were occluded before
+    assert ref_tm.any() and not ref_tm.all()
+    if case != "head_t0":
+        got = gpu.occluded_rays(o, d)
+        assert not got[bad].any() and np.array_equal(got[~bad], ref_inf[~bad])
+
+
 # ---------------------------------------------------------------- O6: manners
 def _rc_of(lib, *args):
     rc_ = lib.rt_occluded_rays(*args)

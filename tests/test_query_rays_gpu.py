@@ -360,6 +360,32 @@ def test_g6_degenerate_rays_are_misses(rc, mode):
     gpu.close()
 
 
+# which of 300 rays get a NaN origin: the first 200 (the wave that draws rays 0-255 refills three times
+# over without starting a walk), all of them (no wave ever walks), the last 130 (its last rounds)
+G6_SPOILED = {"head": slice(0, 200), "all": slice(0, 300), "tail": slice(170, 300)}
+
+
+@pytest.mark.parametrize("case", list(G6_SPOILED))
+def test_g6_refill_rounds_of_invalid_rays_only(rc, mesh_bvh, case):
+    """The BVH kernel's refill rounds in which every ray a wave draws is invalid, so that no lane starts a
+    walk: each invalid ray is a miss record, and the valid rays' records are, bit for bit, those of the
+    same rays queried alone."""
+    R = _rays("mesh41")
+    o, d = R["o"][:300].copy(), R["d"][:300].copy()
+    bad = np.zeros(300, bool)
+    bad[G6_SPOILED[case]] = True
+    o[bad, 0] = np.nan
+    hits = mesh_bvh.query_rays(o, d)
+    assert hits.shape == (300,)
+    assert (hits["prim_id"][bad] == -1).all()
+    assert not hits["distance"][bad].any() and not hits["inside"][bad].any() and not hits["reserved"][bad].any()
+    assert not hits["position"][bad].view(np.uint32).any() and not hits["normal"][bad].view(np.uint32).any()
+    alone = mesh_bvh.query_rays(o[~bad], d[~bad])
+    assert _same_bits(hits[~bad], alone)
+    assert case == "all" or ((alone["prim_id"] >= 0).any() and (alone["prim_id"] < 0).any())
+    assert (R["ids"][:300][bad] >= 0).any()  # some of the spoiled rays were hits
+
+
 def test_g6_a_query_leaves_the_renderer_alone(rc):
     """A render after queries equals the same render before them bit for bit; the counters of
     rt_scene_get_stats and the rt_kernel_times ring are what they were."""

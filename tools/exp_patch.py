@@ -25,7 +25,11 @@ TRACE_CALL = ("            if (query)\n"
 BOUNCE_CALL = "            bounce<VN, false, false, STATS>(L, S, sc, R, vnormals, tests, pq->prims_d, b, *pq);\n"
 RAYS_LINE = "        wave_rays += (unsigned)__popcll(__ballot(L.live)); // one Scene.RayTrace per live lane\n"
 
-NODE_LOAD = '                    const Node4Q q = (ref & RT_HOT_BIT) ? lds_hot[ref & ~RT_HOT_BIT] : Node4Q(nodes4[ref]);\n'
+# path_kernel_bvh's node fetch (the lambda handed to walk_step); the replacements return the Node4Q
+NODE_LOAD = ('            if constexpr (WIDTH == 4) return (ref & RT_HOT_BIT) ? lds_node(hot_rows, ref & ~RT_HOT_BIT) : '
+             'Node4Q(nodes4[ref]);\n')
+NODE_OPEN = "            if constexpr (WIDTH == 4) {\n"
+NODE_CLOSE = "                    return q;\n            }\n"
 HOT_ON = '    static const bool on = !(getenv("RTCORE_HOT_NODES") && getenv("RTCORE_HOT_NODES")[0] == \'0\'); // A/B switch\n'
 
 PATCHES = {
@@ -86,10 +90,10 @@ PATCHES = {
                  "            r[j][2] = make_float4(a2.x, a2.y, a2.z, a2.w);\n"
                  "        }\n")],
     # wide nodes loaded non-temporally
-    "NT_NODES": [("                    const Node4Q q = (ref & RT_HOT_BIT) ? lds_hot[ref & ~RT_HOT_BIT] : Node4Q(nodes4[ref]);\n"
-                  "                    [[maybe_unused]] const int sp0 = sp;\n",
+    "NT_NODES": [(NODE_LOAD,
+                  NODE_OPEN +
                   "                    Node4Q q;\n"
-                  "                    if (ref & RT_HOT_BIT) q = lds_hot[ref & ~RT_HOT_BIT];\n"
+                  "                    if (ref & RT_HOT_BIT) q = lds_node(hot_rows, ref & ~RT_HOT_BIT);\n"
                   "                    else {\n"
                   "                        typedef float ntf4 __attribute__((ext_vector_type(4)));\n"
                   "                        typedef __attribute__((address_space(1))) const ntf4 gf4;\n"
@@ -100,13 +104,13 @@ PATCHES = {
                   "                        q.b = make_float4(a1.x, a1.y, a1.z, a1.w);\n"
                   "                        q.c = make_float4(a2.x, a2.y, a2.z, a2.w);\n"
                   "                        q.d = make_float4(a3.x, a3.y, a3.z, a3.w);\n"
-                  "                    }\n"
-                  "                    [[maybe_unused]] const int sp0 = sp;\n")],
+                  "                    }\n" + NODE_CLOSE)],
     # round 6, C4 visit VALU: no hot-node table (no LDS-or-global select per visit)
-    "WIDE_NOHOT": [(NODE_LOAD, "                    const Node4Q q = nodes4[ref];\n"),
+    "WIDE_NOHOT": [(NODE_LOAD, "            if constexpr (WIDTH == 4) return Node4Q(nodes4[ref]);\n"),
                    (HOT_ON, "    static const bool on = false;\n")],
     # ... and the node read through a buffer resource with a 32-bit byte offset (no 64-bit address math)
     "WIDE_BUFLOAD": [(NODE_LOAD,
+                      NODE_OPEN +
                       "                    Node4Q q;\n"
                       "                    {\n"
                       "                        typedef float v4f __attribute__((ext_vector_type(4)));\n"
@@ -121,12 +125,13 @@ PATCHES = {
                       "                        q.b = make_float4(a1.x, a1.y, a1.z, a1.w);\n"
                       "                        q.c = make_float4(a2.x, a2.y, a2.z, a2.w);\n"
                       "                        q.d = make_float4(a3.x, a3.y, a3.z, a3.w);\n"
-                      "                    }\n"),
+                      "                    }\n" + NODE_CLOSE),
                      (HOT_ON, "    static const bool on = false;\n")],
     # the buffer-resource node read with the hot-node table kept (LDS for the top of the tree)
     "WIDE_BUFLOAD_HOT": [(NODE_LOAD,
+                          NODE_OPEN +
                           "                    Node4Q q;\n"
-                          "                    if (ref & RT_HOT_BIT) q = lds_hot[ref & ~RT_HOT_BIT];\n"
+                          "                    if (ref & RT_HOT_BIT) q = lds_node(hot_rows, ref & ~RT_HOT_BIT);\n"
                           "                    else {\n"
                           "                        typedef float v4f __attribute__((ext_vector_type(4)));\n"
                           "                        const __amdgpu_buffer_rsrc_t rs =\n"
@@ -140,7 +145,7 @@ PATCHES = {
                           "                        q.b = make_float4(a1.x, a1.y, a1.z, a1.w);\n"
                           "                        q.c = make_float4(a2.x, a2.y, a2.z, a2.w);\n"
                           "                        q.d = make_float4(a3.x, a3.y, a3.z, a3.w);\n"
-                          "                    }\n")],
+                          "                    }\n" + NODE_CLOSE)],
     # the leaf step's rows through a buffer resource too (32-bit byte offsets)
     "LEAF_BUFLOAD": [("        r[j][0] = rows[3 * (k + j)];\n"
                       "        r[j][1] = rows[3 * (k + j) + 1];\n"
@@ -159,7 +164,9 @@ PATCHES = {
     # the 4-child sort without its last exchange (the two middle pushes in either order)
     "WIDE_SORT4": [("    cswap(d1, r1, d2, r2);\n", "")],
     # the direction's signs computed once per query (after the shading phase) instead of per visit
-    "WIDE_SIGNS": [("                                           const TravStack& stk, bool& pop)\n",
+    "WIDE_SIGNS": [("__device__ __forceinline__ void wide_visit(const Node4Q& q, V3 id, V3 oi, float best, int& ref, int& sp,\n"
+                    "                                           const TravStack& stk, bool& pop)\n",
+                    "__device__ __forceinline__ void wide_visit(const Node4Q& q, V3 id, V3 oi, float best, int& ref, int& sp,\n"
                     "                                           const TravStack& stk, bool& pop, bool sgx, bool sgy, bool sgz)\n"),
                    ("    const uint32_t nx = id.x >= 0.0f ? lx : hx, fx = id.x >= 0.0f ? hx : lx;\n"
                     "    const uint32_t ny = id.y >= 0.0f ? ly : hy, fy = id.y >= 0.0f ? hy : ly;\n"
@@ -167,16 +174,23 @@ PATCHES = {
                     "    const uint32_t nx = sgx ? lx : hx, fx = sgx ? hx : lx;\n"
                     "    const uint32_t ny = sgy ? ly : hy, fy = sgy ? hy : ly;\n"
                     "    const uint32_t nz = sgz ? lz : hz, fz = sgz ? hz : lz;\n"),
-                   ("    V3 id{0, 0, 0};\n    Best b{", "    V3 id{0, 0, 0};\n    bool sgx = true, sgy = true, sgz = true;\n    Best b{"),
+                   # the signs ride in the Walk: set by the path kernel with 1/d, and by the ray kernels with theirs
+                   ("    int pend;  // the pending leaf (leaf_decode), -1 for none\n};\n",
+                    "    int pend;  // the pending leaf (leaf_decode), -1 for none\n    bool sgx, sgy, sgz;\n};\n"),
                    ("            id = v3(slab_rcp(S.d.x), slab_rcp(S.d.y), slab_rcp(S.d.z));\n",
                     "            id = v3(slab_rcp(S.d.x), slab_rcp(S.d.y), slab_rcp(S.d.z));\n"
-                    "            sgx = id.x >= 0.0f;\n            sgy = id.y >= 0.0f;\n            sgz = id.z >= 0.0f;\n"),
-                   ("                    wide_visit<STACK>(q, id, oi, b.t, ref, sp, stk, pop);\n",
-                    "                    wide_visit<STACK>(q, id, oi, b.t, ref, sp, stk, pop, sgx, sgy, sgz);\n"),
-                   ("                wide_visit<STACK>(q, id, S.o * id, b.t, ref, sp, stk, pop);\n",
-                    "                wide_visit<STACK>(q, id, S.o * id, b.t, ref, sp, stk, pop, id.x >= 0.0f, id.y >= 0.0f, id.z >= 0.0f);\n"),
-                   ("                wide_visit<STACK>(q, id, oi, b.t, ref, sp, stk, pop);\n",
-                    "                wide_visit<STACK>(q, id, oi, b.t, ref, sp, stk, pop, id.x >= 0.0f, id.y >= 0.0f, id.z >= 0.0f);\n")],
+                    "            w.sgx = id.x >= 0.0f;\n            w.sgy = id.y >= 0.0f;\n            w.sgz = id.z >= 0.0f;\n"),
+                   ("            else wide_visit<STACK>(node, id, oi, b.t, w.ref, w.sp, stk, pop);\n",
+                    "            else wide_visit<STACK>(node, id, oi, b.t, w.ref, w.sp, stk, pop, w.sgx, w.sgy, w.sgz);\n"),
+                   ("                wide_visit<STACK>(q, id, oi, b.t, w.ref, w.sp, stk, pop);\n",
+                    "                wide_visit<STACK>(q, id, oi, b.t, w.ref, w.sp, stk, pop, w.sgx, w.sgy, w.sgz);\n"),
+                   ("                    walk_start(w, p.root4, true); // (rt_debug_trace_rays refuses a scene without wide nodes)\n",
+                    "                    walk_start(w, p.root4, true);\n"
+                    "                    w.sgx = id.x >= 0.0f;\n                    w.sgy = id.y >= 0.0f;\n                    w.sgz = id.z >= 0.0f;\n"),
+                   ("                        walk_start(w, p.root4, p.n_nodes4 > 0);\n                        b = Best{",
+                    "                        walk_start(w, p.root4, p.n_nodes4 > 0);\n"
+                    "                        w.sgx = id.x >= 0.0f;\n                        w.sgy = id.y >= 0.0f;\n                        w.sgz = id.z >= 0.0f;\n"
+                    "                        b = Best{")],
     # no literal folding of zero scene fields in the specialised build
     "NO_KFOLD": [("    return __builtin_constant_p(c) && c == 0.0f;\n", "    return false;\n")],
 }
