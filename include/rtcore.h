@@ -260,6 +260,21 @@ int rt_debug_item_order(int32_t w, int32_t h, int32_t spp, int32_t chunks, int32
    1 when there is nothing to bound (an empty bound: no ray meets it), 2 when an extent is not finite
    (no skip for the scene), or a negative rt_status. */
 int rt_debug_scene_bound(const rt_prim* prims, int32_t n_prims, float* lo, float* hi, float* info);
+/* Host only (no device needed): the block cull of a brute-force launch -- which 8x8 pixel blocks of
+   the launch's window hold no pixel whose camera rays can meet the scene bound of these primitives.
+   The path kernels are not dealt such blocks: every sample of their pixels is a primary miss and one
+   ray (RTCORE_BLOCK_CULL=0 turns the cull off, RTCORE_BLOCK_CULL_MIN=<blocks> sets the smallest launch
+   that is culled).  width, height: the frame; (x0, y0, w, h): the window, tile pixel (px, py) being
+   frame pixel (x0 + px, y0 + py), or with band > 0 the band set's frame row
+   y0 + ((py / band) * band_stride + band_offset) * band + py % band (h = rt_band_rows of the set).
+   dead gets one byte per block, row-major over ceil(w / 8) x ceil(h / 8) blocks (1 = dead), while
+   they fit in cap; info (optional) gets {blocks per row, block rows}.  Every block is live when the
+   proof is not available: a scene with planes, a bound without skip, a camera with depth of field or
+   a value that is not finite, or one that stands inside or beside the bound.  Returns the number of
+   live blocks or a negative rt_status. */
+int rt_debug_block_cull(const rt_prim* prims, int32_t n_prims, const rt_camera* camera, int32_t width, int32_t height,
+                        int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t band, int32_t band_stride,
+                        int32_t band_offset, uint8_t* dead, int64_t cap, int32_t* info);
 /* Measurement of a wavefront split's traversal stage.  rt_debug_ray_log: while
    the next instrumented launch of a BVH kernel runs (rt_scene_set_stats; one launch only, then
    logging is off again), the kernel appends every finished query

@@ -256,6 +256,8 @@ def load_library(path: str = "") -> C.CDLL:
                                         P(C.c_int32)]),
         "rt_debug_item_order": (C.c_int, [C.c_int32] * 8 + [P(C.c_uint32), C.c_int64, P(C.c_int32)]),
         "rt_debug_scene_bound": (C.c_int, [P(rt_prim), C.c_int32, P(C.c_float), P(C.c_float), P(C.c_float)]),
+        "rt_debug_block_cull": (C.c_int, [P(rt_prim), C.c_int32, P(rt_camera)] + [C.c_int32] * 9 +
+                                [P(C.c_uint8), C.c_int64, P(C.c_int32)]),
         "rt_debug_ray_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
         "rt_debug_vn_rehit": (C.c_int, [P(C.c_double), P(C.c_double), P(C.c_double), C.c_int32, C.c_double,
                                         C.c_double, P(C.c_float), P(C.c_int32), P(C.c_double), P(C.c_double)]),
@@ -399,6 +401,32 @@ def scene_bound(prims: Sequence[rt_prim]) -> dict:
         _check(state)
     return {"lo": np.array(lo, np.float32), "hi": np.array(hi, np.float32), "limit": np.float32(info[0]),
             "pad": np.float32(info[1]), "state": int(state)}
+
+
+def block_cull(prims: Sequence[rt_prim], camera: rt_camera, size: Tuple[int, int],
+               window: Optional[Tuple[int, int, int, int]] = None,
+               bands: Optional[Tuple[int, int, int]] = None) -> Tuple[np.ndarray, int]:
+    """rt_debug_block_cull (host code, no GPU): the 8x8 pixel blocks of a brute-force launch that the path
+    kernels are not dealt, because no camera ray of their pixels can meet the scene bound.  size: the
+    frame; window = (x0, y0, w, h), default the frame; bands = (band, stride, offset): that band set of
+    the frame (window rows then count the set's rows, default all of them).  Returns the flags as a
+    bool array [block rows, blocks per row] (True = dead) and the number of live blocks."""
+    lib = load_library()
+    n = len(prims)
+    arr = (rt_prim * max(1, n))(*prims)
+    cam = rt_camera.from_buffer_copy(camera)
+    b = bands or (0, 0, 0)
+    W, H = size
+    rows = lib.rt_band_rows(H, b[0], b[1], b[2]) if bands else H
+    x0, y0, w, h = window or (0, 0, W, rows)
+    bx, by = (w + 7) // 8, (h + 7) // 8
+    dead = np.zeros(max(1, bx * by), np.uint8)
+    info = (C.c_int32 * 2)()
+    live = lib.rt_debug_block_cull(arr, n, C.byref(cam), W, H, x0, y0, w, h, b[0], b[1], b[2],
+                                   dead.ctypes.data_as(C.POINTER(C.c_uint8)), bx * by, info)
+    if live < 0:
+        _check(live)
+    return dead[:bx * by].reshape(by, bx).astype(bool), int(live)
 
 
 def ref_bvh_export(prims: Sequence[rt_prim]) -> Tuple[np.ndarray, np.ndarray, int, int]:
@@ -563,6 +591,11 @@ class GpuRaytracer:
 
     def set_traversal(self, traversal: int) -> None:
         _check(self.lib.rt_scene_set_traversal(self.handle, traversal))
+
+    def set_camera(self, camera: rt_camera) -> None:
+        """rt_scene_set_camera: the renders that follow use this camera (the frame size stays)."""
+        self.camera = rt_camera.from_buffer_copy(camera)
+        _check(self.lib.rt_scene_set_camera(self.handle, C.byref(self.camera)))
 
     def info(self) -> rt_scene_info:
         inf = rt_scene_info()

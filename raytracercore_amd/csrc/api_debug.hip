@@ -483,6 +483,42 @@ int rt_debug_scene_bound(const rt_prim* prims, int32_t n_prims, float* lo, float
     return b.empty ? 1 : (b.limit < 0.0f ? 2 : 0);
 }
 
+// Host only: the block cull run_path would plan a brute-force launch of this window with (block_cull.h).
+int rt_debug_block_cull(const rt_prim* prims, int32_t n_prims, const rt_camera* camera, int32_t width, int32_t height,
+                        int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t band, int32_t band_stride,
+                        int32_t band_offset, uint8_t* dead, int64_t cap, int32_t* info)
+{
+    const bool banded = band > 0;
+    if (n_prims < 0 || (n_prims > 0 && !prims) || !camera || width <= 0 || height <= 0 || w <= 0 || h <= 0 || x0 < 0 ||
+        y0 < 0 || x0 + w > width || cap < 0 || (cap > 0 && !dead) || band < 0 ||
+        (camera->kind != RT_CAMERA_FRUSTUM && camera->kind != RT_CAMERA_ORTHO) ||
+        (banded && (band_stride <= 0 || band_offset < 0 || band_offset >= band_stride)) || (!banded && y0 + h > height)) {
+        set_error("rt_debug_block_cull: bad argument");
+        return RT_ERR_ARG;
+    }
+    int n_planes = 0;
+    for (int i = 0; i < n_prims; i++) {
+        if (prims[i].kind < 0 || prims[i].kind > 2) {
+            set_error("rt_debug_block_cull: unknown primitive kind at index " + std::to_string(i));
+            return RT_ERR_ARG;
+        }
+        n_planes += prims[i].kind == RT_PRIM_PLANE ? 1 : 0;
+    }
+    const SceneBound b = make_scene_bound(prepare_prims(prims, n_prims));
+    CameraD camd;
+    CameraF camf;
+    camera_init(*camera, width, height, camd, camf);
+    const CullWindow win{x0, y0, w, h, banded ? band : 0, banded ? band_stride : 0, banded ? band_offset : 0};
+    std::vector<unsigned char> flags;
+    const int live = cull_blocks(camf, b, n_planes, win, flags);
+    for (size_t i = 0; i < flags.size() && (int64_t)i < cap; i++) dead[i] = flags[i];
+    if (info) {
+        info[0] = (w + 7) / 8;
+        info[1] = (h + 7) / 8;
+    }
+    return live;
+}
+
 int rt_parse_scene(const char* text, rt_scene_params* params, rt_prim* prims, int32_t* n_prims, rt_camera* cameras,
                    int32_t* n_cameras)
 {

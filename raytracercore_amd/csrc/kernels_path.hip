@@ -1229,15 +1229,21 @@ __device__ __forceinline__ unsigned lanes_below(unsigned long long m)
 }
 // A work item's pixel: item = ((block << log2_chunks) + chunk) * 64 + pixel of the 8x8 block, tile
 // coordinates (px, py), its chunk c, and its frame coordinates (fx, fy; a band set maps tile rows to
-// frame rows).
-template <class ParT>
+// frame rows).  TABLE (the brute-force kernels' item open): a launch over the live blocks alone
+// (PathParams::cull) reads the block's coordinates from its table, one 4-B load beside the pixel
+// key's; the branch is wave-uniform.  Every other caller decodes launches that are never culled.
+template <bool TABLE = false, class ParT>
 __device__ __forceinline__ void item_pixel(unsigned item, const ParT& p, int& px, int& py, int& c, int& fx, int& fy)
 {
     const unsigned q = item & 63u, t = item >> 6;
     c = (int)(t & (unsigned)(p.n_chunks - 1));
     unsigned by, bx;
     const unsigned blk = t >> p.log2_chunks;
-    if (p.magic_bx != 0) { // multiply-high division (exact here, make_params checks)
+    if (TABLE && p.cull != nullptr) {
+        const unsigned v = p.cull[kCullTable + blk];
+        bx = v & 0xFFFFu;
+        by = v >> 16;
+    } else if (p.magic_bx != 0) { // multiply-high division (exact here, make_params checks)
         by = __umulhi(blk, p.magic_bx);
         bx = blk - by * (unsigned)p.blocks_x;
     } else {
@@ -1391,7 +1397,7 @@ __device__ __forceinline__ void refill(Lane& L, Sample& S, const ParT& p, const 
                 }
             } else {
                 int px, py, c, fx, fy;
-                item_pixel(L.item, p, px, py, c, fx, fy);
+                item_pixel<!NT>(L.item, p, px, py, c, fx, fy);
                 if (px < p.w && py < p.h && c * p.chunk < p.spp) {
                     L.item_open = true;
                     const int s0 = c * p.chunk;
@@ -1667,6 +1673,10 @@ __device__ __forceinline__ void path_body(const CameraF* __restrict__ camp, cons
             cnt.iters++;
         }
     }
+    // a culled launch (PathParams::cull): the first wave of block 0 adds the primary rays of the dead
+    // blocks' pixels, spp each, which no item stands for
+    if (!STATS && !RAYS && P0.cull != nullptr && blockIdx.x == 0 && threadIdx.x < 64)
+        wave_rays += ((unsigned long long)P0.cull[0] | (unsigned long long)P0.cull[1] << 32) * (unsigned long long)P0.spp;
     flush_counts<STATS>(wave_rays, cnt, *(const ParamsC*)pp, lane);
 }
 
@@ -2391,9 +2401,17 @@ __global__ void accumulate_kernel(PathParams p, double* sum, uint32_t* samples, 
     const int x = blockIdx.x * 16 + (threadIdx.x & 15);
     const int y = blockIdx.y * 16 + (threadIdx.x >> 4);
     if (x >= p.w || y >= p.h) return;
-    const size_t blk = (size_t)((y >> 3) * p.blocks_x + (x >> 3));
+    size_t blk = (size_t)((y >> 3) * p.blocks_x + (x >> 3));
     const int q = (y & 7) * 8 + (x & 7);
     const size_t i = (size_t)y * p.w + x;
+    if (p.cull) { // a launch over the live blocks: a dead block's pixels are spp primary misses, their sums stay
+        const int live = (int)p.cull[kCullTable + (p.n_pad >> 6) + blk];
+        if (live < 0) {
+            misses[i] += (uint32_t)p.spp;
+            return;
+        }
+        blk = (size_t)live;
+    }
     double r = sum[i], g = sum[plane + i], bl = sum[2 * plane + i];
     uint32_t ns = 0, nm = 0;
     const int used = (p.spp + p.chunk - 1) / p.chunk; // chunks past spp hold no partial
@@ -2499,8 +2517,10 @@ __global__ void colors_1spp_kernel(PathParams p, float* __restrict__ out)
     const size_t o = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (o >= npix) return;
     const int x = (int)(o / (size_t)p.h), y = (int)(o - (size_t)x * p.h);
-    const int q = ((y >> 3) * p.blocks_x + (x >> 3)) * 64 + (y & 7) * 8 + (x & 7); // 1 spp: one chunk
-    const float4 v = p.partial[q];
+    int blk = (y >> 3) * p.blocks_x + (x >> 3);
+    if (p.cull) blk = (int)p.cull[kCullTable + (p.n_pad >> 6) + blk]; // live number, or -1: a dead block, a miss
+    const int q = (blk < 0 ? 0 : blk) * 64 + (y & 7) * 8 + (x & 7); // 1 spp: one chunk
+    const float4 v = blk < 0 ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : p.partial[q];
     const bool miss = (__float_as_uint(v.w) & 0xFFFFu) == 0;
     out[3 * o + 0] = miss ? -1.0f : v.x;
     out[3 * o + 1] = miss ? -1.0f : v.y;

@@ -58,6 +58,21 @@ void set_item_order(PathParams& p)
     }
 }
 
+// The launch's blocks, item ranges and tickets for n_blocks 8x8 blocks numbered 0 .. n_blocks - 1:
+// the window's own (make_params_for), or the live blocks of a culled launch (run_path, block_cull.h),
+// whose chunks, samples per item and pool stay the window's, so that an item holds the same samples.
+void set_blocks(PathParams& p, int n_blocks)
+{
+    p.n_pad = n_blocks * 64;
+    p.n_split = 1;
+    int want = kMaxSplit;
+    if (const char* e = getenv("RTCORE_XCD_SPLIT")) want = atoi(e) > 0 ? kMaxSplit : 1;
+    if (want > 1 && n_blocks >= 4 * kMaxSplit) p.n_split = kMaxSplit;
+    for (int g = 0; g <= p.n_split; g++)
+        p.split_start[g] = (unsigned)((int64_t)n_blocks * g / p.n_split) * (unsigned)(p.n_chunks * 64);
+    set_item_order(p);
+}
+
 // chunk_npix (default w * h): the pixel count the chunks per pixel are chosen for.  A column band of a
 // tile passes the whole tile's, so that every pixel's samples fall into the same chunks (and its
 // fp64 sum into the same order) as in one launch over the tile.
@@ -164,14 +179,7 @@ PathParams make_params_for(int kernel, int chunks_over, int pool_over, int x0, i
     // on neighbouring pixels and their closest-hit queries share that XCD's L2.  A single range hands
     // the whole frame out in order to all XCDs at once: every L2 then holds the nodes of the same
     // band.  RTCORE_XCD_SPLIT=0 turns it off (A/B).
-    p.n_split = 1;
-    const int n_blocks = p.n_pad / 64;
-    int want = kMaxSplit;
-    if (const char* e = getenv("RTCORE_XCD_SPLIT")) want = atoi(e) > 0 ? kMaxSplit : 1;
-    if (want > 1 && n_blocks >= 4 * kMaxSplit) p.n_split = kMaxSplit;
-    for (int g = 0; g <= p.n_split; g++)
-        p.split_start[g] = (unsigned)((int64_t)n_blocks * g / p.n_split) * (unsigned)(p.n_chunks * 64);
-    set_item_order(p);
+    set_blocks(p, p.n_pad / 64);
     p.seed = seed;
     p.seed_key = rt_rng_seed_key(seed);
     p.sample_base = base;

@@ -17,6 +17,8 @@ PathParams make_params_rays(int kernel, int64_t n, int spp, uint64_t seed, uint6
 int64_t render_rays_max_n(int kernel, int spp);
 // The order in which the dispensers deal p's work items, from p's chunks, pool and ranges.
 void set_item_order(PathParams& p);
+// Plans p's item ranges and tickets (set_item_order) over n_blocks blocks; p.n_pad = 64 n_blocks.
+void set_blocks(PathParams& p, int n_blocks);
 // Band-set launch: tile row r is frame row ((r / band) * stride + offset) * band + r % band.
 void set_band(PathParams& p, int band, int stride, int offset);
 // Every ticket of p's dispensers through ticket_items, as (range, first item, items) triples into

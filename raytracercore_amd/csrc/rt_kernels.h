@@ -96,7 +96,17 @@ struct PathParams {
     unsigned long long stream_base;
     int scene_bound;            // flat brute-force kernel: 1 = a wave of camera rays that all miss the scene bound
                                 // skips its query (RTCORE_SCENE_BOUND, make_params_for)
+    // The block cull (block_cull.h, run_path): null, or a device record of the launch's 8x8 blocks whose
+    // pixels can see the scene.  The launch is then planned over those live blocks alone, numbered
+    // 0 .. n_live - 1 in their original order (n_pad = 64 n_live; blocks_x stays the window's):
+    //   words 0-1  the real pixels of the dead blocks (64 bits; each stands for spp primary misses and rays)
+    //   word  2-3  n_live, blocks of the window
+    //   kCullTable + i             live block i -> bx | by << 16
+    //   kCullTable + n_live + b    window block b = by * blocks_x + bx -> its live number, or -1
+    // One field (last, so that no other moves): the BVH kernels take this record by value.
+    const unsigned int* cull;
 };
+constexpr int kCullTable = 4;  // first table word of PathParams::cull
 constexpr int kRecRows = 6;    // sizeof(rt_debug_ray) / 16
 
 // Ticket t of item range g -> the items it covers, [first, first + len) in the item numbering

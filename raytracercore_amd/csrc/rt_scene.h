@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "block_cull.h"
 #include "host_scene.h"
 #include "launch_params.h"
 #include "rt_jit.h"
@@ -219,6 +220,26 @@ struct rt_scene {
     PathParams* params_h = nullptr;
     std::array<hipEvent_t, kParamRing> slot_ev{};
     unsigned params_next = 0;
+    // The block cull's records (PathParams::cull, plan_block_cull), cached by what they depend on: the
+    // camera (cam_gen, bumped by rt_scene_set_camera), the window and the band set; the frame size
+    // and the bound are the scene's.  A few entries, least recently used replaced, so that a host
+    // which alternates among a few windows (rt_render_tile's column bands) builds each once.  An
+    // entry is built in its pinned words and uploaded stream-ordered; `up` (recorded after the
+    // upload) guards the pinned words against the next rebuild.
+    struct CullEntry {
+        bool valid = false;
+        unsigned cam_gen = 0;
+        CullWindow win{};
+        int n_live = 0, n_blocks = 0;
+        uint64_t dead_px = 0, used = 0;
+        DevBuf<unsigned int> dev;
+        HostBuf<unsigned int> host;
+        hipEvent_t up = nullptr;
+    };
+    static constexpr int kCullEntries = 4;
+    std::array<CullEntry, kCullEntries> cull_cache;
+    uint64_t cull_clock = 0;
+    unsigned cam_gen = 0;
     bool has_camera = false;
     bool flat_overflow = false; // the flat brute-force order exceeds GroupRec's counts (BruteOrder::overflow)
     hipStream_t stream = nullptr;
@@ -241,6 +262,8 @@ struct rt_scene {
         for (hipEvent_t e : slot_ev)
             if (e) (void)hipEventDestroy(e);
         if (done_ev) (void)hipEventDestroy(done_ev);
+        for (CullEntry& c : cull_cache)
+            if (c.up) (void)hipEventDestroy(c.up);
         for (hipEvent_t e : copy_ev)
             if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : band_ev)

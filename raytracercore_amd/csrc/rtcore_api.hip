@@ -164,6 +164,7 @@ int rt_scene_set_camera(rt_scene* s, const rt_camera* cam)
         s->grouped_h.groups = g; // the order the scene-specialised grouped kernel is built with
     }
     s->has_camera = true;
+    s->cam_gen++; // the block cull's records are per camera
     s->jit_gen++; // the scene-specialised kernel carries the camera (and the group order)
     const int rc = calibrate_grouping(s);
     if (rc == RT_OK) (void)prepare_jit(s); // build the scene-specialised kernel now, not in a launch

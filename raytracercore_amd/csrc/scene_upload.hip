@@ -608,9 +608,100 @@ int upload_params(rt_scene* s, const PathParams& p, hipStream_t stream, const Pa
     return RT_OK;
 }
 
+// The block cull of a brute-force launch (block_cull.h): the record of p's window for the current
+// camera from the scene's cache, built on a miss.  ent: the record to launch with, or null when the
+// launch runs whole (the cull is off, or no block is dead); fresh: its words are new and still to be
+// uploaded (run_path does that on the launch stream).  Camera and bound stay the same from launch to
+// launch in real use -- a progressive render repeats one camera until the user moves it -- so the
+// proof is done once per camera and window and a steady launch pays a cache lookup.
+// Off for the instrumented and tracing instances, whose counters and records keep their meaning
+// (rt_render_rays has a launcher of its own and never comes here), and below kCullMinBlocks blocks,
+// so that a host which renders many small tiles (rt_render_tile per 64 x 64 tile) does not build a
+// table per call: the build takes 12 ns per block on the host (0.39 ms for a 1080p frame, 0.09 ms for
+// 4096 blocks, profiles/block_cull/README.md), once per camera and window; 4096 blocks (512 x 512
+// pixels) is the size from which one of rt_render_tile's four column bands of a 1080p frame (8100
+// blocks) and every larger launch is culled.  Read per launch, like RTCORE_SCENE_BOUND:
+// RTCORE_BLOCK_CULL=0 turns it off, RTCORE_BLOCK_CULL_MIN=<blocks> sets the threshold.
+constexpr int kCullMinBlocks = 4096;
+static int plan_block_cull(rt_scene* s, const PathParams& p, rt_scene::CullEntry*& ent, bool& fresh)
+{
+    ent = nullptr;
+    fresh = false;
+    if ((s->variant >> 1) >= 2 || s->stats_on || s->tracing) return RT_OK;
+    if (const char* e = getenv("RTCORE_BLOCK_CULL"))
+        if (atoi(e) == 0) return RT_OK;
+    int min_blocks = kCullMinBlocks;
+    if (const char* e = getenv("RTCORE_BLOCK_CULL_MIN")) min_blocks = std::max(1, atoi(e));
+    const int n_blocks = p.n_pad / 64;
+    if (n_blocks < min_blocks || p.blocks_x > 0xFFFF || n_blocks / p.blocks_x > 0xFFFF) return RT_OK; // (16-bit bx, by)
+    const CullWindow win{p.x0, p.y0, p.w, p.h, p.band > 0 ? p.band : 0, p.band > 0 ? p.band_stride : 0,
+                         p.band > 0 ? p.band_offset : 0};
+    auto same = [](const CullWindow& a, const CullWindow& b) {
+        return a.x0 == b.x0 && a.y0 == b.y0 && a.w == b.w && a.h == b.h && a.band == b.band &&
+               a.band_stride == b.band_stride && a.band_offset == b.band_offset;
+    };
+    rt_scene::CullEntry* c = nullptr;
+    for (rt_scene::CullEntry& e : s->cull_cache)
+        if (e.valid && e.cam_gen == s->cam_gen && same(e.win, win)) c = &e;
+    if (!c) {
+        // replaced: an unused entry or one of an earlier camera first, else the least recently used
+        auto age = [&](const rt_scene::CullEntry& e) { return e.valid && e.cam_gen == s->cam_gen ? e.used : 0; };
+        c = &s->cull_cache[0];
+        for (rt_scene::CullEntry& e : s->cull_cache)
+            if (age(e) < age(*c)) c = &e;
+        c->valid = false;
+        if (c->up) HIP_TRY(hipEventSynchronize(c->up)); // the previous upload has read the pinned words
+        else HIP_TRY(hipEventCreateWithFlags(&c->up, hipEventDisableTiming));
+        std::vector<unsigned char> dead;
+        c->n_live = cull_blocks(s->camf, s->dev.bound, s->dev.n_pln, win, dead);
+        c->n_blocks = n_blocks;
+        c->dead_px = dead_pixels(win, dead);
+        c->cam_gen = s->cam_gen;
+        c->win = win;
+        if (c->n_live < n_blocks) {
+            const size_t words = (size_t)kCullTable + (size_t)c->n_live + (size_t)n_blocks;
+            HIP_TRY(c->host.reserve(words));
+            HIP_TRY(c->dev.reserve(words));
+            unsigned int* h = c->host.p;
+            h[0] = (unsigned)(c->dead_px & 0xFFFFFFFFull);
+            h[1] = (unsigned)(c->dead_px >> 32);
+            h[2] = (unsigned)c->n_live;
+            h[3] = (unsigned)n_blocks;
+            unsigned live = 0;
+            for (int b = 0; b < n_blocks; b++) {
+                if (!dead[(size_t)b]) h[kCullTable + live] = (unsigned)(b % p.blocks_x) | (unsigned)(b / p.blocks_x) << 16;
+                h[kCullTable + c->n_live + b] = dead[(size_t)b] ? 0xFFFFFFFFu : live;
+                live += dead[(size_t)b] ? 0u : 1u;
+            }
+            fresh = true; // valid once the upload is queued (run_path)
+        } else {
+            c->valid = true; // nothing to cull for this camera and window: remembered, never launched with
+        }
+    }
+    c->used = ++s->cull_clock;
+    if (c->n_live < c->n_blocks) ent = c;
+    return RT_OK;
+}
+
 // Launch the path kernel for p (work buffers sized here), timing it with the scene's events.
 int run_path(rt_scene* s, PathParams& p, unsigned long long* d_rays, hipStream_t stream, bool timed)
 {
+    // A brute-force launch is planned over the blocks that can see the scene (block_cull.h): tickets,
+    // item ranges, n_pad, the item total and the partial buffer over the n_live live blocks in their
+    // original order.  Chunks, samples per item and pool stay the window's, so an item holds the same
+    // samples, its fp32 partial has the same bits and the fixed-order fold gives the same fp64 sums;
+    // the kernels that fold the partials (accumulate_kernel, colors_1spp_kernel) count a dead block's
+    // pixels as spp primary misses, and the path kernel adds their rays (path_body).  The kernel is
+    // launched even when no block is live, so rt_kernel_times keeps one event pair per launch.
+    rt_scene::CullEntry* cull = nullptr;
+    bool cull_fresh = false;
+    p.cull = nullptr;
+    const int crc = plan_block_cull(s, p, cull, cull_fresh);
+    if (crc != RT_OK) return crc;
+    if (cull) {
+        set_blocks(p, cull->n_live);
+        p.cull = cull->dev.p;
+    }
     const size_t need = (size_t)p.n_chunks * (size_t)p.n_pad;
     // 32-bit item indices: the end-of-work sentinel is `need` itself and a pool's end is at most
     // p.pool past it.  The dispensers count tickets, one per >= 64 items, and every wave draws once
@@ -635,6 +726,12 @@ int run_path(rt_scene* s, PathParams& p, unsigned long long* d_rays, hipStream_t
     if (p.ray_log) s->ray_log = nullptr;
     // order after the previous operation when it ran on another stream (shared scratch)
     if (s->any_op && stream != s->last_stream) HIP_TRY(hipStreamWaitEvent(stream, s->done_ev, 0));
+    if (cull && cull_fresh) { // a new record: after the operations that read the entry's previous one
+        const size_t words = (size_t)kCullTable + (size_t)cull->n_live + (size_t)cull->n_blocks;
+        HIP_TRY(hipMemcpyAsync(cull->dev.p, cull->host.p, words * sizeof(unsigned int), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipEventRecord(cull->up, stream));
+        cull->valid = true;
+    }
     HIP_TRY(hipMemsetAsync(p.counter, 0, sizeof(unsigned int) * kSplitStride * p.n_split, stream));
     int grid = s->n_cu * (s->stats_on ? s->stats_blocks_per_cu : s->blocks_per_cu);
     p.stack_ovf = nullptr;
@@ -654,7 +751,8 @@ int run_path(rt_scene* s, PathParams& p, unsigned long long* d_rays, hipStream_t
     // renders an item never changes what it computes.  RTCORE_GRID_BPC caps it (tuning).
     if ((s->variant >> 1) < 2 && !s->stats_on) {
         constexpr double kSamplesPerLane = 6.0;
-        const double samples = (double)p.w * (double)p.h * (double)p.spp;
+        // (a culled launch: the samples of the live blocks' pixels)
+        const double samples = ((double)p.w * (double)p.h - (cull ? (double)cull->dead_px : 0.0)) * (double)p.spp;
         int cap = (int)std::ceil(samples / ((double)s->n_cu * 256.0 * kSamplesPerLane));
         if (const char* e = getenv("RTCORE_GRID_BPC")) cap = atoi(e);
         cap = std::max(1, cap);
