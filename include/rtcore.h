@@ -47,7 +47,8 @@ extern "C" {
                                    detects them by symbol; so were rt_select_pixels, rt_select_pixels_device,
                                    rt_select_rays, rt_select_rays_device and rt_debug_select_rays, and
                                    rt_render_rays and rt_render_rays_device, and rt_occluded_rays and
-                                   rt_occluded_rays_device */
+                                   rt_occluded_rays_device, and rt_render_pixels, rt_render_pixels_device,
+                                   rt_adaptive_select_device and rt_debug_adaptive_select */
 
 typedef enum rt_status {
     RT_OK = 0,
@@ -252,6 +253,10 @@ int rt_debug_brute_layout(const rt_prim* prims, int32_t n_prims, int32_t* out, i
    also deals the empty chunk slots (A/B). */
 int rt_debug_item_order(int32_t w, int32_t h, int32_t spp, int32_t chunks, int32_t pool, int32_t band,
                         int32_t band_stride, int32_t band_offset, uint32_t* out, int64_t cap_words, int32_t* info);
+/* Host only (no device needed): how rt_render_pixels plans a list of n entries at spp samples per pixel
+   for kernel 0 (BRUTE), 1 (GROUPED) or 3 (BVH): info[0..3] = {chunk slots per entry, samples per work
+   item, work items per entry that hold samples, blocks of 64 entries}. */
+int rt_debug_pixels_plan(int32_t kernel, int64_t n, int32_t spp, int32_t* info);
 /* Host only (no device needed): the scene bound of these primitives -- the padded fp32 box over every
    primitive but the planes that the flat brute-force path kernel tests a wave of camera rays against, to
    skip the query of a wave that looks past the scene (RTCORE_SCENE_BOUND=0 turns the skip off).
@@ -624,6 +629,112 @@ int rt_render_rays(rt_scene* scene, const rt_ray* rays, int64_t n, int32_t spp, 
 int rt_render_rays_device(rt_scene* scene, const rt_ray* d_rays, int64_t n, int32_t spp, uint64_t seed,
                           uint64_t sample_base, uint64_t stream_base, double* d_sum, uint32_t* d_samples,
                           uint32_t* d_misses, unsigned long long* d_rays_count, void* stream);
+
+/* ----------------------------------------------------------- adaptive sampling --- */
+/*
+ * rt_render_pixels / rt_render_pixels_device: spp of the camera's own samples, exactly as a tile render
+ * draws them, for a list of frame pixels, added into whole-frame accumulators; optionally two more
+ * accumulators from which a per-pixel standard error follows.  rt_adaptive_select_device turns such
+ * accumulators into the next pixel list on the device, so a "render until the noise is below x" loop
+ * runs without the image leaving device memory.
+ *
+ * A list entry is the frame pixel index fy * width + fx (the number rt_rng_pixel_key is keyed by).
+ * The path kernels run in the scene's traversal mode (BRUTE, GROUPED or BVH with either builder;
+ * RT_ERR_STATE on a BVH2 scene, as rt_render_rays), always the generic kernels, whatever rt_set_jit says.
+ *
+ * What is promised (normative):
+ *   - Sample k of a listed pixel is the sample rt_render_tile_1spp(seed, sample_base + k) returns for
+ *     it, bit for bit, in the scene's traversal mode: the stream rt_rng_init(seed, pixel, sample_base + k)
+ *     with nothing discarded (GetCameraRay's two draws are used, then the depth-of-field and bounce draws).
+ *   - A pixel's result depends on (seed, pixel, the sample indices, the traversal mode) only: not on n,
+ *     on the pixel's place in the list or on the host entry's chunking.  The samples per work item are
+ *     s = min(64, ceil(spp / B)), B = 24 (BRUTE, GROUPED) or 64 (BVH), a function of spp alone; an
+ *     item's samples are summed in fp32 in sample order and the items folded into fp64 in sample order.
+ *   - The sums equal rt_render_device's bit for bit from equal accumulator contents wherever that
+ *     launch puts the same samples into an item: any window of at most 1920 x 1080 pixels at spp <= B,
+ *     and a window of exactly 2,073,600 pixels at any spp.
+ *   - rays_out / d_rays count the Scene.RayTrace equivalents in rt_render_tile's unit (added to).
+ *   - Coherence: entries 64 j .. 64 j + 63 share a wave for every sample, so list neighbouring pixels
+ *     next to each other; rt_adaptive_select_device's order does.
+ *
+ * The moments.  With q and batches (both or neither, else RT_ERR_ARG) every work item j of a pixel with
+ * t_j = samples + misses > 0 finished samples is one batch: with Y_j = 0.299 r + 0.587 g + 0.114 b of
+ * the item's fp32 colour sums (DoubleColor.GetLuminance, DoubleColor.cs:76-79, in fp64, left to right,
+ * each operation rounded on its own; a miss counts as luminance 0),
+ *     q[pixel] += sum over the call's batches of Y_j * Y_j / t_j        batches[pixel] += their number
+ * (the call's terms are summed in item order and added to q once).  The estimate these give:
+ *     N = samples + misses,  Y = 0.299 sum.r + 0.587 sum.g + 0.114 sum.b,  J = batches,  Q = q
+ *     variance per sample  s2 = max(0, (Q - Y * Y / N) / (J - 1))    for J >= 2
+ *     standard error of the pixel's mean luminance  se = sqrt(s2 / N)
+ * Batches of unequal size keep it unbiased: E[sum Y_j^2 / t_j] - E[Y^2 / N] = (J - 1) s2.  Up to spp = B
+ * per call every batch is one sample and s2 is the plain sample variance.  It adds over calls, over
+ * sample_base ranges and over GPUs.
+ *
+ * rt_render_pixels (host): whole-frame caller buffers in the x * height + y order, everything added to,
+ * every pixel not in the list untouched (rt_render_bands' contract with a list in the band set's
+ * place).  q and batches may both be NULL.  Synchronous, on the scene's own stream; any n, in chunks of
+ * at most 2^19 entries (RTCORE_QUERY_CHUNK; fewer where spp makes a chunk's items pass 2^26), two of
+ * them resident, uploads and downloads overlapping the kernels as in rt_render_rays: 4 B up and one
+ * 48-B record down per entry.  RT_ERR_ARG also for an entry >= width * height and for a pixel named twice
+ * (checked with a bitmap of the frame before anything is launched).
+ * rt_render_pixels_device: accumulators in rt_render_device's layout over the whole frame, index
+ * y * width + x, planes `plane` elements apart (0 = width * height).  Asynchronous on `stream`, ordered
+ * like the device-resident renders; one launch, RT_ERR_ARG for n above rt_render_rays_device's bound at
+ * this spp.  An entry outside the frame is skipped: not traced, nothing written.  A pixel named twice
+ * is undefined (its accumulators are updated by two threads).
+ *
+ * Errors, before anything is launched: RT_ERR_ARG for a null scene, a null list or sum, samples or
+ * misses pointer, only one of q / batches, n < 0, spp <= 0, a frame of 2^32 pixels or more or of more
+ * than 2^20 rows; RT_ERR_STATE without a camera and on a BVH2 scene.  n == 0 returns RT_OK and touches
+ * nothing.  The counters of rt_scene_get_stats, an armed rt_debug_ray_log, rt_kernel_times and the
+ * scene-specialised kernels are left as they were.
+ */
+int rt_render_pixels(rt_scene* scene, const uint32_t* pixels, int64_t n, int32_t spp, uint64_t seed, uint64_t sample_base,
+                     rt_color* sum_rgb, uint32_t* samples, uint32_t* misses, double* q, uint32_t* batches,
+                     uint64_t* rays_out);
+int rt_render_pixels_device(rt_scene* scene, const uint32_t* d_pixels, int64_t n, int32_t spp, uint64_t seed,
+                            uint64_t sample_base, double* d_sum, uint32_t* d_samples, uint32_t* d_misses, double* d_q,
+                            uint32_t* d_batches, uint64_t plane, unsigned long long* d_rays, void* stream);
+
+/*
+ * The selection rule.  With N, Y, Q, J of a pixel as above, active(N, Y, Q, J) is, in this order:
+ *   1. N < min_samples   -> 1
+ *   2. N >= max_samples  -> 0
+ *   3. J < 2             -> 1
+ *   4. otherwise  se > rel_tol * max(Y / N, lum_floor)
+ * A NaN in an accumulator makes step 4's comparison false: the pixel is inactive (it cannot converge,
+ * so it is not sampled for ever).  An all-miss pixel (Y = Q = 0) has se = 0 and stops at min_samples.
+ */
+typedef struct rt_adaptive_params {   /* 32 B */
+    double   rel_tol;      /* converged when se <= rel_tol * max(Y / N, lum_floor)          */
+    double   lum_floor;    /* > 0; keeps black pixels from never converging                 */
+    uint32_t min_samples;  /* a pixel with N < min_samples is always active                 */
+    uint32_t max_samples;  /* a pixel with N >= max_samples is never active                 */
+    uint32_t reserved[2];  /* 0 */
+} rt_adaptive_params;
+/*
+ * rt_adaptive_select_device: the active pixels' frame indices into d_pixels, from accumulators in
+ * rt_render_pixels_device's layout (planes `plane` apart, 0 = width * height), on the calling thread's
+ * current device (as rt_tonemap_device), asynchronous on `stream`.  The order is normative: by 8 x 8
+ * block of the frame, blocks row-major; within a block by (y & 7) * 8 + (x & 7), the path kernels' own
+ * pixel order, so 64 consecutive entries are a few neighbouring blocks.  *d_count receives the number
+ * of active pixels, also when it exceeds cap; then only the first cap are stored.  Deterministic: a
+ * count per block (one wave per block, ballot), an exclusive scan over the block counts, the write
+ * by ballot prefix; no atomic decides a position.  The temporary block counts are the library's own,
+ * per device; calls on one device are serialised by the caller.  RT_ERR_ARG for a null pointer (d_pixels
+ * may be NULL with cap = 0), rel_tol or lum_floor NaN or negative, lum_floor == 0, a frame of no pixels
+ * or of 2^32 or more.
+ * rt_debug_adaptive_select: the host twin (host only, no device needed): the same arguments on host
+ * arrays in the same layout, the same rule function, the same order; returns the count (at most cap
+ * entries stored), or a negative rt_status.
+ */
+int rt_adaptive_select_device(const rt_adaptive_params* params, const double* d_sum, const uint32_t* d_samples,
+                              const uint32_t* d_misses, const double* d_q, const uint32_t* d_batches, uint64_t plane,
+                              int32_t width, int32_t height, uint32_t* d_pixels, uint32_t cap, uint32_t* d_count,
+                              void* stream);
+int64_t rt_debug_adaptive_select(const rt_adaptive_params* params, const double* sum, const uint32_t* samples,
+                                 const uint32_t* misses, const double* q, const uint32_t* batches, uint64_t plane,
+                                 int32_t width, int32_t height, uint32_t* pixels, uint32_t cap);
 
 /* Device-side DebugRaycaster Primitives pass: d_ids[y*w + x].  Asynchronous. */
 int rt_primary_ids_device(rt_scene* scene, int32_t x0, int32_t y0, int32_t w, int32_t h,

@@ -157,6 +157,12 @@ class rt_selection(C.Structure):
     _fields_ = [("item", C.c_int32), ("reserved", C.c_int32), ("distance", C.c_double)]
 
 
+class rt_adaptive_params(C.Structure):
+    """The selection rule of adaptive sampling (rt_adaptive_select_device), 32 B."""
+    _fields_ = [("rel_tol", C.c_double), ("lum_floor", C.c_double), ("min_samples", C.c_uint32),
+                ("max_samples", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 SELECT_ITEM_DTYPE = np.dtype([("kind", np.int32), ("index", np.int32)])
 SELECTION_DTYPE = np.dtype([("item", np.int32), ("reserved", np.int32), ("distance", np.float64)])
 
@@ -171,7 +177,8 @@ HIT_DTYPE = np.dtype([
 # named by RTCORE_LIB may not)
 _OPTIONAL = ("rt_query_rays", "rt_query_rays_device", "rt_camera_rays", "rt_select_pixels", "rt_select_pixels_device",
              "rt_select_rays", "rt_select_rays_device", "rt_render_rays", "rt_render_rays_device",
-             "rt_occluded_rays", "rt_occluded_rays_device")
+             "rt_occluded_rays", "rt_occluded_rays_device", "rt_render_pixels", "rt_render_pixels_device",
+             "rt_adaptive_select_device")
 
 _lib: Optional[C.CDLL] = None
 
@@ -280,6 +287,16 @@ def load_library(path: str = "") -> C.CDLL:
         "rt_occluded_rays": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
         "rt_occluded_rays_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                               C.c_void_p]),
+        "rt_render_pixels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64,
+                                       P(rt_color), P(C.c_uint32), P(C.c_uint32), P(C.c_double), P(C.c_uint32),
+                                       P(C.c_uint64)]),
+        "rt_render_pixels_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64] +
+                                    [C.c_void_p] * 5 + [C.c_uint64, C.c_void_p, C.c_void_p]),
+        "rt_adaptive_select_device": (C.c_int, [P(rt_adaptive_params)] + [C.c_void_p] * 5 + [C.c_uint64, C.c_int32,
+                                                C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+        "rt_debug_adaptive_select": (C.c_int64, [P(rt_adaptive_params)] + [C.c_void_p] * 5 + [C.c_uint64, C.c_int32,
+                                                 C.c_int32, C.c_void_p, C.c_uint32]),
+        "rt_debug_pixels_plan": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, P(C.c_int32)]),
     }
     for name, (res, args) in sig.items():
         if (name.startswith("rt_debug_") or name in _OPTIONAL) and not hasattr(lib, name):
@@ -795,6 +812,112 @@ class GpuRaytracer:
                                               stream_base, C.c_void_p(d_sum), C.c_void_p(d_samples),
                                               C.c_void_p(d_misses), C.c_void_p(d_rays), C.c_void_p(stream)))
 
+    def _pixel_list(self, pixels) -> np.ndarray:
+        p = np.asarray(pixels)
+        if p.ndim == 2 and p.shape[1] == 2:  # (x, y) pairs
+            p = p[:, 1].astype(np.int64) * self.width + p[:, 0].astype(np.int64)
+        p = p.reshape(-1)
+        if p.size and (p.min() < 0 or p.max() >= 1 << 32):
+            raise ValueError("pixel indices must lie in [0, 2^32)")
+        return np.ascontiguousarray(p, np.uint32)
+
+    def render_pixels(self, pixels, spp: int, seed: int = 0, sample_base: int = 0, out=None, moments: bool = False):
+        """rt_render_pixels: spp of the camera's own samples (those a tile render draws, sample indices
+        sample_base ..) for a list of frame pixels, given as frame indices y * width + x or as an (n, 2)
+        array of (x, y).  Whole-frame arrays in render_tile's [x, y] shape, added to: new zeroed arrays, or
+        the caller's `out` = (sum, samples, misses), with moments (sum, samples, misses, q, batches).
+        Returns (sum[W,H,3] f64, samples[W,H] u32, misses[W,H] u32, rays), with moments
+        (sum, samples, misses, rays, q[W,H] f64, batches[W,H] u32): the standard error of a pixel's mean
+        luminance follows from them (pixel_standard_error)."""
+        W, H = self.width, self.height
+        px = self._pixel_list(pixels)
+        if out is None:
+            out = (np.zeros((W, H, 3), np.float64), np.zeros((W, H), np.uint32), np.zeros((W, H), np.uint32))
+            if moments:
+                out += (np.zeros((W, H), np.float64), np.zeros((W, H), np.uint32))
+        if len(out) != (5 if moments else 3):
+            raise ValueError("out must be (sum, samples, misses), with moments (sum, samples, misses, q, batches)")
+        shapes = (((W, H, 3), np.float64), ((W, H), np.uint32), ((W, H), np.uint32), ((W, H), np.float64), ((W, H), np.uint32))
+        for a, (shape, dt) in zip(out, shapes):
+            if a.shape != shape or a.dtype != dt or not a.flags.c_contiguous:
+                raise ValueError("out must be C-contiguous whole-frame arrays (sum f64 [W, H, 3], samples, misses, "
+                                 "batches u32 [W, H], q f64 [W, H])")
+        s, ns, ms = out[:3]
+        q = out[3].ctypes.data_as(C.POINTER(C.c_double)) if moments else None
+        b = out[4].ctypes.data_as(C.POINTER(C.c_uint32)) if moments else None
+        count = C.c_uint64(0)
+        _check(self.lib.rt_render_pixels(self.handle, px.ctypes.data_as(C.c_void_p), px.size, spp, seed, sample_base,
+                                         s.ctypes.data_as(C.POINTER(rt_color)), ns.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                         ms.ctypes.data_as(C.POINTER(C.c_uint32)), q, b, C.byref(count)))
+        return (s, ns, ms, count.value) + tuple(out[3:])
+
+    def render_pixels_device(self, d_pixels: int, n: int, spp: int, seed: int, sample_base: int, d_sum: int,
+                             d_samples: int, d_misses: int, d_q: int = 0, d_batches: int = 0, plane: int = 0,
+                             d_rays: int = 0, stream: int = 0) -> None:
+        """rt_render_pixels_device: asynchronous render of the n frame pixels listed (uint32 frame indices) at
+        device pointer d_pixels into whole-frame device accumulators in render_device's layout (index
+        y * width + x; d_sum planes R | G | B `plane` doubles apart, 0 = width * height; d_q, d_batches both
+        or 0; d_rays one uint64 ray counter or 0) on `stream`."""
+        _check(self.lib.rt_render_pixels_device(self.handle, C.c_void_p(d_pixels), n, spp, seed, sample_base,
+                                                C.c_void_p(d_sum), C.c_void_p(d_samples), C.c_void_p(d_misses),
+                                                C.c_void_p(d_q), C.c_void_p(d_batches), plane, C.c_void_p(d_rays),
+                                                C.c_void_p(stream)))
+
+    def render_adaptive(self, rel_tol: float, min_spp: int, max_spp: int, batch_spp: int, seed: int = 0,
+                        lum_floor: float = 1e-3):
+        """Render until every pixel's standard error is at most rel_tol of its luminance (rtcore.h, "adaptive
+        sampling"), with the accumulators and the pixel list held as torch tensors on this scene's device.
+        Each iteration: rt_adaptive_select_device builds the list of pixels that still need samples, the
+        list's length is read (one 4-byte copy, the loop's only synchronisation), and
+        rt_render_pixels_device adds batch_spp samples of the listed pixels at
+        sample_base = iteration * batch_spp.  The loop stops when the list is empty.  The first select names
+        every pixel (N = 0 < min_spp), so there is no special first pass.  Once a pixel leaves the list its
+        accumulators no longer change, so the rule gives the same answer for ever and it never comes back;
+        every listed pixel has therefore been in every earlier list and has the same N = iteration *
+        batch_spp, which is why one sample_base per iteration is right.  min_spp and max_spp are rounded up
+        to multiples of batch_spp.
+        Returns a dict: sum (3, H, W) f64, samples, misses, batches (H, W) i32 (the uint32 bits), q (H, W) f64
+        -- device tensors in render_device's layout -- spp (H, W) i64 = samples + misses, counts (the list
+        sizes per iteration), lists (the lists themselves, device tensors), rays, params."""
+        import torch
+
+        if batch_spp <= 0 or min_spp <= 0 or max_spp < min_spp:
+            raise ValueError("need batch_spp > 0 and 0 < min_spp <= max_spp")
+        up = lambda v: -(-int(v) // batch_spp) * batch_spp  # noqa: E731
+        par = rt_adaptive_params(float(rel_tol), float(lum_floor), up(min_spp), up(max_spp))
+        W, H = self.width, self.height
+        dev = torch.device("cuda", self.device)
+        with torch.cuda.device(dev):
+            acc = {"sum": torch.zeros((3, H, W), dtype=torch.float64, device=dev),
+                   "samples": torch.zeros((H, W), dtype=torch.int32, device=dev),
+                   "misses": torch.zeros((H, W), dtype=torch.int32, device=dev),
+                   "q": torch.zeros((H, W), dtype=torch.float64, device=dev),
+                   "batches": torch.zeros((H, W), dtype=torch.int32, device=dev)}
+            d_count = torch.zeros(1, dtype=torch.int32, device=dev)
+            d_rays = torch.zeros(1, dtype=torch.int64, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            counts, lists = [], []
+            while True:
+                lst = torch.empty(W * H if not counts else counts[-1], dtype=torch.int32, device=dev)
+                adaptive_select_device(par, acc["sum"].data_ptr(), acc["samples"].data_ptr(), acc["misses"].data_ptr(),
+                                       acc["q"].data_ptr(), acc["batches"].data_ptr(), W, H, lst.data_ptr(), lst.numel(),
+                                       d_count.data_ptr(), stream=stream)
+                n = int(d_count.item()) & 0xFFFFFFFF
+                if n == 0:
+                    break
+                if n > lst.numel():
+                    raise RtError("render_adaptive: the list of active pixels grew")
+                lst = lst[:n]
+                self.render_pixels_device(lst.data_ptr(), n, batch_spp, seed, len(counts) * batch_spp,
+                                          acc["sum"].data_ptr(), acc["samples"].data_ptr(), acc["misses"].data_ptr(),
+                                          acc["q"].data_ptr(), acc["batches"].data_ptr(), 0, d_rays.data_ptr(), stream)
+                counts.append(n)
+                lists.append(lst)
+            torch.cuda.synchronize(dev)
+        acc["spp"] = acc["samples"].to(torch.int64) + acc["misses"].to(torch.int64)
+        acc.update(counts=counts, lists=lists, rays=int(d_rays.item()), params=par)
+        return acc
+
     def select_pixels(self, items, x0: int = 0, y0: int = 0, w: Optional[int] = None,
                       h: Optional[int] = None) -> np.ndarray:
         """rt_select_pixels (DebugRaycaster Selection mode): per pixel of the tile, which item of the list
@@ -878,6 +1001,59 @@ def tonemap_device(d_sum: int, d_samples: int, d_misses: int, w: int, h: int, d_
     """rt_tonemap_device: SampleSet.GetOutput for every pixel of device accumulators (pointers)."""
     _check(load_library().rt_tonemap_device(d_sum, d_samples, d_misses, w, h, rt_color(*background),
                                             background_alpha, exposure, d_argb, stream))
+
+
+def adaptive_select_device(params: rt_adaptive_params, d_sum: int, d_samples: int, d_misses: int, d_q: int,
+                           d_batches: int, width: int, height: int, d_pixels: int, cap: int, d_count: int,
+                           plane: int = 0, stream: int = 0) -> None:
+    """rt_adaptive_select_device: from whole-frame device accumulators (render_pixels_device's layout) the
+    compacted list of active pixels' frame indices into d_pixels (at most cap), their number into the
+    uint32 at d_count; 8x8 block order.  Works on the current device; asynchronous on `stream`."""
+    _check(load_library().rt_adaptive_select_device(C.byref(params), d_sum, d_samples, d_misses, d_q, d_batches, plane,
+                                                    width, height, d_pixels, cap, d_count, stream))
+
+
+def adaptive_select_host(params: rt_adaptive_params, sum_planes: np.ndarray, samples: np.ndarray, misses: np.ndarray,
+                         q: np.ndarray, batches: np.ndarray, width: int, height: int, cap: Optional[int] = None,
+                         plane: int = 0) -> Tuple[np.ndarray, int]:
+    """rt_debug_adaptive_select, the host twin of adaptive_select_device (no GPU): host arrays in the device
+    layout (sum: three planes `plane` doubles apart, 0 = width * height; the others row-major y * width +
+    x).  Returns (the first min(count, cap) list entries, count)."""
+    npix = width * height
+    pl = plane or npix
+    s = np.ascontiguousarray(sum_planes, np.float64).reshape(-1)
+    arrs = [np.ascontiguousarray(a, dt).reshape(-1) for a, dt in
+            ((samples, np.uint32), (misses, np.uint32), (q, np.float64), (batches, np.uint32))]
+    if s.size < 2 * pl + npix or any(a.size < npix for a in arrs):
+        raise ValueError("accumulator arrays smaller than the frame")
+    cap = npix if cap is None else int(cap)
+    out = np.zeros(max(cap, 1), np.uint32)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    n = load_library().rt_debug_adaptive_select(C.byref(params), ptr(s), ptr(arrs[0]), ptr(arrs[1]), ptr(arrs[2]),
+                                                ptr(arrs[3]), plane, width, height, ptr(out), cap)
+    if n < 0:
+        _check(int(n))
+    return out[:min(int(n), cap)].copy(), int(n)
+
+
+def pixels_plan(kernel: int, n: int, spp: int) -> dict:
+    """rt_debug_pixels_plan (host code, no GPU): how rt_render_pixels plans n list entries at spp for
+    kernel 0 (BRUTE), 1 (GROUPED) or 3 (BVH)."""
+    info = (C.c_int32 * 4)()
+    _check(load_library().rt_debug_pixels_plan(kernel, n, spp, info))
+    return dict(zip(("n_chunks", "samples_per_item", "used_chunks", "blocks"), (int(v) for v in info)))
+
+
+def pixel_standard_error(sum_rgb: np.ndarray, samples: np.ndarray, misses: np.ndarray, q: np.ndarray,
+                         batches: np.ndarray) -> np.ndarray:
+    """The standard error of each pixel's mean luminance from accumulators with moments (rtcore.h's
+    estimate); sum_rgb has the colour as its last axis.  inf where fewer than two batches were taken."""
+    n = samples.astype(np.float64) + misses.astype(np.float64)
+    y = 0.299 * sum_rgb[..., 0] + 0.587 * sum_rgb[..., 1] + 0.114 * sum_rgb[..., 2]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        var = np.maximum(0.0, (q - y * y / n) / (batches.astype(np.float64) - 1.0))
+        se = np.sqrt(var / n)
+    return np.where(batches >= 2, se, np.inf)
 
 
 def _frame_inputs(scene: ParsedScene, camera_index: int, size: Optional[Tuple[int, int]]):

@@ -459,6 +459,21 @@ int rt_debug_item_order(int32_t w, int32_t h, int32_t spp, int32_t chunks, int32
     return (int)n;
 }
 
+// Host only: the launch record of rt_render_pixels for a list of n entries (make_params_pixels).
+int rt_debug_pixels_plan(int32_t kernel, int64_t n, int32_t spp, int32_t* info)
+{
+    if (kernel < 0 || kernel > 3 || kernel == 2 || n <= 0 || n > ((int64_t)1 << 30) || spp <= 0 || !info) {
+        set_error("rt_debug_pixels_plan: bad argument");
+        return RT_ERR_ARG;
+    }
+    const PathParams p = make_params_pixels(kernel, n, spp, 0, 0, 1920, 1080);
+    info[0] = p.n_chunks;
+    info[1] = p.chunk;
+    info[2] = (p.spp + p.chunk - 1) / p.chunk;
+    info[3] = p.n_pad / 64;
+    return RT_OK;
+}
+
 // Host only: the scene bound rt_scene_create would give the brute-force path kernels for these primitives.
 int rt_debug_scene_bound(const rt_prim* prims, int32_t n_prims, float* lo, float* hi, float* info)
 {

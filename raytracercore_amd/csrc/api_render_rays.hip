@@ -34,7 +34,7 @@ int run_rays(rt_scene* s, PathParams& p, const rt_ray* d_rays, unsigned long lon
     HIP_TRY(hipMemsetAsync(p.counter, 0, sizeof(unsigned int) * kSplitStride * p.n_split, stream));
     const size_t dyn = path_dyn_lds(s->dev, s->variant);
     if (s->rays_variant != s->variant) {
-        s->rays_blocks_per_cu = path_blocks_per_cu(s->variant, dyn, false, s->dev.n_vn > 0, true);
+        s->rays_blocks_per_cu = path_blocks_per_cu(s->variant, dyn, false, s->dev.n_vn > 0, ITEMS_RAYS);
         s->rays_variant = s->variant;
     }
     int grid = s->n_cu * s->rays_blocks_per_cu;
@@ -51,7 +51,7 @@ int run_rays(rt_scene* s, PathParams& p, const rt_ray* d_rays, unsigned long lon
     const PathParams* pa = nullptr;
     const int rc = upload_params(s, p, stream, &pa);
     if (rc != RT_OK) return rc;
-    HIP_TRY(launch_path(s->dev, s->camf_d.p, pa, s->variant, grid, stream, false, true));
+    HIP_TRY(launch_path(s->dev, s->camf_d.p, pa, s->variant, grid, stream, false, ITEMS_RAYS));
     return RT_OK;
 }
 

@@ -1297,6 +1297,21 @@ __device__ __forceinline__ unsigned item_ray(unsigned item, const ParT& p)
     return ((item >> (6 + p.log2_chunks)) << 6) | (item & 63u);
 }
 
+// rt_render_pixels (the PIXELS instances): a list entry pix = fy * width + fx -> (fx, fy), by the
+// fp32-reciprocal divmod the item decode uses.  Exact: the estimate (float)pix * inv_frame_w carries
+// three roundings of 2^-24 relative each, less than 2^-22 fy in all, so for fy < 2^20 rows
+// (check_render_pixels refuses taller frames) it is within 1 of fy, which divmod's one correction
+// step repairs.  A multiply-high by ceil(2^32 / width) is exact only while pix * (M * width - 2^32) <
+// 2^32, which a 1080p frame already passes.
+template <class ParT>
+__device__ __forceinline__ void list_pixel(unsigned pix, const ParT& p, int& fx, int& fy)
+{
+    unsigned q, r;
+    divmod(pix, (unsigned)p.scene.width, p.inv_frame_w, q, r);
+    fx = (int)r;
+    fy = (int)q;
+}
+
 // The next sample of the lane's item.  The BVH (NT) kernels hold no register for it: the item's
 // first sample (its chunk, from the item index) plus the samples it finished (samples + misses).
 template <bool NT, class ParT>
@@ -1306,12 +1321,19 @@ __device__ __forceinline__ int item_sample(const Lane& L, const ParT& p)
     const int c = (int)((L.item >> 6) & (unsigned)(p.n_chunks - 1));
     return c * p.chunk + (int)(L.cnt & 0xFFu) + (int)((L.cnt >> 8) & 0xFFu);
 }
-// RAYS (rt_render_rays' instances): an item names a ray of p.ray_list instead of a pixel (item_ray),
+// SRC, where a launch's items come from (ItemSource, rt_kernels.h).
+// ITEMS_RAYS (rt_render_rays' instances): an item names a ray of p.ray_list instead of a pixel (item_ray),
 // its pixel key is that of p.stream_base + ray, and a sample starts from the ray as given, with the
 // two draws GetCameraRay would have spent discarded; the camera is never read.  The brute-force
 // kernels keep the ray index in L.fx; every kernel loads the ray's rows again at each sample start
 // (they stay in the cache between an item's samples) instead of holding six more registers.
-template <bool NT, bool RAYS = false, class ParT, class SceneT, class CamT>
+// ITEMS_PIXELS (rt_render_pixels' instances): an item names entry item_ray(item) of p.pixel_list, a
+// frame pixel index fy * width + fx, and from there on the lane does what a tile launch does for that
+// frame pixel: its key from the table or the hash, the rng of sample_base + sample, start_sample with
+// both GetCameraRay draws used.  An entry at or past p.n_frame_px opens no item.  The brute-force
+// kernels keep fx, fy in the lane; the BVH kernel reads the entry again at each sample start, as it
+// decodes a tile's item again (list_pixel).
+template <bool NT, int SRC = ITEMS_TILE, class ParT, class SceneT, class CamT>
 __device__ __forceinline__ void refill(Lane& L, Sample& S, const ParT& p, const SceneT& s, const CamT& cam, int lane,
                                       unsigned total)
 {
@@ -1383,7 +1405,23 @@ __device__ __forceinline__ void refill(Lane& L, Sample& S, const ParT& p, const 
                 // (no ticket drawn for it yet: it asks again in the next iteration)
             } else if (L.item >= total) {
                 L.active = false;
-            } else if constexpr (RAYS) {
+            } else if constexpr (SRC == ITEMS_PIXELS) {
+                const unsigned li = item_ray(L.item, p);
+                const int s0 = (int)((L.item >> 6) & (unsigned)(p.n_chunks - 1)) * p.chunk;
+                if (li < p.n_rays && s0 < p.spp) {
+                    const unsigned pix = p.pixel_list[li];
+                    if (pix < p.n_frame_px) {
+                        L.item_open = true;
+                        if (!NT) L.s_next = s0;
+                        L.cnt = (unsigned)(min(p.spp, s0 + p.chunk) - s0) << 16; // chunk <= 64
+                        if (!NT) {
+                            list_pixel(pix, p, L.fx, L.fy);
+                            if (p.pkeys) L.pkey = p.pkeys[pix];
+                            else L.pkey = rt_rng_pixel_key(p.seed_key, (unsigned long long)pix);
+                        }
+                    }
+                }
+            } else if constexpr (SRC == ITEMS_RAYS) {
                 const unsigned ri = item_ray(L.item, p);
                 const int s0 = (int)((L.item >> 6) & (unsigned)(p.n_chunks - 1)) * p.chunk;
                 if (ri < p.n_rays && s0 < p.spp) {
@@ -1425,7 +1463,7 @@ __device__ __forceinline__ void refill(Lane& L, Sample& S, const ParT& p, const 
             L.pool_next += k;
         }
     }
-    if constexpr (RAYS) {
+    if constexpr (SRC == ITEMS_RAYS) {
         if (L.active && L.item_open && !L.live && L.cnt >= 65536u) {
             const unsigned ri = NT ? item_ray(L.item, p) : (unsigned)L.fx;
             if (NT) L.pkey = rt_rng_pixel_key(p.seed_key, p.stream_base + (unsigned long long)ri);
@@ -1450,7 +1488,11 @@ __device__ __forceinline__ void refill(Lane& L, Sample& S, const ParT& p, const 
     }
     if (L.active && L.item_open && !L.live && L.cnt >= 65536u) {
         int fx = L.fx, fy = L.fy;
-        if (NT) { // the pixel and its key again at every sample start: three registers fewer held
+        if (NT && SRC == ITEMS_PIXELS) { // the list entry again (it stays in the cache between an item's samples)
+            const unsigned pix = p.pixel_list[item_ray(L.item, p)];
+            list_pixel(pix, p, fx, fy);
+            L.pkey = rt_rng_pixel_key(p.seed_key, (unsigned long long)pix);
+        } else if (NT) { // the pixel and its key again at every sample start: three registers fewer held
             int px, py, c;
             item_pixel(L.item, p, px, py, c, fx, fy);
             L.pkey = rt_rng_pixel_key(p.seed_key, (unsigned long long)fy * (unsigned long long)p.scene.width +
@@ -1571,7 +1613,7 @@ typedef RT_AS_CONST const PathParams ParamsC;
 
 // Brute-force megakernel: every loop iteration issues one closest-hit query per live lane
 // (the scene's records arrive through scalar loads) and shades it.
-template <bool CULL, bool LDS, bool STATS, bool VN, bool RAYS = false>
+template <bool CULL, bool LDS, bool STATS, bool VN, int SRC = ITEMS_TILE>
 __device__ __forceinline__ void path_body(const CameraF* __restrict__ camp, const PathParams* __restrict__ pp)
 {
     // everything but the LDS staging is read from the launch record *pp (fill_launch) in the
@@ -1613,7 +1655,7 @@ __device__ __forceinline__ void path_body(const CameraF* __restrict__ camp, cons
 #if defined(RT_SCENE_CONST) && RT_SCENE_CONST_CAMERA
         refill<false>(L, S, *pq, sc, *(const CameraF*)kCameraW, lane, total); // the camera compiled in too
 #else
-        refill<false, RAYS>(L, S, *pq, sc, *cp, lane, total);
+        refill<false, SRC>(L, S, *pq, sc, *cp, lane, total);
 #endif
         if (!__any(L.active)) break;
         if (STATS) t1 = __builtin_readcyclecounter();
@@ -1675,19 +1717,20 @@ __device__ __forceinline__ void path_body(const CameraF* __restrict__ camp, cons
     }
     // a culled launch (PathParams::cull): the first wave of block 0 adds the primary rays of the dead
     // blocks' pixels, spp each, which no item stands for
-    if (!STATS && !RAYS && P0.cull != nullptr && blockIdx.x == 0 && threadIdx.x < 64)
+    if (!STATS && SRC == ITEMS_TILE && P0.cull != nullptr && blockIdx.x == 0 && threadIdx.x < 64)
         wave_rays += ((unsigned long long)P0.cull[0] | (unsigned long long)P0.cull[1] << 32) * (unsigned long long)P0.spp;
     flush_counts<STATS>(wave_rays, cnt, *(const ParamsC*)pp, lane);
 }
 
-// RAYS: rt_render_rays' instances (refill); every other instance is as it was without the switch.
-template <bool CULL, bool LDS, bool STATS, bool VN, bool RAYS = false>
+// SRC: ITEMS_RAYS / ITEMS_PIXELS, rt_render_rays' / rt_render_pixels' instances (refill); the tile
+// instances are as they were without the switch.
+template <bool CULL, bool LDS, bool STATS, bool VN, int SRC = ITEMS_TILE>
 __global__ void __launch_bounds__(256, CULL ? RT_GROUPED_WAVES : RT_PATH_WAVES)
     path_kernel(PathScene, const CameraF* __restrict__ camp, const PathParams* __restrict__ pp, const TestRec*,
                 const RectRec*, const FrameRec*, const PrimF*, const NodeF*, const Node4Q*, const GroupRec*,
                 const XformF*, const MatF*, const float4*)
 {
-    path_body<CULL, LDS, STATS, VN, RAYS>(camp, pp); // the other arguments are the BVH kernels' (same launch)
+    path_body<CULL, LDS, STATS, VN, SRC>(camp, pp); // the other arguments are the BVH kernels' (same launch)
 }
 
 // The BVH order's outer group (DevScene::groups_bvh): the world rects and closed boxes left out of
@@ -1850,7 +1893,7 @@ __device__ __forceinline__ WalkStep walk_step(Walk& w, bool trav, int spec, Fetc
 // p.refill lanes wait (or none is still traversing).  So one long traversal no longer holds the
 // other 63 lanes of its wave, and the divergent shading code is paid once per batch of finished
 // queries.
-template <int WIDTH, int STACK, bool LDS, bool STATS, bool VN, bool RAYS = false>
+template <int WIDTH, int STACK, bool LDS, bool STATS, bool VN, int SRC = ITEMS_TILE>
 __global__ void __launch_bounds__(256, WIDTH == 4 ? RT_BVH_WAVES : RT_BVH2_WAVES)
     path_kernel_bvh(PathScene, const CameraF* __restrict__ camp, const PathParams* __restrict__ pp, const TestRec*,
                     const RectRec*, const FrameRec*, const PrimF*, const NodeF*, const Node4Q*, const GroupRec*,
@@ -1940,7 +1983,7 @@ __global__ void __launch_bounds__(256, WIDTH == 4 ? RT_BVH_WAVES : RT_BVH2_WAVES
                 bounce<VN, !LDS, true, STATS>(L, S, s, R, vnormals, tests, pq->prims_d, b, p);
                 done = false;
             }
-            refill<true, RAYS>(L, S, p, s, *cp, lane, total);
+            refill<true, SRC>(L, S, p, s, *cp, lane, total);
             if (L.live && !trav) { // start the next query
                 walk_start(w, s.root, true); // (PathScene carries no node count; root is taken as it is)
                 b = query_start<VN>(s, S.prev);
@@ -2473,6 +2516,69 @@ __global__ void accumulate_rays_kernel(PathParams p, double* sum, uint32_t* samp
     }
 }
 
+// rt_render_pixels: the fold per list entry.  Entry i's partials are at accumulate_rays_kernel's
+// addresses; they go, in chunk order, into the frame accumulators at the entry's pixel a = pix (row-major
+// y * W + x is the list's own index), exactly as accumulate_kernel adds a window's: r = sum[a], then
+// r += v.x per chunk.  With q: per used chunk j of t_j = samples + misses > 0 finished samples,
+// Y_j = 0.299 r + 0.587 g + 0.114 b of the chunk's fp32 sums (DoubleColor.GetLuminance, left to
+// right, every operation rounded on its own), q += Y_j Y_j / t_j and batches += 1.  recs: the same
+// from zero as one PixelRec per entry (the host entry's download), zero for a skipped entry.
+__global__ void accumulate_pixels_kernel(PathParams p, double* sum, uint32_t* samples, uint32_t* misses, double* q,
+                                         uint32_t* batches, size_t plane, PixelRec* recs)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)p.n_rays) return;
+    const size_t a = p.pixel_list[i];
+    const bool inside = a < (size_t)p.n_frame_px;
+    if (!inside && !recs) return;
+    double r = 0.0, g = 0.0, bl = 0.0, qs = 0.0;
+    if (!recs) {
+        r = sum[a];
+        g = sum[plane + a];
+        bl = sum[2 * plane + a];
+    }
+    uint32_t ns = 0, nm = 0, nb = 0;
+    const int used = inside ? (p.spp + p.chunk - 1) / p.chunk : 0;
+    for (int c = 0; c < used; c++) {
+        const float4 v = p.partial[((((i >> 6) << p.log2_chunks) + c) << 6) + (i & 63)];
+        r += v.x;
+        g += v.y;
+        bl += v.z;
+        const uint32_t k = __float_as_uint(v.w);
+        ns += k & 0xFFFFu;
+        nm += k >> 16;
+        const uint32_t t = (k & 0xFFFFu) + (k >> 16);
+        if ((q || recs) && t > 0) {
+            const double y = __dadd_rn(__dadd_rn(__dmul_rn(0.299, (double)v.x), __dmul_rn(0.587, (double)v.y)),
+                                       __dmul_rn(0.114, (double)v.z));
+            qs = __dadd_rn(qs, __ddiv_rn(__dmul_rn(y, y), (double)t));
+            nb++;
+        }
+    }
+    if (recs) {
+        PixelRec t;
+        t.r = r;
+        t.g = g;
+        t.b = bl;
+        t.q = qs;
+        t.samples = ns;
+        t.misses = nm;
+        t.batches = nb;
+        t.pad = 0;
+        recs[i] = t;
+    } else {
+        sum[a] = r;
+        sum[plane + a] = g;
+        sum[2 * plane + a] = bl;
+        samples[a] += ns;
+        misses[a] += nm;
+        if (q) {
+            q[a] = __dadd_rn(q[a], qs);
+            batches[a] += nb;
+        }
+    }
+}
+
 // SampleSet.GetOutput / GetColorCode (SampleSet.cs:50-113) per pixel of planar accumulators.
 __device__ __forceinline__ uint32_t color_code(double r, double g, double b, double a)
 {
@@ -2622,18 +2728,28 @@ using PathKernel = void (*)(PathScene, const CameraF*, const PathParams*, const 
 // vn: the scene has vertex-normal triangles (their re-hit test, vn_rehit_test, is fp64 code that
 // costs the other scenes' kernels registers, so it is compiled only into separate instances)
 template <bool CULL, bool LDS>
-PathKernel pick_brute(bool stats, bool vn, bool rays)
+PathKernel pick_brute(bool stats, bool vn, ItemSource src)
 {
-    if (rays) return vn ? path_kernel<CULL, LDS, false, true, true> : path_kernel<CULL, LDS, false, false, true>;
+    if (src == ITEMS_PIXELS)
+        return vn ? path_kernel<CULL, LDS, false, true, ITEMS_PIXELS> : path_kernel<CULL, LDS, false, false, ITEMS_PIXELS>;
+    if (src == ITEMS_RAYS)
+        return vn ? path_kernel<CULL, LDS, false, true, ITEMS_RAYS> : path_kernel<CULL, LDS, false, false, ITEMS_RAYS>;
     if (vn) return stats ? path_kernel<CULL, LDS, true, true> : path_kernel<CULL, LDS, false, true>;
     return stats ? path_kernel<CULL, LDS, true, false> : path_kernel<CULL, LDS, false, false>;
 }
 template <int WIDTH, int STACK, bool LDS>
-PathKernel pick_bvh(bool stats, bool vn, bool rays)
+PathKernel pick_bvh(bool stats, bool vn, ItemSource src)
 {
-    if (rays) { // (the wide kernel only; rt_render_rays refuses a BVH2 scene before it gets here)
+    if (src == ITEMS_PIXELS) { // (the wide kernel only, as for the rays)
         if constexpr (WIDTH == 4)
-            return vn ? path_kernel_bvh<WIDTH, STACK, LDS, false, true, true> : path_kernel_bvh<WIDTH, STACK, LDS, false, false, true>;
+            return vn ? path_kernel_bvh<WIDTH, STACK, LDS, false, true, ITEMS_PIXELS>
+                      : path_kernel_bvh<WIDTH, STACK, LDS, false, false, ITEMS_PIXELS>;
+        return nullptr;
+    }
+    if (src == ITEMS_RAYS) { // (the wide kernel only; rt_render_rays refuses a BVH2 scene before it gets here)
+        if constexpr (WIDTH == 4)
+            return vn ? path_kernel_bvh<WIDTH, STACK, LDS, false, true, ITEMS_RAYS>
+                      : path_kernel_bvh<WIDTH, STACK, LDS, false, false, ITEMS_RAYS>;
         return nullptr;
     }
     if (vn) return stats ? path_kernel_bvh<WIDTH, STACK, LDS, true, true> : path_kernel_bvh<WIDTH, STACK, LDS, false, true>;
@@ -2642,18 +2758,19 @@ PathKernel pick_bvh(bool stats, bool vn, bool rays)
 
 // variant = kernel * 2 + lds; kernel 0 brute force (flat), 1 brute force (grouped, culled),
 // 2 BVH2 (24-entry LDS stack), 3 wide BVH (RT_WIDE_STACK-entry LDS stack); both overflow to global memory.
-// rays: rt_render_rays' instance of the variant (never instrumented; none for the BVH2 kernel)
-PathKernel pick(int variant, bool stats, bool vn, bool rays = false)
+// src: ITEMS_RAYS / ITEMS_PIXELS, rt_render_rays' / rt_render_pixels' instance of the variant (never
+// instrumented; none for the BVH2 kernel)
+PathKernel pick(int variant, bool stats, bool vn, ItemSource src = ITEMS_TILE)
 {
     switch (variant) {
-    case 1: return pick_brute<false, true>(stats, vn, rays);
-    case 2: return pick_brute<true, false>(stats, vn, rays);
-    case 3: return pick_brute<true, true>(stats, vn, rays);
-    case 4: return pick_bvh<2, 24, false>(stats, vn, rays);
-    case 5: return pick_bvh<2, 24, true>(stats, vn, rays);
-    case 6: return pick_bvh<4, RT_WIDE_STACK, false>(stats, vn, rays);
-    case 7: return pick_bvh<4, RT_WIDE_STACK, true>(stats, vn, rays);
-    default: return pick_brute<false, false>(stats, vn, rays);
+    case 1: return pick_brute<false, true>(stats, vn, src);
+    case 2: return pick_brute<true, false>(stats, vn, src);
+    case 3: return pick_brute<true, true>(stats, vn, src);
+    case 4: return pick_bvh<2, 24, false>(stats, vn, src);
+    case 5: return pick_bvh<2, 24, true>(stats, vn, src);
+    case 6: return pick_bvh<4, RT_WIDE_STACK, false>(stats, vn, src);
+    case 7: return pick_bvh<4, RT_WIDE_STACK, true>(stats, vn, src);
+    default: return pick_brute<false, false>(stats, vn, src);
     }
 }
 
@@ -2735,9 +2852,9 @@ int blocks_per_cu(KernelT kernel, size_t dyn_lds = 0)
     return n;
 }
 
-int path_blocks_per_cu(int variant, size_t dyn_lds, bool stats, bool vn, bool rays)
+int path_blocks_per_cu(int variant, size_t dyn_lds, bool stats, bool vn, ItemSource src)
 {
-    return blocks_per_cu(pick(variant, stats, vn, rays), dyn_lds);
+    return blocks_per_cu(pick(variant, stats, vn, src), dyn_lds);
 }
 
 void fill_launch(const DevScene& s, int variant, PathParams& p)
@@ -2774,9 +2891,9 @@ void fill_launch(const DevScene& s, int variant, PathParams& p)
 }
 
 hipError_t launch_path(const DevScene& s, const CameraF* d_cam, const PathParams* d_params, int variant,
-                       int grid_blocks, hipStream_t stream, bool stats, bool rays)
+                       int grid_blocks, hipStream_t stream, bool stats, ItemSource src)
 {
-    const PathKernel kernel = pick(variant, stats, s.n_vn > 0, rays);
+    const PathKernel kernel = pick(variant, stats, s.n_vn > 0, src);
     if (!kernel) return hipErrorInvalidValue;
     PathParams h{}; // the same launch record as the device copy: the BVH kernels take it as arguments
     fill_launch(s, variant, h);
@@ -2813,6 +2930,24 @@ hipError_t launch_accumulate_rays(const PathParams& p, double* d_sum, uint32_t* 
     if (p.n_rays == 0) return hipSuccess;
     hipLaunchKernelGGL(accumulate_rays_kernel, dim3((p.n_rays + 255u) / 256u), dim3(256), 0, stream, p, d_sum, d_samples,
                        d_misses, d_recs);
+    return hipGetLastError();
+}
+
+hipError_t launch_accumulate_pixels(const PathParams& p, double* d_sum, uint32_t* d_samples, uint32_t* d_misses,
+                                    double* d_q, uint32_t* d_batches, size_t plane, hipStream_t stream)
+{
+    if (p.n_rays == 0) return hipSuccess;
+    if (plane == 0) plane = (size_t)p.n_frame_px;
+    hipLaunchKernelGGL(accumulate_pixels_kernel, dim3((p.n_rays + 255u) / 256u), dim3(256), 0, stream, p, d_sum, d_samples,
+                       d_misses, d_q, d_batches, plane, (PixelRec*)nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_accumulate_pixels_recs(const PathParams& p, PixelRec* d_recs, hipStream_t stream)
+{
+    if (p.n_rays == 0) return hipSuccess;
+    hipLaunchKernelGGL(accumulate_pixels_kernel, dim3((p.n_rays + 255u) / 256u), dim3(256), 0, stream, p, (double*)nullptr,
+                       (uint32_t*)nullptr, (uint32_t*)nullptr, (double*)nullptr, (uint32_t*)nullptr, (size_t)0, d_recs);
     return hipGetLastError();
 }
 

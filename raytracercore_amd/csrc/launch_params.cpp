@@ -201,6 +201,21 @@ PathParams make_params_rays(int kernel, int64_t n, int spp, uint64_t seed, uint6
     return p;
 }
 
+// rt_render_pixels: a list of n frame pixels, planned as a ray list is: the 8-wide tile, so that entry
+// i is pixel i & 63 of block i >> 6 and 64 consecutive entries share a wave, and the chunks of a
+// 1080p frame at this spp whatever n is.  The samples per item are then min(64, ceil(spp / B)), B = 24
+// for the brute-force kernels and 64 for the BVH kernel: a function of spp alone, so a pixel's fp32
+// partial sums do not depend on the list it came in, and they are those of rt_render_device wherever
+// that launch has the same samples per item.
+PathParams make_params_pixels(int kernel, int64_t n, int spp, uint64_t seed, uint64_t base, int width, int height)
+{
+    PathParams p = make_params_for(kernel, 0, 0, 0, 0, 8, (int)((n + 7) / 8), spp, seed, base, 2073600.0);
+    p.n_rays = (unsigned)n;
+    p.n_frame_px = (unsigned)((uint64_t)width * (uint64_t)height);
+    p.inv_frame_w = 1.0f / (float)width;
+    return p;
+}
+
 // Most rays of one RAYS launch at this spp: 32-bit item indices, n_chunks slots per ray padded to
 // whole blocks of 64, below the bound run_path holds every launch to (0xF0000000 items), and below
 // 2^30 rays (n_pad is an int).  0 when not even one block fits.

@@ -15,6 +15,9 @@ PathParams make_params_for(int kernel, int chunks_over, int pool_over, int x0, i
 // this spp (32-bit item indices).
 PathParams make_params_rays(int kernel, int64_t n, int spp, uint64_t seed, uint64_t base, uint64_t stream_base);
 int64_t render_rays_max_n(int kernel, int spp);
+// rt_render_pixels: the launch record of a list of n frame pixels of a width x height frame, planned as
+// make_params_rays plans n rays (p.pixel_list is set by the caller); render_rays_max_n bounds n.
+PathParams make_params_pixels(int kernel, int64_t n, int spp, uint64_t seed, uint64_t base, int width, int height);
 // The order in which the dispensers deal p's work items, from p's chunks, pool and ranges.
 void set_item_order(PathParams& p);
 // Plans p's item ranges and tickets (set_item_order) over n_blocks blocks; p.n_pad = 64 n_blocks.

@@ -8,6 +8,10 @@ namespace rtc {
 constexpr int kMaxSplit = 8;     // item ranges of a launch: one per XCD of the MI355X
 constexpr int kSplitStride = 32; // dispenser words apart (one 128-B line each)
 
+// Where the work items of a path launch come from (refill, kernels_path.hip): the pixels of a window,
+// a caller's rays (rt_render_rays) or a list of frame pixels (rt_render_pixels).
+enum ItemSource : int { ITEMS_TILE = 0, ITEMS_RAYS = 1, ITEMS_PIXELS = 2 };
+
 // Work decomposition of one path-tracing launch over a w x h tile.
 struct PathParams {
     int x0, y0, w, h;           // tile within the frame
@@ -91,9 +95,23 @@ struct PathParams {
     // field moves): the caller's rays as rt_ray rows.  The launch is planned as a tile 8 pixels wide
     // (make_params_rays), so the 64 items of block b and one chunk are the rays 64 b .. 64 b + 63: ray
     // i = (block << 6) | pixel of the item, and its pixel key is that of stream_base + i.
-    const double2* ray_list;    // four 16-B rows per ray (origin xy, origin zw, direction xy, direction zw)
-    unsigned int n_rays;        // rays of the launch (the items of the last block past it stay closed)
-    unsigned long long stream_base;
+    // rt_render_pixels, the PIXELS instances only: the launch is planned in the same way
+    // (make_params_pixels), entry i = (block << 6) | pixel of the item names the frame pixel
+    // pixel_list[i] = fy * scene.width + fx, and an entry at or past n_frame_px is skipped.  The list's
+    // fields share the rays' storage, so that the record keeps its size and no field moves: the kernels
+    // that take it by value are as they were.
+    union {
+        const double2* ray_list;    // four 16-B rows per ray (origin xy, origin zw, direction xy, direction zw)
+        const uint32_t* pixel_list; // frame pixel indices
+    };
+    unsigned int n_rays;        // rays or list entries of the launch (the items of the last block past it stay closed)
+    union {
+        unsigned long long stream_base;
+        struct {
+            unsigned int n_frame_px; // scene.width * frame height
+            float inv_frame_w;       // fp32 1 / scene.width (list_pixel)
+        };
+    };
     int scene_bound;            // flat brute-force kernel: 1 = a wave of camera rays that all miss the scene bound
                                 // skips its query (RTCORE_SCENE_BOUND, make_params_for)
     // The block cull (block_cull.h, run_path): null, or a device record of the launch's 8x8 blocks whose
@@ -225,11 +243,13 @@ size_t path_lds_bytes(const DevScene& s);   // dynamic LDS of the staged (lds) v
 size_t path_dyn_lds(const DevScene& s, int variant); // all dynamic LDS of a variant (+ the wide kernel's hot nodes)
 // Launch the persistent kernel; stats counts node visits / primitive tests (slower build).
 // The camera and the launch parameters are read from device memory (d_cam, d_params).
-// rays: rt_render_rays' instance of the variant (PathParams::ray_list; the brute-force and the wide
-// BVH kernels, never instrumented), which does not read the camera.
+// src: ITEMS_RAYS, rt_render_rays' instance of the variant (PathParams::ray_list), which does not read
+// the camera; ITEMS_PIXELS, rt_render_pixels' (PathParams::pixel_list).  Both exist for the brute-force
+// and the wide BVH kernels and are never instrumented.
 hipError_t launch_path(const DevScene& s, const CameraF* d_cam, const PathParams* d_params, int variant,
-                       int grid_blocks, hipStream_t stream, bool stats, bool rays = false);
-int path_blocks_per_cu(int variant, size_t dyn_lds, bool stats, bool vn, bool rays = false); // vn: scene has vertex-normal triangles
+                       int grid_blocks, hipStream_t stream, bool stats, ItemSource src = ITEMS_TILE);
+// vn: scene has vertex-normal triangles
+int path_blocks_per_cu(int variant, size_t dyn_lds, bool stats, bool vn, ItemSource src = ITEMS_TILE);
 // The trace-only kernel (waves per SIMD 6 / 7 / 8 with LDS stacks of 20 / 16 / 16 entries): blocks
 // per CU and launch (grid blocks of 256).
 int trace_rays_blocks_per_cu(int waves);
@@ -264,6 +284,19 @@ struct TileRec {
 // d_sum (planes R | G | B of p.n_rays doubles), d_samples, d_misses; else written to d_recs[p.n_rays].
 hipError_t launch_accumulate_rays(const PathParams& p, double* d_sum, uint32_t* d_samples, uint32_t* d_misses,
                                   TileRec* d_recs, hipStream_t stream);
+// rt_render_pixels: a PIXELS launch's partials (at accumulate_rays_kernel's addresses) folded per list
+// entry, in chunk order, into whole-frame accumulators at pixel_list[i] (row-major, planes `plane`
+// apart, as launch_accumulate), added to; d_q and d_batches (both or neither) get the moments of
+// rtcore.h's "adaptive sampling".  An entry outside the frame is skipped.
+hipError_t launch_accumulate_pixels(const PathParams& p, double* d_sum, uint32_t* d_samples, uint32_t* d_misses,
+                                    double* d_q, uint32_t* d_batches, size_t plane, hipStream_t stream);
+// One list entry of rt_render_pixels' host entry: what the fold adds to the entry's pixel.
+struct PixelRec {
+    double r, g, b, q;
+    uint32_t samples, misses, batches, pad;
+};
+// The same fold from zero, one PixelRec per entry (q and batches always)
+hipError_t launch_accumulate_pixels_recs(const PathParams& p, PixelRec* d_recs, hipStream_t stream);
 // planar row-major accumulators (w*h) -> TileRec[w*h] in x*h + y order
 hipError_t launch_tile_host_layout(int w, int h, const double* d_sum, const uint32_t* d_samples,
                                   const uint32_t* d_misses, TileRec* d_out, hipStream_t stream);

@@ -1,5 +1,6 @@
 // rt_scene.h -- the scene object behind the C ABI and what the API's translation units share
-// (rtcore_api.hip, scene_upload.hip, api_frame.hip, api_debug.hip, api_query.hip, api_select.hip, api_render_rays.hip).
+// (rtcore_api.hip, scene_upload.hip, api_frame.hip, api_debug.hip, api_query.hip, api_select.hip, api_render_rays.hip,
+// api_render_pixels.hip).
 #pragma once
 #include <algorithm>
 #include <array>
@@ -191,6 +192,11 @@ struct rt_scene {
     // the blocks per CU of the RAYS instance of `rays_variant`
     DevBuf<TileRec> render_rays_recs;
     int rays_variant = -1, rays_blocks_per_cu = 1;
+    // rt_render_pixels: two chunks of list entries and of per-entry records, and the blocks per CU of
+    // the PIXELS instance of `pixels_variant`
+    DevBuf<uint32_t> pixel_list;
+    DevBuf<PixelRec> pixel_recs;
+    int pixels_variant = -1, pixels_blocks_per_cu = 1;
     // the selection pass (api_select.hip): the caller's item list on the device, and the host-buffer
     // entry points' rays (one chunk) and results
     DevBuf<rt_select_item> select_items;
@@ -313,6 +319,9 @@ int end_op(rt_scene* s, hipStream_t stream);
 int queue_copy(rt_scene* s, CopyPlan& plan, const void* d_src, size_t a, size_t b, size_t rec_bytes, int k,
                hipStream_t stream);
 int consume_copies(rt_scene* s, const CopyPlan& plan, const std::function<void(const unsigned char*, size_t, size_t)>& consume);
+// api_render_pixels.hip: rt_render_pixels' list check (every entry below npix, none twice); null, or
+// what is wrong with entry *at
+const char* check_pixel_list(const uint32_t* pixels, int64_t n, uint64_t npix, int64_t* at);
 int copy_consume(rt_scene* s, const void* d_src, size_t n_items, size_t rec_bytes,
                  const std::function<void(const unsigned char*, size_t, size_t)>& consume);
 
