@@ -48,7 +48,8 @@ extern "C" {
                                    rt_select_rays, rt_select_rays_device and rt_debug_select_rays, and
                                    rt_render_rays and rt_render_rays_device, and rt_occluded_rays and
                                    rt_occluded_rays_device, and rt_render_pixels, rt_render_pixels_device,
-                                   rt_adaptive_select_device and rt_debug_adaptive_select */
+                                   rt_adaptive_select_device and rt_debug_adaptive_select, and
+                                   rt_primary_hits_device, rt_denoise_device and rt_debug_denoise */
 
 typedef enum rt_status {
     RT_OK = 0,
@@ -735,6 +736,84 @@ int rt_adaptive_select_device(const rt_adaptive_params* params, const double* d_
 int64_t rt_debug_adaptive_select(const rt_adaptive_params* params, const double* sum, const uint32_t* samples,
                                  const uint32_t* misses, const double* q, const uint32_t* batches, uint64_t plane,
                                  int32_t width, int32_t height, uint32_t* pixels, uint32_t cap);
+
+/* ------------------------------------------------------------------- denoising --- */
+/*
+ * The guide pass.  d_hits[y*w + x] is, bit for bit, what rt_query_rays(RT_QUERY_FAST) answers for the ray
+ * rt_camera_rays gives for pixel (x0 + x, y0 + y) of the scene's frame: Camera.GetRay(x, y).Offset(imagePlane),
+ * the pixel centre, no lens sample.  The rays are made on the device, in chunks of whole rows of at most
+ * 2^19 rays (one row where a row is longer), so the scene's scratch for them stays below rt_query_rays'.
+ * Asynchronous on `stream`, ordered like the device-resident renders.  RT_ERR_STATE without a camera and on
+ * a BVH2 scene; RT_ERR_ARG for a null pointer, w or h <= 0 or a tile outside the frame.  The generic
+ * kernels run, whatever rt_set_jit says; the counters of rt_scene_get_stats, an armed rt_debug_ray_log,
+ * rt_kernel_times and the scene-specialised kernels are left as they were.
+ */
+int rt_primary_hits_device(rt_scene* scene, int32_t x0, int32_t y0, int32_t w, int32_t h, rt_hit* d_hits, void* stream);
+
+/*
+ * rt_denoise_device: an edge-avoiding a-trous filter (the spatial half of SVGF) over whole-frame
+ * accumulators with moments, guided by the first hits of rt_primary_hits_device and by the pixels' own
+ * variance estimate.  The definition is normative; the device pass and the host twin rt_debug_denoise
+ * compile it from one set of functions and agree bit for bit.  Every operation is rounded on its own (no
+ * contraction), division and square root are IEEE on both sides, no library function is called.  The
+ * state is fp32 unless stated.
+ *
+ * Valid pixel: samples > 0, the hit's prim_id >= 0, and c and v (below, as fp32) finite.  An invalid
+ * pixel passes through -- out_sum = sum bit for bit, out_var = 0 -- and contributes to no other pixel.
+ *
+ * Preparation, in fp64, each result rounded to fp32 once: c = sum / samples per channel; with N, Y, Q, J
+ * and s2 of "adaptive sampling" above, v = s2 * N / samples^2 for J >= 2 (the variance of c's luminance)
+ * and v = (Y / samples)^2 for J < 2 (no estimate: the pixel's own luminance squared, which keeps the
+ * luminance edge stop wide open).  Guides: the hit's normal n and position x, and d = (float)distance.
+ *
+ * Level k = 0 .. iterations - 1, step s = 2^k, for a valid pixel p.  Its taps are q = p + s (i, j),
+ * i, j in -2 .. 2, inside the frame and valid, visited with j ascending, then i ascending; h = {1/16, 1/4,
+ * 3/8, 1/4, 1/16}; the weight of a tap is w = h(i) h(j) w_n w_z w_l, multiplied left to right, and a tap
+ * whose w is not above 0 contributes nothing.  The centre tap's w is the constant 9/64, not computed
+ * (a centre whose normal is NaN, rt_debug_ray.normal's quirk, keeps its own colour).
+ *   w_n = max(0, n_p . n_q)^(2^normal_pow_log2), by that many squarings; a NaN dot product gives 0;
+ *         with RT_DENOISE_SAME_PRIM, 0 for a tap of another prim_id
+ *   w_z = f(|n_p . (x_q - x_p)| / (sigma_z d_p))               (dot products left to right)
+ *   w_l = f(|L(c_q) - L(c_p)| / (sigma_l sqrt(g_p) + lum_eps)),   L = 0.299 r + 0.587 g + 0.114 b
+ *   f(t) = 1 / (1 + t + 0.5 t t) for t >= 0, else 0 (NaN gives 0)
+ *   g_p = sum k_q v_q / sum k_q over p and its neighbours q = p + (i, j), i, j in -1 .. 1 (distance 1 at
+ *         every level), k = {1/4, 1/2, 1/4}^2, that lie in the frame, are valid and have w_n > 0 towards p,
+ *         in the same order.  (The w_n > 0 condition keeps the filter from leaking across an edge that
+ *         the normals or prim_ids stop: without it a pixel beside the edge would read the variance of the
+ *         pixels behind it.)
+ *   c' = c_p + sum w (c_q - c_p) / sum w per channel -- an exactly constant image maps to itself --
+ *   v' = sum w w v_q / (sum w)^2; the levels ping-pong between two state buffers.
+ * Output: out_sum = (double)c * (double)samples per channel and out_var = v after the last level, so
+ * rt_tonemap_device(d_out_sum, d_samples, d_misses, ...) works unchanged.
+ *
+ * Accumulators in rt_render_pixels_device's layout (index y * width + x, planes `plane` elements apart,
+ * 0 = width * height); d_hits is rt_primary_hits_device's output for the whole frame; d_out_sum has
+ * d_sum's layout and must not overlap it; d_out_var (width * height floats) may be NULL.  The pass runs
+ * on the calling thread's current device, asynchronous on `stream`; its scratch (a 32-byte guide record
+ * and two 16-byte state records per pixel) is the library's own, per device, grown on demand; a call on
+ * another stream than the last one on that device is ordered after it.
+ * RT_ERR_ARG, before anything is launched, for a null pointer (d_out_var excepted), a frame of no pixels
+ * or of 2^32 or more, out_sum overlapping sum, a sigma or lum_eps that is not above 0 (NaN included),
+ * normal_pow_log2 outside 0 .. 8, iterations outside 1 .. 5, unknown flag bits or non-zero reserved.
+ * rt_debug_denoise: the host twin (host only, no device needed), the same arguments on host arrays.
+ */
+#define RT_DENOISE_SAME_PRIM 1u
+typedef struct rt_denoise_params {   /* 32 B */
+    float    sigma_l;          /* luminance edge stop, in standard deviations; > 0            */
+    float    sigma_z;          /* plane-distance edge stop, relative to the centre's distance; > 0 */
+    float    lum_eps;          /* > 0, added to sigma_l * sqrt(g) */
+    int32_t  normal_pow_log2;  /* 0..8: w_n = max(0, n_p . n_q)^(2^m), by m squarings          */
+    int32_t  iterations;       /* 1..5 levels, step 2^k                                        */
+    uint32_t flags;            /* RT_DENOISE_SAME_PRIM = 1: a tap of another prim_id weighs 0  */
+    uint32_t reserved[2];      /* 0 */
+} rt_denoise_params;
+int rt_denoise_device(const rt_denoise_params* params, const double* d_sum, const uint32_t* d_samples,
+                      const uint32_t* d_misses, const double* d_q, const uint32_t* d_batches, uint64_t plane,
+                      const rt_hit* d_hits, int32_t width, int32_t height, double* d_out_sum, float* d_out_var,
+                      void* stream);
+int rt_debug_denoise(const rt_denoise_params* params, const double* sum, const uint32_t* samples,
+                     const uint32_t* misses, const double* q, const uint32_t* batches, uint64_t plane,
+                     const rt_hit* hits, int32_t width, int32_t height, double* out_sum, float* out_var);
 
 /* Device-side DebugRaycaster Primitives pass: d_ids[y*w + x].  Asynchronous. */
 int rt_primary_ids_device(rt_scene* scene, int32_t x0, int32_t y0, int32_t w, int32_t h,

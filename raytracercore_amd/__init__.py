@@ -163,6 +163,38 @@ class rt_adaptive_params(C.Structure):
                 ("max_samples", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+RT_DENOISE_SAME_PRIM = 1  # rt_denoise_params.flags: a tap of another prim_id weighs 0
+
+
+class rt_denoise_params(C.Structure):
+    """The a-trous filter's parameters (rt_denoise_device), 32 B."""
+    _fields_ = [("sigma_l", C.c_float), ("sigma_z", C.c_float), ("lum_eps", C.c_float), ("normal_pow_log2", C.c_int32),
+                ("iterations", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+# what GpuRaytracer.denoise uses where the caller names no value (DESIGN.md 4.7: sigma_l counts standard
+# deviations of a pixel mean that adaptive sampling left as large as rel_tol of the luminance, so it is small)
+DENOISE_DEFAULTS = dict(sigma_l=1.5, sigma_z=0.05, lum_eps=1e-4, normal_pow_log2=6, iterations=5, flags=0)
+
+
+def denoise_iterations(width: int, height: int) -> int:
+    """The levels GpuRaytracer.denoise runs where the caller names none: the filter's reach, 2 (2^k - 1) pixels
+    each way after k levels, held to about a twentieth of the frame's shorter side -- 5 from 1024 pixels up,
+    one fewer per halving, at least 1."""
+    return max(1, min(5, int(min(width, height)).bit_length() - 6))
+
+
+def denoise_params(**kw) -> rt_denoise_params:
+    """rt_denoise_params from keywords, DENOISE_DEFAULTS for the rest."""
+    v = dict(DENOISE_DEFAULTS)
+    unknown = set(kw) - set(v)
+    if unknown:
+        raise TypeError(f"unknown denoise parameter(s): {sorted(unknown)}")
+    v.update(kw)
+    return rt_denoise_params(float(v["sigma_l"]), float(v["sigma_z"]), float(v["lum_eps"]), int(v["normal_pow_log2"]),
+                             int(v["iterations"]), int(v["flags"]))
+
+
 SELECT_ITEM_DTYPE = np.dtype([("kind", np.int32), ("index", np.int32)])
 SELECTION_DTYPE = np.dtype([("item", np.int32), ("reserved", np.int32), ("distance", np.float64)])
 
@@ -178,7 +210,7 @@ HIT_DTYPE = np.dtype([
 _OPTIONAL = ("rt_query_rays", "rt_query_rays_device", "rt_camera_rays", "rt_select_pixels", "rt_select_pixels_device",
              "rt_select_rays", "rt_select_rays_device", "rt_render_rays", "rt_render_rays_device",
              "rt_occluded_rays", "rt_occluded_rays_device", "rt_render_pixels", "rt_render_pixels_device",
-             "rt_adaptive_select_device")
+             "rt_adaptive_select_device", "rt_primary_hits_device", "rt_denoise_device")
 
 _lib: Optional[C.CDLL] = None
 
@@ -297,6 +329,11 @@ def load_library(path: str = "") -> C.CDLL:
         "rt_debug_adaptive_select": (C.c_int64, [P(rt_adaptive_params)] + [C.c_void_p] * 5 + [C.c_uint64, C.c_int32,
                                                  C.c_int32, C.c_void_p, C.c_uint32]),
         "rt_debug_pixels_plan": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, P(C.c_int32)]),
+        "rt_primary_hits_device": (C.c_int, [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p]),
+        "rt_denoise_device": (C.c_int, [P(rt_denoise_params)] + [C.c_void_p] * 5 + [C.c_uint64, C.c_void_p, C.c_int32,
+                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "rt_debug_denoise": (C.c_int, [P(rt_denoise_params)] + [C.c_void_p] * 5 + [C.c_uint64, C.c_void_p, C.c_int32,
+                                       C.c_int32, C.c_void_p, C.c_void_p]),
     }
     for name, (res, args) in sig.items():
         if (name.startswith("rt_debug_") or name in _OPTIONAL) and not hasattr(lib, name):
@@ -918,6 +955,40 @@ class GpuRaytracer:
         acc.update(counts=counts, lists=lists, rays=int(d_rays.item()), params=par)
         return acc
 
+    def primary_hits_device(self, d_hits: int, x0: int = 0, y0: int = 0, w: Optional[int] = None, h: Optional[int] = None,
+                            stream: int = 0) -> None:
+        """rt_primary_hits_device: the fast first hit of every pixel centre of the tile into w * h rt_hit at
+        device pointer d_hits, row-major (y * w + x): what query_rays answers for camera_rays of the tile,
+        the rays made on the device.  Asynchronous on `stream`."""
+        w = self.width - x0 if w is None else w
+        h = self.height - y0 if h is None else h
+        _check(self.lib.rt_primary_hits_device(self.handle, x0, y0, w, h, C.c_void_p(d_hits), C.c_void_p(stream)))
+
+    def denoise(self, res: dict, return_var: bool = False, **params):
+        """The a-trous filter (rtcore.h, "denoising") over render_adaptive's result `res`: one
+        rt_primary_hits_device pass for the frame's guides, then rt_denoise_device, on torch's current
+        stream.  params: the fields of rt_denoise_params (DENOISE_DEFAULTS for the rest, and
+        denoise_iterations of the frame for the levels).  Returns the filtered sums as a (3, H, W) f64 device
+        tensor in res["sum"]'s layout -- tonemap_device takes it with res["samples"] and res["misses"] -- and
+        with return_var also the filtered variance, (H, W) f32."""
+        import torch
+
+        W, H = self.width, self.height
+        params.setdefault("iterations", denoise_iterations(W, H))
+        par = denoise_params(**params)
+        dev = torch.device("cuda", self.device)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            hits = torch.empty((H * W, HIT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+            out = torch.empty((3, H, W), dtype=torch.float64, device=dev)
+            var = torch.empty((H, W), dtype=torch.float32, device=dev) if return_var else None
+            self.primary_hits_device(hits.data_ptr(), stream=stream)
+            denoise_device(par, res["sum"].data_ptr(), res["samples"].data_ptr(), res["misses"].data_ptr(),
+                           res["q"].data_ptr(), res["batches"].data_ptr(), hits.data_ptr(), W, H, out.data_ptr(),
+                           var.data_ptr() if return_var else 0, stream=stream)
+            torch.cuda.synchronize(dev)  # (hits is released on return)
+        return (out, var) if return_var else out
+
     def select_pixels(self, items, x0: int = 0, y0: int = 0, w: Optional[int] = None,
                       h: Optional[int] = None) -> np.ndarray:
         """rt_select_pixels (DebugRaycaster Selection mode): per pixel of the tile, which item of the list
@@ -1034,6 +1105,39 @@ def adaptive_select_host(params: rt_adaptive_params, sum_planes: np.ndarray, sam
     if n < 0:
         _check(int(n))
     return out[:min(int(n), cap)].copy(), int(n)
+
+
+def denoise_device(params: rt_denoise_params, d_sum: int, d_samples: int, d_misses: int, d_q: int, d_batches: int,
+                   d_hits: int, width: int, height: int, d_out_sum: int, d_out_var: int = 0, plane: int = 0,
+                   stream: int = 0) -> None:
+    """rt_denoise_device: the a-trous filter over whole-frame device accumulators with moments
+    (render_pixels_device's layout) and the frame's first hits (primary_hits_device), into d_out_sum (d_sum's
+    layout, not overlapping it) and, unless 0, width * height floats of filtered variance at d_out_var.
+    Works on the current device; asynchronous on `stream`."""
+    _check(load_library().rt_denoise_device(C.byref(params), d_sum, d_samples, d_misses, d_q, d_batches, plane, d_hits,
+                                            width, height, d_out_sum, d_out_var or None, stream))
+
+
+def denoise_host(params: rt_denoise_params, sum_planes: np.ndarray, samples: np.ndarray, misses: np.ndarray,
+                 q: np.ndarray, batches: np.ndarray, hits: np.ndarray, width: int, height: int,
+                 plane: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    """rt_debug_denoise, the host twin of denoise_device (no GPU): host arrays in the device layout (sum: three
+    planes `plane` doubles apart, 0 = width * height; the others and hits, a HIT_DTYPE array, row-major
+    y * width + x).  Returns (out_sum, a flat f64 array of sum's size whose bytes outside the three planes
+    are 0, and out_var, f32 (height, width))."""
+    npix = width * height
+    pl = plane or npix
+    s = np.ascontiguousarray(sum_planes, np.float64).reshape(-1)
+    arrs = [np.ascontiguousarray(a, dt).reshape(-1) for a, dt in
+            ((samples, np.uint32), (misses, np.uint32), (q, np.float64), (batches, np.uint32), (hits, HIT_DTYPE))]
+    if pl < npix or s.size < 2 * pl + npix or any(a.size < npix for a in arrs):
+        raise ValueError("accumulator arrays smaller than the frame")
+    out = np.zeros(s.size, np.float64)
+    var = np.zeros((height, width), np.float32)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    _check(load_library().rt_debug_denoise(C.byref(params), ptr(s), ptr(arrs[0]), ptr(arrs[1]), ptr(arrs[2]), ptr(arrs[3]),
+                                           plane, ptr(arrs[4]), width, height, ptr(out), ptr(var)))
+    return out, var
 
 
 def pixels_plan(kernel: int, n: int, spp: int) -> dict:

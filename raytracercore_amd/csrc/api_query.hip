@@ -130,9 +130,49 @@ int query_device(rt_scene* s, int32_t mode, const rt_ray* d_rays, int64_t n, rt_
     return end_op(s, st);
 }
 
+// rt_primary_hits_device's rays: rows [y0, y0 + rows) of the tile's columns [x0, x0 + w), rays[y * w + x],
+// by the function rt_camera_rays runs on the host.
+__global__ void __launch_bounds__(256) camera_rays_kernel(CameraD cam, int x0, int y0, int w, unsigned n, rt_ray* __restrict__ rays)
+{
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const int y = (int)(i / (unsigned)w), x = (int)(i - (unsigned)y * (unsigned)w);
+    Vec4d o, d;
+    camera_ray_d(cam, (double)(x0 + x), (double)(y0 + y), o, d);
+    rays[i] = rt_ray{rt_vec4d{o.x, o.y, o.z, o.w}, rt_vec4d{d.x, d.y, d.z, d.w}};
+}
+
 } // namespace
 
 extern "C" {
+
+int rt_primary_hits_device(rt_scene* s, int32_t x0, int32_t y0, int32_t w, int32_t h, rt_hit* d_hits, void* stream)
+{
+    int rc = check_tile(s, x0, y0, w, h);
+    if (rc != RT_OK) return rc;
+    bool empty;
+    rc = check_query(s, RT_QUERY_FAST, d_hits, 1, d_hits, "rt_primary_hits_device", &empty);
+    if (rc != RT_OK) return rc;
+    if ((int64_t)w > kQueryLaunchMax) {
+        set_error("rt_primary_hits_device: bad argument (a row of more than 2^30 pixels)");
+        return RT_ERR_ARG;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int rows =(int)std::min<int64_t>(h, std::max<int64_t>(1, kQueryChunk / w));
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(s->primary_rays.reserve((size_t)rows * (size_t)w));
+    // the rays, the work counter and the stack overflow area are the scene's: order after its last operation
+    if (s->any_op && st != s->last_stream) HIP_TRY(hipStreamWaitEvent(st, s->done_ev, 0));
+    for (int r = 0; r < h; r += rows) {
+        const unsigned n = (unsigned)std::min(rows, h - r) * (unsigned)w;
+        hipLaunchKernelGGL(camera_rays_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, s->camd, x0, y0 + r, w, n,
+                           s->primary_rays.p);
+        HIP_TRY(hipGetLastError());
+        rc = launch_rays(s, RT_QUERY_FAST, s->primary_rays.p, n, d_hits + (size_t)r * (size_t)w, st);
+        if (rc != RT_OK) return rc;
+    }
+    return end_op(s, st);
+}
 
 int rt_query_rays_device(rt_scene* s, int32_t mode, const rt_ray* d_rays, int64_t n, rt_hit* d_hits, void* stream)
 {

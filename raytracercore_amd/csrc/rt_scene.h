@@ -1,6 +1,6 @@
 // rt_scene.h -- the scene object behind the C ABI and what the API's translation units share
 // (rtcore_api.hip, scene_upload.hip, api_frame.hip, api_debug.hip, api_query.hip, api_select.hip, api_render_rays.hip,
-// api_render_pixels.hip).
+// api_render_pixels.hip, api_adaptive.hip, api_denoise.hip).
 #pragma once
 #include <algorithm>
 #include <array>
@@ -185,6 +185,9 @@ struct rt_scene {
     DevBuf<rt_ray> query_rays;
     DevBuf<rt_hit> query_hits;
     std::array<hipEvent_t, 2> query_up_ev{};
+    // rt_primary_hits_device: one chunk of camera rays, made and read on the caller's stream (its own
+    // buffer: rt_query_rays fills query_rays from its copy stream)
+    DevBuf<rt_ray> primary_rays;
     // rt_occluded_rays: two chunks of segment ends and of answer bytes (its rays share query_rays and query_up_ev)
     DevBuf<double> occluded_t_max;
     DevBuf<unsigned char> occluded_out;

@@ -2,14 +2,16 @@
 and rt_adaptive_select_device in a loop, the image never leaving the device), toned with rt_tonemap_device.
 
 usage: python tools/render_adaptive.py SCENE [--size W H] [--tol T] [--min N] [--max N] [--batch N] [--seed S]
-                                       [--floor L] [--exposure E] [--traversal MODE] [--out PREFIX]
+                                       [--floor L] [--exposure E] [--traversal MODE] [--out PREFIX] [--denoise]
 
 SCENE is a scene file (or the name of one shipped in tests/golden/scenes).  A pixel is sampled in batches of
 --batch samples until the standard error of its mean luminance is at most --tol times that luminance (held
 up to --floor for dark pixels), between --min and --max samples (include/rtcore.h, "adaptive sampling").
 Writes PREFIX.npy / PREFIX.ppm (the ARGB codes as int32 [H, W] / a binary P6) and PREFIX_spp.npy /
 PREFIX_spp.ppm (the samples every pixel got, int32 [H, W] / grey, white = --max), and prints the samples
-taken against max x pixels.
+taken against max x pixels.  With --denoise the result also goes through GpuRaytracer.denoise (rt_primary_hits_device
+and rt_denoise_device, include/rtcore.h "denoising", its default parameters) and is written toned the same way as
+PREFIX_denoised.npy / PREFIX_denoised.ppm.
 """
 from __future__ import annotations
 
@@ -44,6 +46,7 @@ def main(argv=None) -> int:
     ap.add_argument("--exposure", type=float, default=1.0)
     ap.add_argument("--traversal", default="AUTO", choices=["AUTO", "BRUTE", "GROUPED", "BVH"])
     ap.add_argument("--out", default="adaptive")
+    ap.add_argument("--denoise", action="store_true")
     a = ap.parse_args(argv)
     if a.batch < 1 or a.min_spp < 1 or a.max_spp < a.min_spp or not a.tol >= 0 or not a.floor > 0:
         ap.error("need --batch >= 1, 1 <= --min <= --max, --tol >= 0 and --floor > 0")
@@ -66,6 +69,12 @@ def main(argv=None) -> int:
                               d_argb.data_ptr(), (amb.r, amb.g, amb.b), 1.0, a.exposure,
                               stream=torch.cuda.current_stream().cuda_stream)
             argb = d_argb.cpu().numpy()
+            if a.denoise:
+                filtered = gpu.denoise(res)
+                rc.tonemap_device(filtered.data_ptr(), res["samples"].data_ptr(), res["misses"].data_ptr(), W, H,
+                                  d_argb.data_ptr(), (amb.r, amb.g, amb.b), 1.0, a.exposure,
+                                  stream=torch.cuda.current_stream().cuda_stream)
+                argb_denoised = d_argb.cpu().numpy()
         spp = res["spp"].cpu().numpy().astype(np.int32)
     finally:
         gpu.close()
@@ -74,10 +83,14 @@ def main(argv=None) -> int:
     write_ppm(a.out + ".ppm", argb)
     np.save(a.out + "_spp.npy", spp)
     write_ppm(a.out + "_spp.ppm", spp_map_argb(spp, cap))
+    if a.denoise:
+        np.save(a.out + "_denoised.npy", argb_denoised)
+        write_ppm(a.out + "_denoised.ppm", argb_denoised)
     total = int(spp.sum())
     print(f"{os.path.basename(path)} {W}x{H}: tol {a.tol}, {int(res['params'].min_samples)}..{cap} spp in batches of {a.batch}: "
           f"{len(res['counts'])} passes, {total} samples of {cap * W * H} ({total / (cap * W * H):.1%}), {res['rays']} rays, "
-          f"{int((spp < cap).sum())} of {W * H} pixels stopped early -> {a.out}.npy, {a.out}.ppm, {a.out}_spp.npy, {a.out}_spp.ppm")
+          f"{int((spp < cap).sum())} of {W * H} pixels stopped early -> {a.out}.npy, {a.out}.ppm, {a.out}_spp.npy, {a.out}_spp.ppm"
+          + (f", {a.out}_denoised.npy, {a.out}_denoised.ppm" if a.denoise else ""))
     return 0
 
 
