@@ -281,6 +281,18 @@ int rt_debug_scene_bound(const rt_prim* prims, int32_t n_prims, float* lo, float
 int rt_debug_block_cull(const rt_prim* prims, int32_t n_prims, const rt_camera* camera, int32_t width, int32_t height,
                         int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t band, int32_t band_stride,
                         int32_t band_offset, uint8_t* dead, int64_t cap, int32_t* info);
+/* Host only (no device needed): the start rows of a brute-force launch -- a wave that opens work items
+   builds every camera ray of those items with all its lanes and keeps them as 16-B rows in a buffer
+   of its own, and a lane's sample start loads its row instead of building the ray; the results are
+   the same bit for bit (RTCORE_START_ROWS=0 turns them off).  kernel 0 (BRUTE), 1 (GROUPED), 2 / 3
+   (the BVH kernels: never); camera: its kind and depth of field decide; (w, h, spp): the launch, chunks
+   > 0 that many chunks per pixel (as RTCORE_PATH_CHUNKS), 0 the tuned count; grid_blocks: blocks of
+   256 threads of the persistent grid; flags: 1 an instrumented launch, 2 a scene with vertex-normal
+   triangles (neither gets them).  info[0..2] = {rows per wave, bytes of the buffer, samples per work
+   item}; rows and bytes are 0 when off.  Off for more than 16 samples per item and for a buffer over
+   256 MiB.  Returns 1 (on), 0 (off) or a negative rt_status. */
+int rt_debug_start_rows(int32_t kernel, const rt_camera* camera, int32_t w, int32_t h, int32_t spp, int32_t chunks,
+                        int32_t grid_blocks, int32_t flags, int64_t* info);
 /* Measurement of a wavefront split's traversal stage.  rt_debug_ray_log: while
    the next instrumented launch of a BVH kernel runs (rt_scene_set_stats; one launch only, then
    logging is off again), the kernel appends every finished query

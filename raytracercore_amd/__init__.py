@@ -297,6 +297,7 @@ def load_library(path: str = "") -> C.CDLL:
         "rt_debug_scene_bound": (C.c_int, [P(rt_prim), C.c_int32, P(C.c_float), P(C.c_float), P(C.c_float)]),
         "rt_debug_block_cull": (C.c_int, [P(rt_prim), C.c_int32, P(rt_camera)] + [C.c_int32] * 9 +
                                 [P(C.c_uint8), C.c_int64, P(C.c_int32)]),
+        "rt_debug_start_rows": (C.c_int, [C.c_int32, P(rt_camera)] + [C.c_int32] * 6 + [P(C.c_int64)]),
         "rt_debug_ray_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
         "rt_debug_vn_rehit": (C.c_int, [P(C.c_double), P(C.c_double), P(C.c_double), C.c_int32, C.c_double,
                                         C.c_double, P(C.c_float), P(C.c_int32), P(C.c_double), P(C.c_double)]),
@@ -481,6 +482,22 @@ def block_cull(prims: Sequence[rt_prim], camera: rt_camera, size: Tuple[int, int
     if live < 0:
         _check(live)
     return dead[:bx * by].reshape(by, bx).astype(bool), int(live)
+
+
+def start_rows(kernel: int, camera: rt_camera, w: int, h: int, spp: int, chunks: int = 0, grid_blocks: int = 1792,
+               instrumented: bool = False, vertex_normals: bool = False) -> dict:
+    """rt_debug_start_rows (host code, no GPU): whether a brute-force launch over a w x h tile at spp
+    samples per pixel keeps its camera rays in start rows, and what they take -- on, rows (per wave),
+    bytes (of the buffer) and chunk (samples per work item).  grid_blocks: blocks of the persistent
+    grid (default: 256 CUs x 7)."""
+    lib = load_library()
+    cam = rt_camera.from_buffer_copy(camera)
+    info = (C.c_int64 * 3)()
+    on = lib.rt_debug_start_rows(kernel, C.byref(cam), w, h, spp, chunks, grid_blocks,
+                                 int(bool(instrumented)) | int(bool(vertex_normals)) << 1, info)
+    if on < 0:
+        _check(on)
+    return {"on": bool(on), "rows": int(info[0]), "bytes": int(info[1]), "chunk": int(info[2])}
 
 
 def ref_bvh_export(prims: Sequence[rt_prim]) -> Tuple[np.ndarray, np.ndarray, int, int]:

@@ -534,6 +534,26 @@ int rt_debug_block_cull(const rt_prim* prims, int32_t n_prims, const rt_camera* 
     return live;
 }
 
+// Host only: the start rows run_path would plan for such a launch (make_params_for, plan_start_rows).
+int rt_debug_start_rows(int32_t kernel, const rt_camera* camera, int32_t w, int32_t h, int32_t spp, int32_t chunks,
+                        int32_t grid_blocks, int32_t flags, int64_t* info)
+{
+    if (kernel < 0 || kernel > 3 || !camera || w <= 0 || h <= 0 || spp <= 0 || chunks < 0 || grid_blocks <= 0 || !info ||
+        (camera->kind != RT_CAMERA_FRUSTUM && camera->kind != RT_CAMERA_ORTHO)) {
+        set_error("rt_debug_start_rows: bad argument");
+        return RT_ERR_ARG;
+    }
+    CameraD camd;
+    CameraF camf;
+    camera_init(*camera, w, h, camd, camf);
+    const PathParams p = make_params_for(kernel, chunks, 0, 0, 0, w, h, spp, 0, 0, 0.0);
+    const StartRowsPlan sr = plan_start_rows(kernel, (flags & 1) != 0, (flags & 2) != 0, camf.kind, camf.dof != 0.0f, p.chunk, grid_blocks);
+    info[0] = sr.rows;
+    info[1] = (int64_t)sr.bytes;
+    info[2] = p.chunk;
+    return sr.on ? 1 : 0;
+}
+
 int rt_parse_scene(const char* text, rt_scene_params* params, rt_prim* prims, int32_t* n_prims, rt_camera* cameras,
                    int32_t* n_cameras)
 {

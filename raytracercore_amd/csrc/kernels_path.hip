@@ -809,11 +809,19 @@ __device__ __forceinline__ Ray3 camera_ray(const CamT& c, float x, float y)
 // LEAN (the brute-force kernels): x + U as one fma of the integer draw (U = h * 2^-24 exactly, so the
 // single rounding is the add's: the same value); the BVH kernels keep the add (their register
 // allocation moved spills into the traversal loop with it, C4 44.4 -> 55.9 ms)
+// sample_point: the sample's point in its pixel, subX and subY (the start rows' loop in refill
+// draws them the same way)
+template <bool LEAN>
+__device__ __forceinline__ void sample_point(int x, int y, Sample& S, float& sx, float& sy)
+{
+    sx = LEAN ? fmaf((float)rt_rng_next24(&S.rng), 0x1p-24f, (float)x) : (float)x + next_u(S.rng);
+    sy = LEAN ? fmaf((float)rt_rng_next24(&S.rng), 0x1p-24f, (float)y) : (float)y + next_u(S.rng);
+}
 template <bool LEAN = false, class CamT>
 __device__ __forceinline__ void start_sample(const CamT& cam, int x, int y, Sample& S)
 {
-    const float sx = LEAN ? fmaf((float)rt_rng_next24(&S.rng), 0x1p-24f, (float)x) : (float)x + next_u(S.rng);
-    const float sy = LEAN ? fmaf((float)rt_rng_next24(&S.rng), 0x1p-24f, (float)y) : (float)y + next_u(S.rng);
+    float sx, sy;
+    sample_point<LEAN>(x, y, S, sx, sy);
     const Ray3 r = camera_ray(cam, sx, sy);
     S.o = r.o;
     S.d = r.d;
@@ -1333,7 +1341,47 @@ __device__ __forceinline__ int item_sample(const Lane& L, const ParT& p)
 // both GetCameraRay draws used.  An entry at or past p.n_frame_px opens no item.  The brute-force
 // kernels keep fx, fy in the lane; the BVH kernel reads the entry again at each sample start, as it
 // decodes a tile's item again (list_pixel).
-template <bool NT, int SRC = ITEMS_TILE, class ParT, class SceneT, class CamT>
+// ROWS (the brute-force tile instances that are not instrumented and have no vertex normals, whose
+// instances already spill): start rows, PathParams::starts.
+// A lane that starts a camera sample does so alone or with a few others: the lanes of a wave finish
+// their samples at different bounces, so the start's ~60 VALU instructions were issued in most
+// iterations for a tenth of the lanes.  The item open is where a wave's lanes are together (p.batch)
+// and know every sample they will start: there the wave runs the start of each of the item's
+// samples, the same functions on the same inputs, and stores one 16-B row per sample, direction
+// and rng state; the sample start loads the lane's row and finishes camera_ray's last line.  A lane
+// reads only rows it wrote itself, so no fence; lanes that open items without the rest of the wave
+// run the loop under their mask.  The host sets the pointer only for a frustum camera without depth
+// of field (plan_start_rows); a scene-specialised build knows the camera's kind and leaves the code out.
+template <bool NT, int SRC, bool ROWS, class ParT, class CamT>
+__device__ __forceinline__ bool start_rows_on(const ParT& p, [[maybe_unused]] const CamT& cam)
+{
+    if constexpr (NT || SRC != ITEMS_TILE || !ROWS) {
+        return false;
+    } else {
+#ifdef RT_SCENE_CONST
+        if (!cam_frustum(cam) || cam_dof(cam)) return false;
+#endif
+        return p.starts != nullptr;
+    }
+}
+typedef float row_f4 __attribute__((ext_vector_type(4)));
+#ifdef __HIP_DEVICE_COMPILE__
+typedef __attribute__((address_space(1))) row_f4 row_g4;      // global: plain global_load / global_store
+typedef __attribute__((address_space(1))) unsigned char row_g1;
+#else
+typedef row_f4 row_g4;
+typedef unsigned char row_g1;
+#endif
+// byte offset of row r of this lane: the buffer stays below 4 GiB (plan_start_rows' cap)
+template <class ParT>
+__device__ __forceinline__ unsigned start_row_offset(const ParT& p, unsigned r, int lane)
+{
+    // (blocks of 256 threads: 4 waves)
+    const unsigned wave = blockIdx.x * 4u + (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    return (((wave * (unsigned)p.start_rows + r) << 6) | (unsigned)lane) * 16u;
+}
+
+template <bool NT, int SRC = ITEMS_TILE, bool ROWS = false, class ParT, class SceneT, class CamT>
 __device__ __forceinline__ void refill(Lane& L, Sample& S, const ParT& p, const SceneT& s, const CamT& cam, int lane,
                                       unsigned total)
 {
@@ -1462,6 +1510,21 @@ __device__ __forceinline__ void refill(Lane& L, Sample& S, const ParT& p, const 
         } else {
             L.pool_next += k;
         }
+        // The rows of the items just opened (k: wave-uniform; the lanes that asked had no open item).
+        if (k != 0 && start_rows_on<NT, SRC, ROWS>(p, cam)) {
+            const unsigned n = need && L.item_open ? L.cnt >> 16 : 0u;
+            row_g1* const rows = (row_g1*)(unsigned long long)p.starts;
+            for (unsigned j = 0; j < (unsigned)p.start_rows; j++) {
+                if (j < n) { // start_sample's ray, built in the lane's own sample registers: it has no sample
+                    S.rng = rt_rng_from_pixel_key(L.pkey, p.sample_base + (unsigned long long)(L.s_next + (int)j));
+                    float sx, sy;
+                    sample_point<true>(L.fx, L.fy, S, sx, sy);
+                    S.d = camera_ray(cam, sx, sy).d;
+                    const row_f4 v = {S.d.x, S.d.y, S.d.z, __uint_as_float(S.rng.x)};
+                    *(row_g4*)(rows + start_row_offset(p, j, lane)) = v;
+                }
+            }
+        }
     }
     if constexpr (SRC == ITEMS_RAYS) {
         if (L.active && L.item_open && !L.live && L.cnt >= 65536u) {
@@ -1487,6 +1550,23 @@ __device__ __forceinline__ void refill(Lane& L, Sample& S, const ParT& p, const 
         return;
     }
     if (L.active && L.item_open && !L.live && L.cnt >= 65536u) {
+        if (start_rows_on<NT, SRC, ROWS>(p, cam)) {
+            // the sample's row: the samples and misses the item has finished.  The writes to S in
+            // start_sample's order: with another order the two branches' stores were merged by
+            // address and four of S's fields stayed in scratch.
+            const unsigned r = (L.cnt & 0xFFu) + ((L.cnt >> 8) & 0xFFu);
+            const row_g1* const rows = (const row_g1*)(unsigned long long)p.starts;
+            const row_f4 v = *(const row_g4*)(rows + start_row_offset(p, r, lane));
+            const V3 d = v3(v.x, v.y, v.z);
+            S.rng.x = __float_as_uint(v.w);
+            S.o = madd(d, cam.image_plane, xyz(cam.position)); // camera_ray's last line
+            S.d = d;
+            S.tint = v3(1.0f, 1.0f, 1.0f);
+            S.bounce = 0;
+            S.prev = -1;
+            L.live = true;
+            return;
+        }
         int fx = L.fx, fy = L.fy;
         if (NT && SRC == ITEMS_PIXELS) { // the list entry again (it stays in the cache between an item's samples)
             const unsigned pix = p.pixel_list[item_ray(L.item, p)];
@@ -1653,9 +1733,10 @@ __device__ __forceinline__ void path_body(const CameraF* __restrict__ camp, cons
         const auto& sc = pq->scene;
 #endif
 #if defined(RT_SCENE_CONST) && RT_SCENE_CONST_CAMERA
-        refill<false>(L, S, *pq, sc, *(const CameraF*)kCameraW, lane, total); // the camera compiled in too
+        // (the camera compiled in too)
+        refill<false, ITEMS_TILE, !STATS && !VN>(L, S, *pq, sc, *(const CameraF*)kCameraW, lane, total);
 #else
-        refill<false, SRC>(L, S, *pq, sc, *cp, lane, total);
+        refill<false, SRC, !STATS && !VN>(L, S, *pq, sc, *cp, lane, total);
 #endif
         if (!__any(L.active)) break;
         if (STATS) t1 = __builtin_readcyclecounter();

@@ -226,6 +226,28 @@ int64_t render_rays_max_n(int kernel, int spp)
     return std::min<int64_t>(blocks * 64, (int64_t)1 << 30);
 }
 
+// Start rows: a wave that opens items builds every camera ray of those items with all its lanes and
+// keeps them in a row buffer of its own; the sample start, which the lanes reach one by one, loads
+// the lane's row instead of building the ray (refill).  For the brute-force tile launches that are
+// not instrumented, of scenes without vertex-normal triangles (those instances spill already and
+// would spill more), with a frustum camera without depth of field (another camera draws more per
+// start and would need two rows per sample).  Up to kStartRowsMaxChunk samples per item: the loop at
+// the item open runs `chunk` times for every lane, and a lane that opens an item alone pays it alone.
+// The buffer is one row set per wave of the persistent grid; over kStartRowsCap the launch does
+// without.  RTCORE_START_ROWS=0 turns them off; read per launch, like RTCORE_SCENE_BOUND.
+StartRowsPlan plan_start_rows(int kernel, bool instrumented, bool vertex_normals, int camera_kind, bool dof, int chunk,
+                              int grid_blocks)
+{
+    const StartRowsPlan off{false, 0, 0};
+    if (kernel < 0 || kernel >= 2 || instrumented || vertex_normals || camera_kind != RT_CAMERA_FRUSTUM || dof) return off;
+    if (chunk < 1 || chunk > kStartRowsMaxChunk || grid_blocks < 1) return off;
+    if (const char* e = getenv("RTCORE_START_ROWS"))
+        if (atoi(e) == 0) return off;
+    const size_t bytes = (size_t)grid_blocks * 4u * (size_t)chunk * 64u * 16u;
+    if (bytes > kStartRowsCap) return off;
+    return StartRowsPlan{true, chunk, bytes};
+}
+
 // Band-set launch: tile row r is frame row ((r / band) * stride + offset) * band + r % band; the
 // kernel divides by a shift for power-of-two bands, else by the fp32 reciprocal.
 void set_band(PathParams& p, int band, int stride, int offset)

@@ -28,6 +28,20 @@ void set_band(PathParams& p, int band, int stride, int offset);
 // out while they fit in cap_words; returns the number of tickets.
 int64_t list_tickets(const PathParams& p, uint32_t* out, int64_t cap_words);
 
+// Start rows (PathParams::starts, refill in kernels_path.hip): whether a tile launch of `kernel` with
+// `chunk` samples per item on a grid of grid_blocks blocks of 256 gets them, and the buffer they take.
+// instrumented / vertex_normals: the launch runs an instance without them.  camera_kind / dof: the
+// camera's kind (rt_camera_kind) and whether it has depth of field.
+constexpr int kStartRowsMaxChunk = 16;          // rows per wave: an item's samples
+constexpr size_t kStartRowsCap = 256u << 20;    // bytes of the buffer (a 1080p frame at 256 spp: 79 MB)
+struct StartRowsPlan {
+    bool on;
+    int rows;      // per wave (= chunk), 0 when off
+    size_t bytes;  // grid_blocks * 4 waves * rows * 64 lanes * 16 B, 0 when off
+};
+StartRowsPlan plan_start_rows(int kernel, bool instrumented, bool vertex_normals, int camera_kind, bool dof, int chunk,
+                              int grid_blocks);
+
 // A band set (band, stride, offset) is frame rows {y : (y / band) % stride == offset}.
 int band_set_rows(int H, int band, int stride, int offset);
 int band_slot_rows(int H, int band, int stride); // largest band set of the split

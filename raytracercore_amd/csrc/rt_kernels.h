@@ -100,11 +100,20 @@ struct PathParams {
     // pixel_list[i] = fy * scene.width + fx, and an entry at or past n_frame_px is skipped.  The list's
     // fields share the rays' storage, so that the record keeps its size and no field moves: the kernels
     // that take it by value are as they were.
+    // Start rows, the brute-force tile instances only (run_path plans them, plan_start_rows; null / 0:
+    // off): float4 starts[wave][start_rows][64], wave = blockIdx.x * 4 + threadIdx.x / 64 of the
+    // persistent grid, start_rows = chunk.  A wave that opens items writes every camera sample of a
+    // lane's item as one row (direction xyz, the rng after GetCameraRay's two draws), all lanes
+    // together; a lane's sample start reads its own row back (refill).  The pointer shares the lists'
+    // storage (a tile launch has no list) and the count takes the padding after n_rays, so that the
+    // record keeps its size and no field moves.
     union {
         const double2* ray_list;    // four 16-B rows per ray (origin xy, origin zw, direction xy, direction zw)
         const uint32_t* pixel_list; // frame pixel indices
+        float4* starts;
     };
     unsigned int n_rays;        // rays or list entries of the launch (the items of the last block past it stay closed)
+    int start_rows;
     union {
         unsigned long long stream_base;
         struct {
@@ -124,6 +133,9 @@ struct PathParams {
     // One field (last, so that no other moves): the BVH kernels take this record by value.
     const unsigned int* cull;
 };
+static_assert(__builtin_offsetof(PathParams, start_rows) == __builtin_offsetof(PathParams, n_rays) + 4 &&
+                  __builtin_offsetof(PathParams, scene_bound) == __builtin_offsetof(PathParams, n_rays) + 16,
+              "start_rows takes the padding after n_rays");
 constexpr int kCullTable = 4;  // first table word of PathParams::cull
 constexpr int kRecRows = 6;    // sizeof(rt_debug_ray) / 16
 

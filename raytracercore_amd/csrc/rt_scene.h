@@ -166,6 +166,7 @@ struct rt_scene {
     DevBuf<rt_key2> pkeys;       // pixel-key table of the brute-force kernels (PathParams::pkeys)
     bool pkeys_valid = false;
     uint64_t pkeys_seed = 0;
+    DevBuf<float4> starts;       // start rows of the brute-force kernels (PathParams::starts), grown on demand
     DevBuf<int> stack_ovf;
     DevBuf<unsigned long long> rays;
     DevBuf<float4> partial;

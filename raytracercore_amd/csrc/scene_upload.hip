@@ -777,6 +777,16 @@ int run_path(rt_scene* s, PathParams& p, unsigned long long* d_rays, hipStream_t
         }
         p.pkeys = s->pkeys.p;
     }
+    // Start rows (plan_start_rows, launch_params.cpp): one row set per wave of the grid launched.
+    p.starts = nullptr;
+    p.start_rows = 0;
+    const StartRowsPlan sr = plan_start_rows(s->variant >> 1, s->stats_on || s->tracing, s->dev.n_vn > 0, s->camf.kind,
+                                             s->camf.dof != 0.0f, p.chunk, jit ? jit_grid : grid);
+    if (sr.on) {
+        HIP_TRY(s->starts.reserve(sr.bytes / sizeof(float4)));
+        p.starts = s->starts.p;
+        p.start_rows = sr.rows;
+    }
     const PathParams* pa = nullptr;
     const int urc = upload_params(s, p, stream, &pa);
     if (urc != RT_OK) return urc;

@@ -23,6 +23,7 @@ TRACE_CALL = ("            if (query)\n"
               "                trace_brute<CULL, STATS>(sc, groups, tests, rects, frames, boxes, xf, S.o, S.d, S.prev, b, cnt.tris,\n"
               "                                         cnt.sphs, cnt.nodes);\n")
 BOUNCE_CALL = "            bounce<VN, false, false, STATS>(L, S, sc, R, vnormals, tests, pq->prims_d, b, *pq);\n"
+START_CALL = "        start_sample<!NT>(cam, fx, fy, S);\n"  # refill's last branch
 RAYS_LINE = "        wave_rays += (unsigned)__popcll(__ballot(L.live)); // one Scene.RayTrace per live lane\n"
 
 # path_kernel_bvh's node fetch (the lambda handed to walk_step); the replacements return the Node4Q
@@ -52,6 +53,20 @@ PATCHES = {
                    "            start_sample<true>(*cp, L.fx, L.fy, S2);\n"
                    "            if (S2.o.x + S2.d.y == 1234.5f) pq->partial[0].x = 1.0f;\n"
                    "        }\n" + RAYS_LINE)],
+    # the real sample start repeated where it runs, in refill's last branch and so under its lane mask
+    # (DUP_START above runs for every live lane): the key, the sample index and the pixel pass through
+    # empty asm so that nothing of the copy is shared with the original; the brute-force kernels only
+    "DUP_START_INPLACE": [(START_CALL,
+                           START_CALL +
+                           "        if (!NT) {\n"
+                           "            rt_key2 k2 = L.pkey;\n"
+                           "            int s2 = item_sample<NT>(L, p), fx2 = fx, fy2 = fy;\n"
+                           "            asm volatile(\"\" : \"+v\"(k2.a), \"+v\"(k2.b), \"+v\"(s2), \"+v\"(fx2), \"+v\"(fy2));\n"
+                           "            Sample S2;\n"
+                           "            S2.rng = rt_rng_from_pixel_key(k2, p.sample_base + (unsigned long long)s2);\n"
+                           "            start_sample<true>(cam, fx2, fy2, S2);\n"
+                           "            if (S2.d.x + S2.d.y + S2.d.z + S2.o.x == 1234.5f && S2.rng.x == 77u) p.partial[0].x = 1.0f;\n"
+                           "        }\n")],
     # no depth of field in the sample start
     "NO_DOF": [("    if (cam_dof(cam)) {\n", "    if (false) {\n")],
     # the bounce direction never renormalised (round 3's brute-force form)
@@ -229,8 +244,9 @@ def main() -> None:
     with open(kp, "w") as f:
         f.write(apply(src, names))
     jobs = str(min(16, os.cpu_count() or 8))
-    subprocess.run(["make", "-s", "-C", dst, "-j" + jobs, "OUT=" + out, "EXTRA=" + extra], check=True)
-    print(os.path.join(out, "librtcore_hip.so"))
+    lib = os.path.join(out, "librtcore_hip.so")  # the library alone: the copy has no tests/host for worker_host
+    subprocess.run(["make", "-s", "-C", dst, "-j" + jobs, "OUT=" + out, "EXTRA=" + extra, lib], check=True)
+    print(lib)
 
 
 if __name__ == "__main__":
