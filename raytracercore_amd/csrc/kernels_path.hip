@@ -1198,6 +1198,10 @@ struct Lane {
     unsigned cnt; // item bookkeeping: samples (bits 0-7) | misses (8-15) | samples left (16-31)
     unsigned pool_next, pool_end;
     unsigned split_j; // lane 0: item ranges (after its own) this wave found spent (PathParams::n_split)
+    // sample rounds (refill, ROUNDS instances; wave-uniform): the open ticket runs in rounds, and the
+    // wave's ray count, modulo 2^32, when it drew that ticket
+    bool rounds;
+    unsigned ticket_mark;
 };
 
 __device__ __forceinline__ void lane_init(Lane& L)
@@ -1211,6 +1215,8 @@ __device__ __forceinline__ void lane_init(Lane& L)
     L.cnt = 0;
     L.pool_next = L.pool_end = 0;
     L.split_j = 0;
+    L.rounds = false;
+    L.ticket_mark = 0;
 }
 
 // Lanes without a sample in flight close finished items and take new ones from the wave's
@@ -1381,10 +1387,29 @@ __device__ __forceinline__ unsigned start_row_offset(const ParT& p, unsigned r, 
     return (((wave * (unsigned)p.start_rows + r) << 6) | (unsigned)lane) * 16u;
 }
 
-template <bool NT, int SRC = ITEMS_TILE, bool ROWS = false, class ParT, class SceneT, class CamT>
+// ROUNDS (the instances that have ROWS, for the same reason): sample rounds, PathParams::sample_rounds.
+// A wave opens a ticket's 64 items together and closes them together (p.batch), so the lanes whose
+// paths end early wait at the ticket's end in any case; and where nearly every path runs to the
+// recursion limit (a closed room) some lane of the 64 is at full length in every sample.  In rounds
+// that wait is taken at each sample's end instead: a lane with samples left starts the next one only
+// once no lane of the wave is live, so the wave starts sample k of the ticket together.  The wave's
+// iterations stay what they were (sum over samples of the longest path against the longest sum of
+// paths, +0.01 % on bounce.txt, tools/round_sim.py), and every live lane is then at the same bounce
+// in every iteration: the sample start below, shade's body past the recursion limit and the sample's
+// end run for all lanes in one iteration of recursion + 1 and are branched over in the others.
+// Where path lengths differ the wait is real (die.txt +15 %), so each ticket chooses (ticket_rounds,
+// rt_kernels.h; rays_now: the wave's ray count).  The vote is taken here, outside the divergent code,
+// and the mode is wave-uniform.
+// Progress: a lane held back waits for live lanes only, never for a lane that waits, and a live lane
+// ends within recursion + 1 iterations; once none is live every lane with samples left starts.  So
+// the wait is bounded whatever p.batch is and however the items were opened.
+template <bool NT, int SRC = ITEMS_TILE, bool ROWS = false, bool ROUNDS = false, class ParT, class SceneT, class CamT>
 __device__ __forceinline__ void refill(Lane& L, Sample& S, const ParT& p, const SceneT& s, const CamT& cam, int lane,
-                                      unsigned total)
+                                      unsigned total, [[maybe_unused]] unsigned rays_now = 0)
 {
+    static_assert(!ROUNDS || (!NT && SRC == ITEMS_TILE), "sample rounds: the brute-force tile instances");
+    bool go = true; // wave-uniform
+    if constexpr (ROUNDS) go = !L.rounds || __ballot(L.live) == 0ull;
     const bool need = L.active && !L.live && (!L.item_open || L.cnt < 65536u);
     if (need && L.item_open) {
         const float4 part = make_float4(L.ar, L.ag, L.ab, __uint_as_float((L.cnt & 0xFFu) | ((L.cnt & 0xFF00u) << 8)));
@@ -1442,6 +1467,11 @@ __device__ __forceinline__ void refill(Lane& L, Sample& S, const ParT& p, const 
                 }
             }
             got = __builtin_amdgcn_readfirstlane(got);
+            if constexpr (ROUNDS) { // the new ticket's mode, from the rays of the one before (pool_end 0: none)
+                L.rounds = __builtin_amdgcn_readfirstlane(
+                               (int)ticket_rounds(p, s.recursion, L.pool_end == 0u, rays_now - L.ticket_mark)) != 0;
+                L.ticket_mark = rays_now;
+            }
             fresh = linear ? got : total; // all spent -> total, which ends the lane
             if (!linear && (got >> 28) < (unsigned)p.n_split)
                 ticket_items(p, got >> 28, got & 0xFFFFFFFu, fresh, fresh_len);
@@ -1549,7 +1579,7 @@ __device__ __forceinline__ void refill(Lane& L, Sample& S, const ParT& p, const 
         }
         return;
     }
-    if (L.active && L.item_open && !L.live && L.cnt >= 65536u) {
+    if (go && L.active && L.item_open && !L.live && L.cnt >= 65536u) {
         if (start_rows_on<NT, SRC, ROWS>(p, cam)) {
             // the sample's row: the samples and misses the item has finished.  The writes to S in
             // start_sample's order: with another order the two branches' stores were merged by
@@ -1734,9 +1764,11 @@ __device__ __forceinline__ void path_body(const CameraF* __restrict__ camp, cons
 #endif
 #if defined(RT_SCENE_CONST) && RT_SCENE_CONST_CAMERA
         // (the camera compiled in too)
-        refill<false, ITEMS_TILE, !STATS && !VN>(L, S, *pq, sc, *(const CameraF*)kCameraW, lane, total);
+        refill<false, ITEMS_TILE, !STATS && !VN, !STATS && !VN>(L, S, *pq, sc, *(const CameraF*)kCameraW, lane, total,
+                                                         (unsigned)wave_rays);
 #else
-        refill<false, SRC, !STATS && !VN>(L, S, *pq, sc, *cp, lane, total);
+        refill<false, SRC, !STATS && !VN, !STATS && !VN && SRC == ITEMS_TILE>(L, S, *pq, sc, *cp, lane, total,
+                                                                              (unsigned)wave_rays);
 #endif
         if (!__any(L.active)) break;
         if (STATS) t1 = __builtin_readcyclecounter();

@@ -165,6 +165,12 @@ PathParams make_params_for(int kernel, int chunks_over, int pool_over, int x0, i
     // Kernel ms, one call, three rounds: C2 16.01-16.05 -> 14.97-15.00.
     p.scene_bound = 1;
     if (const char* e = getenv("RTCORE_SCENE_BOUND")) p.scene_bound = atoi(e) != 0 ? 1 : 0;
+    // Brute-force tile kernels: sample rounds (refill; ticket_rounds in rt_kernels.h has the rule).  The
+    // result is the same either way: only when a lane starts its next sample changes.
+    // RTCORE_SAMPLE_ROUNDS=0 turns them off, 2 runs every ticket in rounds, 1 (the default) lets each
+    // wave choose per ticket; read per launch, like RTCORE_SCENE_BOUND.
+    p.sample_rounds = 1;
+    if (const char* e = getenv("RTCORE_SAMPLE_ROUNDS")) p.sample_rounds = std::max(0, std::min(2, atoi(e)));
     // BVH kernels: the shading phase runs once 28 lanes wait; a leaf step once 12 lanes are blocked
     // on a pending leaf.  Round 5, C4 with the walls as outer records (profiles/r05/c4_outer_sweep.log):
     // refill 24 / 28 / 32 at spec 16: 44.0 / 43.6 / 43.6 ms; spec 12 / 16 / 20 at refill 24: 43.8 /

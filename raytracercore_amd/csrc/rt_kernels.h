@@ -123,6 +123,10 @@ struct PathParams {
     };
     int scene_bound;            // flat brute-force kernel: 1 = a wave of camera rays that all miss the scene bound
                                 // skips its query (RTCORE_SCENE_BOUND, make_params_for)
+    // Sample rounds, the brute-force tile instances only (refill; RTCORE_SAMPLE_ROUNDS, make_params_for):
+    // 0 no ticket runs in rounds, 2 every ticket, 1 those ticket_rounds below picks.  It takes the
+    // padding after scene_bound, so that the record keeps its size and no field moves.
+    int sample_rounds;
     // The block cull (block_cull.h, run_path): null, or a device record of the launch's 8x8 blocks whose
     // pixels can see the scene.  The launch is then planned over those live blocks alone, numbered
     // 0 .. n_live - 1 in their original order (n_pad = 64 n_live; blocks_x stays the window's):
@@ -136,6 +140,9 @@ struct PathParams {
 static_assert(__builtin_offsetof(PathParams, start_rows) == __builtin_offsetof(PathParams, n_rays) + 4 &&
                   __builtin_offsetof(PathParams, scene_bound) == __builtin_offsetof(PathParams, n_rays) + 16,
               "start_rows takes the padding after n_rays");
+static_assert(__builtin_offsetof(PathParams, sample_rounds) == __builtin_offsetof(PathParams, scene_bound) + 4 &&
+                  __builtin_offsetof(PathParams, cull) == __builtin_offsetof(PathParams, scene_bound) + 8,
+              "sample_rounds takes the padding after scene_bound");
 constexpr int kCullTable = 4;  // first table word of PathParams::cull
 constexpr int kRecRows = 6;    // sizeof(rt_debug_ray) / 16
 
@@ -158,6 +165,30 @@ __host__ __device__ inline void ticket_items(const ParT& p, unsigned g, unsigned
         len = p.tail_len;
     }
     first = p.split_start[g] + (blk << (p.log2_chunks + 6)) + off;
+}
+
+// Sample rounds: does the ticket a wave draws now run in rounds (refill holds every lane at its
+// sample's end until no lane of the wave is live, so that the wave starts its samples together)?
+// Rounds cost no wave iteration where the paths of a ticket are equally long, and many where they
+// are not, so a wave chooses per ticket, from what its previous ticket was like.  first: the wave has
+// had no ticket yet, and runs this one free.  prev_rays: the rays the wave traced since it drew its
+// previous ticket.  Rounds when that ticket's paths nearly all ran to the recursion limit, at least
+// kRoundsNum / kRoundsDen of pool x chunk samples x (recursion + 1) rays (bounce.txt: a closed room).
+// A ticket whose samples all missed says nothing about the next one: rounds after it as well cost
+// die.txt's silhouette blocks their ragged paths (die4k +0.5 %, DESIGN appendix A) and bought
+// bounce.txt nothing.  A short last ticket counts against the full one, so it can only fall below
+// the bound.  The ray count
+// is taken modulo 2^32; a ticket has fewer rays than that up to recursion 16383, and past it the
+// choice, never a result, may go wrong.  Wave-uniform in the kernels; the host check
+// (tests/host/rounds_rule_check.cpp) calls it too.
+constexpr unsigned kRoundsNum = 4, kRoundsDen = 5; // T = 0.8 (tools/round_sim.py)
+template <class ParT>
+__host__ __device__ inline bool ticket_rounds(const ParT& p, int recursion, bool first, unsigned prev_rays)
+{
+    if (p.sample_rounds != 1) return p.sample_rounds == 2;
+    if (first) return false;
+    const unsigned long long samples = (unsigned long long)(unsigned)p.pool * (unsigned long long)(unsigned)p.chunk;
+    return (unsigned long long)prev_rays * kRoundsDen >= samples * (unsigned long long)(unsigned)(recursion + 1) * kRoundsNum;
 }
 
 // Trace-only kernel over a ray list (rt_debug_trace_rays): the wide BVH's speculative traversal
