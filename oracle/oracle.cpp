@@ -87,13 +87,146 @@ V4 random_shine(S& rs, V4 dir, double shininess)
     return create_horizon(dir, z, theta);
 }
 
+// A sampler that counts its draws (the bounce step reports how many it took).
+template <class S>
+struct Counted {
+    S& s;
+    int n = 0;
+    double next()
+    {
+        n++;
+        return s.next();
+    }
+};
+
+// One bounce of GetColor after the closest hit (Raytracer.cs:100-244): what it decided and made.
+struct Step {
+    int type = 0;        // rt_bounce_type: 1 diffuse .. 5 emission, 6 pure black
+    bool go_on = false;  // the path continues with `out`
+    Ray out{v4(0, 0, 0, 0), v4(0, 0, 0, 0)};
+    Col factor = col(0); // new tint * max(total, 1)
+    double cs = 0, fresnel = std::nan("");
+    int draws = 0;
+    // decision margins (+inf where the decision is not taken)
+    double m_lobe = kInf, m_sin = kInf, m_cos = kInf, m_spec = kInf;
+};
+
+// The body of GetColor's loop from RandomShine to the tint factor, for the ray `ray` as it was
+// traced and its hit.  get_color and orc_shade_steps both run this one function.
+template <class S>
+Step shade_step(const Scene& sc, const Ray& ray, const Hit& hit, S& sampler)
+{
+    Step st;
+    Counted<S> rs{sampler};
+    const Prim& pr = sc.prims[hit.prim];
+    Ray out{v4(0, 0, 0, 0), v4(0, 0, 0, 0)};
+    bool have_out = false;
+    V4 rough = random_shine(rs, hit.normal, pr.shininess);
+    double diff_lum = lum(pr.diffuse), spec_lum = lum(pr.specular()), refr_lum = lum(pr.refraction()),
+           emis_lum = lum(pr.emission);
+    double cs = -dot(rough, ray.d);
+    st.cs = cs;
+    double cos_out = 0, ior_ratio = 0;
+    if (((refr_lum > 0) | (spec_lum > 0)) && pr.refractive_index != 0) st.m_cos = std::fabs(cs);
+    if (((refr_lum > 0) | (spec_lum > 0)) && pr.refractive_index != 0 && cs >= 0) {
+        double ior_in, ior_out;
+        if (hit.inside) {
+            ior_in = pr.refractive_index;
+            ior_out = sc.air_ior;
+        } else {
+            ior_in = sc.air_ior;
+            ior_out = pr.refractive_index;
+        }
+        ior_ratio = ior_in / ior_out;
+        double sin_out = ior_ratio * std::sqrt(1 - (cs * cs));
+        st.m_sin = std::fabs(sin_out - 1);
+        if (sin_out >= 1) {
+            refr_lum = 0;
+            st.fresnel = 1;
+        } else {
+            cos_out = std::sqrt(1 - (sin_out * sin_out));
+            double rs_ = ((ior_out * cs) - (ior_in * cos_out)) / ((ior_out * cs) + (ior_in * cos_out));
+            double rp = ((ior_in * cs) - (ior_out * cos_out)) / ((ior_in * cs) + (ior_out * cos_out));
+            double ratio = ((rs_ * rs_) + (rp * rp)) / 2;
+            spec_lum *= ratio;
+            refr_lum *= 1 - ratio;
+            st.fresnel = ratio;
+        }
+    } else {
+        refr_lum = 0;
+    }
+    double total = diff_lum + spec_lum + refr_lum + emis_lum;
+    if (total <= 0) {
+        st.type = RT_BOUNCE_PURE_BLACK;
+        st.draws = rs.n;
+        return st;
+    }
+    Col new_tint = col(0);
+    double ray_rand = rs.next() * total;
+    {
+        double edge = 0;
+        for (double l : {refr_lum, spec_lum, diff_lum})
+            if (l != 0) {
+                edge += l;
+                st.m_lobe = std::min(st.m_lobe, std::fabs(ray_rand - edge) / total);
+            }
+    }
+    if (refr_lum != 0 && (ray_rand -= refr_lum) <= 0) {
+        V4 od = (rough * -cos_out) + ((ray.d + (rough * cs)) * ior_ratio);
+        out = Ray{hit.pos, od};
+        have_out = true;
+        new_tint = pr.refraction();
+        if (hit.inside) new_tint = col(1);
+        st.type = RT_BOUNCE_TRANSMITTED;
+    } else if (spec_lum != 0 && (ray_rand -= spec_lum) <= 0) {
+        V4 od = ray.d + (rough * (cs * 2)); // Raytracer.Reflection (:58-61)
+        st.m_spec = std::fabs(dot(od, hit.normal));
+        if (dot(od, hit.normal) > 0) {
+            out = Ray{hit.pos, od};
+            have_out = true;
+            new_tint = pr.specular();
+            st.type = RT_BOUNCE_SPECULAR;
+        } else {
+            st.type = RT_BOUNCE_SPECULAR_FAIL;
+        }
+    } else if (diff_lum != 0 && (ray_rand -= diff_lum) <= 0) {
+        double z = (2 * std::acos(rs.next())) / kPi;
+        double theta = rs.next() * kPi * 2;
+        out = Ray{hit.pos, create_horizon(hit.normal, z, theta)};
+        have_out = true;
+        new_tint = pr.diffuse;
+        st.type = RT_BOUNCE_DIFFUSE;
+    } else {
+        st.type = RT_BOUNCE_EMISSION;
+        st.draws = rs.n;
+        return st;
+    }
+    st.draws = rs.n;
+    // `outRay == Ray.Zero` (Raytracer.cs:231): origin and direction both zero (XYZ)
+    if (!have_out || (eq3(out.o, v4(0, 0, 0, 0)) && eq3(out.d, v4(0, 0, 0, 0)))) return st;
+    st.go_on = true;
+    st.out = out;
+    st.factor = new_tint * net_max(total, 1);
+    return st;
+}
+
+// What get_color can report of each bounce besides `trace` (diagnostic, orc_sample_path).
+struct PathRow {
+    V4 dir, normal, pos;
+    Col tint;
+    int prim, type, inside;
+};
+
 // Raytracer.GetColor(Ray, ref DebugRay[]) (Raytracer.cs:65-246).  Returns the colour;
 // `rays` counts Scene.RayTrace calls.
 template <class S>
-Col get_color(const Scene& sc, Ray ray, S& rs, int& rays, std::vector<Leaf>& scratch, int32_t* trace = nullptr)
+Col get_color(const Scene& sc, Ray ray, S& rs, int& rays, std::vector<Leaf>& scratch, int32_t* trace = nullptr,
+              std::vector<PathRow>* rows = nullptr)
 {
     // trace (diagnostic, may be null): per bounce i, trace[2i] = primitive hit (-1 miss),
     // trace[2i+1] = event (1 diffuse, 2 specular, 3 specular fail, 4 transmitted, 5 emission, 0 other)
+    // rows (diagnostic, may be null): per bounce the ray as traced, the hit and the tint before it,
+    // with the rt_bounce_type of how the bounce ended
     Hit prev, hit;
     bool have_prev = false;
     Col tint = col(1);
@@ -102,83 +235,23 @@ Col get_color(const Scene& sc, Ray ray, S& rs, int& rays, std::vector<Leaf>& scr
         hit = sc.raytrace(ray, have_prev ? &prev : nullptr, scratch);
         rays++;
         if (trace) trace[2 * i] = hit.prim;
+        if (rows) rows->push_back(PathRow{ray.d, hit.normal, hit.pos, tint, hit.prim, RT_BOUNCE_MISSED, hit.inside});
         if (hit.prim < 0) {
             if (i == 0) return col(-1);
             return sc.ambient;
         }
         const Prim& pr = sc.prims[hit.prim];
+        if (rows) rows->back().type = sc.debug_geom ? RT_BOUNCE_DEBUG : RT_BOUNCE_RECURSION_COMPLETE;
         if (sc.debug_geom) return pr.specular() + pr.diffuse + pr.emission;
         if (i >= sc.recursion) break;
-        Ray out{v4(0, 0, 0, 0), v4(0, 0, 0, 0)};
-        bool have_out = false;
-        V4 rough = random_shine(rs, hit.normal, pr.shininess);
-        double diff_lum = lum(pr.diffuse), spec_lum = lum(pr.specular()), refr_lum = lum(pr.refraction()),
-               emis_lum = lum(pr.emission);
-        double cs = -dot(rough, ray.d);
-        double cos_out = 0, ior_ratio = 0;
-        if (((refr_lum > 0) | (spec_lum > 0)) && pr.refractive_index != 0 && cs >= 0) {
-            double ior_in, ior_out;
-            if (hit.inside) {
-                ior_in = pr.refractive_index;
-                ior_out = sc.air_ior;
-            } else {
-                ior_in = sc.air_ior;
-                ior_out = pr.refractive_index;
-            }
-            ior_ratio = ior_in / ior_out;
-            double sin_out = ior_ratio * std::sqrt(1 - (cs * cs));
-            if (sin_out >= 1) {
-                refr_lum = 0;
-            } else {
-                cos_out = std::sqrt(1 - (sin_out * sin_out));
-                double rs_ = ((ior_out * cs) - (ior_in * cos_out)) / ((ior_out * cs) + (ior_in * cos_out));
-                double rp = ((ior_in * cs) - (ior_out * cos_out)) / ((ior_in * cs) + (ior_out * cos_out));
-                double ratio = ((rs_ * rs_) + (rp * rp)) / 2;
-                spec_lum *= ratio;
-                refr_lum *= 1 - ratio;
-            }
-        } else {
-            refr_lum = 0;
-        }
-        double total = diff_lum + spec_lum + refr_lum + emis_lum;
-        if (total <= 0) break;
-        Col new_tint = col(0);
-        double ray_rand = rs.next() * total;
-        if (refr_lum != 0 && (ray_rand -= refr_lum) <= 0) {
-            V4 od = (rough * -cos_out) + ((ray.d + (rough * cs)) * ior_ratio);
-            out = Ray{hit.pos, od};
-            have_out = true;
-            new_tint = pr.refraction();
-            if (hit.inside) new_tint = col(1);
-            if (trace) trace[2 * i + 1] = 4;
-        } else if (spec_lum != 0 && (ray_rand -= spec_lum) <= 0) {
-            V4 od = ray.d + (rough * (cs * 2)); // Raytracer.Reflection (:58-61)
-            if (dot(od, hit.normal) > 0) {
-                out = Ray{hit.pos, od};
-                have_out = true;
-                new_tint = pr.specular();
-                if (trace) trace[2 * i + 1] = 2;
-            } else if (trace) {
-                trace[2 * i + 1] = 3;
-            }
-        } else if (diff_lum != 0 && (ray_rand -= diff_lum) <= 0) {
-            double z = (2 * std::acos(rs.next())) / kPi;
-            double theta = rs.next() * kPi * 2;
-            out = Ray{hit.pos, create_horizon(hit.normal, z, theta)};
-            have_out = true;
-            new_tint = pr.diffuse;
-            if (trace) trace[2 * i + 1] = 1;
-        } else {
-            if (trace) trace[2 * i + 1] = 5;
-            break; // emission
-        }
-        // `outRay == Ray.Zero` (Raytracer.cs:231): origin and direction both zero (XYZ)
-        if (!have_out || (eq3(out.o, v4(0, 0, 0, 0)) && eq3(out.d, v4(0, 0, 0, 0)))) break;
+        const Step st = shade_step(sc, ray, hit, rs);
+        if (trace && st.type <= RT_BOUNCE_EMISSION) trace[2 * i + 1] = st.type;
+        if (rows) rows->back().type = st.type;
+        if (!st.go_on) break;
         prev = hit;
         have_prev = true;
-        ray = out;
-        new_tint = new_tint * net_max(total, 1);
-        tint = tint * new_tint;
+        ray = st.out;
+        tint = tint * st.factor;
     }
     return tint * sc.prims[hit.prim].emission;
 }
@@ -565,6 +638,84 @@ int32_t orc_sample_trace(const orc_scene* s, int32_t x, int32_t y, uint64_t seed
     Col c = get_color(sc, r, rs, nr, scratch, trace);
     if (color) *color = to_abi(c);
     return ceq(c, col(-1)) ? 1 : 0;
+}
+
+// The camera ray of one sample as bounce 0 traces it (GetColor normalises the direction there).
+int32_t orc_camera_sample_ray(const orc_scene* s, int32_t x, int32_t y, uint64_t seed, uint64_t smp, double* origin,
+                              double* direction)
+{
+    if (!s || s->sc.cameras.empty() || !origin || !direction) return -1;
+    const Scene& sc = s->sc;
+    Sampler base{rt_rng_init(seed, (uint64_t)y * (uint64_t)sc.width + (uint64_t)x, smp)};
+    Counted<Sampler> rs{base};
+    Ray r = camera_ray(sc.cameras[sc.current_camera], rs, x, y);
+    r = ray_directional(r.o, r.d);
+    origin[0] = r.o.x, origin[1] = r.o.y, origin[2] = r.o.z;
+    direction[0] = r.d.x, direction[1] = r.d.y, direction[2] = r.d.z;
+    return rs.n;
+}
+
+int32_t orc_shade_steps(const orc_scene* s, int32_t n, const double* dir, const double* normal, const double* pos,
+                        const int32_t* inside, const int32_t* prim, const int32_t* bounce, uint64_t seed,
+                        const uint64_t* pixel, const uint64_t* smp, const int32_t* cursor, int32_t* type, double* cos_in,
+                        double* fresnel, double* out_origin, double* out_dir, double* factor, int32_t* draws,
+                        double* margins)
+{
+    if (!s || n < 0) return -1;
+    const Scene& sc = s->sc;
+    for (int32_t k = 0; k < n; k++) {
+        if (prim[k] < 0 || prim[k] >= (int32_t)sc.prims.size() || cursor[k] < 0) return -1;
+        Sampler rs{rt_rng_init(seed, pixel[k], smp[k])};
+        for (int32_t c = 0; c < cursor[k]; c++) rs.next();
+        const double *d = dir + 3 * k, *nn = normal + 3 * k, *p = pos + 3 * k;
+        Hit hit;
+        hit.prim = prim[k];
+        hit.pos = v4(p[0], p[1], p[2], 1);
+        hit.normal = v4(nn[0], nn[1], nn[2], 0);
+        hit.inside = inside[k] != 0;
+        const Ray ray{v4(0, 0, 0, 1), v4(d[0], d[1], d[2], 0)};
+        const Step st = shade_step(sc, ray, hit, rs);
+        // the ray as GetColor traces it next: normalised where the next bounce index is a multiple of 3
+        Ray out = st.out;
+        if (st.go_on && (bounce[k] + 1) % 3 == 0) out = ray_directional(out.o, out.d);
+        const double nan = std::nan("");
+        type[k] = st.type;
+        cos_in[k] = st.cs;
+        fresnel[k] = st.fresnel;
+        out_origin[3 * k] = st.go_on ? out.o.x : nan, out_origin[3 * k + 1] = st.go_on ? out.o.y : nan,
+                       out_origin[3 * k + 2] = st.go_on ? out.o.z : nan;
+        out_dir[3 * k] = st.go_on ? out.d.x : nan, out_dir[3 * k + 1] = st.go_on ? out.d.y : nan,
+                    out_dir[3 * k + 2] = st.go_on ? out.d.z : nan;
+        factor[3 * k] = st.go_on ? st.factor.r : nan, factor[3 * k + 1] = st.go_on ? st.factor.g : nan,
+                   factor[3 * k + 2] = st.go_on ? st.factor.b : nan;
+        draws[k] = st.draws;
+        margins[4 * k] = st.m_lobe, margins[4 * k + 1] = st.m_sin, margins[4 * k + 2] = st.m_cos,
+                    margins[4 * k + 3] = st.m_spec;
+    }
+    return 0;
+}
+
+// Diagnostic: one sample (as orc_sample) with every bounce's inputs to the bounce step.
+int32_t orc_sample_path(const orc_scene* s, int32_t x, int32_t y, uint64_t seed, uint64_t smp, rt_color* color,
+                        double* rows, int32_t* irows)
+{
+    if (!s || s->sc.cameras.empty() || !rows || !irows) return -1;
+    const Scene& sc = s->sc;
+    std::vector<Leaf> scratch;
+    std::vector<PathRow> path;
+    Sampler rs{rt_rng_init(seed, (uint64_t)y * (uint64_t)sc.width + (uint64_t)x, smp)};
+    Ray r = camera_ray(sc.cameras[sc.current_camera], rs, x, y);
+    int nr = 0;
+    Col c = get_color(sc, r, rs, nr, scratch, nullptr, &path);
+    if (color) *color = to_abi(c);
+    for (size_t i = 0; i < path.size(); i++) {
+        const PathRow& q = path[i];
+        const double v[12] = {q.dir.x, q.dir.y, q.dir.z, q.normal.x, q.normal.y, q.normal.z,
+                              q.pos.x, q.pos.y, q.pos.z, q.tint.r,   q.tint.g,   q.tint.b};
+        std::copy(v, v + 12, rows + 12 * i);
+        irows[3 * i] = q.prim, irows[3 * i + 1] = q.type, irows[3 * i + 2] = q.inside;
+    }
+    return (int32_t)path.size();
 }
 
 int32_t orc_render_tile_netrandom(const orc_scene* s, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t spp,

@@ -71,6 +71,37 @@ int32_t orc_render_tile(const orc_scene* s, int32_t x0, int32_t y0, int32_t w, i
 int32_t orc_sample_trace(const orc_scene* s, int32_t x, int32_t y, uint64_t seed, uint64_t sample,
                          rt_color* color, int32_t* trace);
 
+/* Diagnostic: one sample (as orc_sample) with what each bounce fed the bounce step.  Per bounce i,
+ * rows[12i..] = the direction as traced, the hit normal, the hit position, the tint before the
+ * bounce (3 doubles each); irows[3i..] = primitive (-1 miss), rt_bounce_type of how the bounce
+ * ended, inside.  Room for recursion + 1 bounces; returns their number. */
+int32_t orc_sample_path(const orc_scene* s, int32_t x, int32_t y, uint64_t seed, uint64_t sample,
+                        rt_color* color, double* rows, int32_t* irows);
+
+/* GetCameraRay with the keyed stream, as bounce 0 traces it (direction normalised): origin and
+ * direction (3 doubles each).  Returns the draws it took (2, or 4 with depth of field). */
+int32_t orc_camera_sample_ray(const orc_scene* s, int32_t x, int32_t y, uint64_t seed, uint64_t sample,
+                              double* origin, double* direction);
+
+/*
+ * The bounce step of GetColor (RandomShine to the tint factor; the function get_color itself
+ * runs) on n caller-supplied hits.  Item k: the incoming direction as traced, the hit normal and
+ * position (n x 3 doubles each), inside, primitive ID (material and ior are the scene's), bounce
+ * index, and the stream (seed, pixel[k], sample[k]) advanced by cursor[k] draws.  Out: type
+ * (rt_bounce_type 1..6), cos, the Fresnel ratio (NaN where the Fresnel block is not reached, 1 on
+ * total internal reflection), the outgoing ray as GetColor traces it next (its origin: the hit
+ * position; its direction unnormalised, unless bounce + 1 is a multiple of 3) and the tint factor
+ * new_tint * max(total, 1) (all NaN where the path ends: also at a zero hit position with a zero
+ * direction, Ray.Zero), the draws consumed, and the decision margins (+inf where the decision is
+ * not taken): margins[4k] = min |rayRand - lobe threshold| / total, [4k+1] = |sin_out - 1|,
+ * [4k+2] = |cos|, [4k+3] = |out . normal| of a specular event.  Returns 0, -1 on a bad argument.
+ */
+int32_t orc_shade_steps(const orc_scene* s, int32_t n, const double* dir, const double* normal, const double* pos,
+                        const int32_t* inside, const int32_t* prim, const int32_t* bounce, uint64_t seed,
+                        const uint64_t* pixel, const uint64_t* sample, const int32_t* cursor, int32_t* type,
+                        double* cos_in, double* fresnel, double* out_origin, double* out_dir, double* factor,
+                        int32_t* draws, double* margins);
+
 /* Diagnostic: the same accumulation with the draws of one reference worker thread: one .NET Core
  * 3.1 System.Random(seed) stream, spp passes over the tile row by row (Raytracer.cs:48,302-320). */
 int32_t orc_render_tile_netrandom(const orc_scene* s, int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t spp,

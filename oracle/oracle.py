@@ -59,6 +59,13 @@ def lib() -> C.CDLL:
                                                                                P(C.c_uint64)]),
             "orc_sample_trace": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, P(rt_color),
                                              P(C.c_int32)]),
+            "orc_sample_path": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, P(rt_color),
+                                            P(C.c_double), P(C.c_int32)]),
+            "orc_camera_sample_ray": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64,
+                                                  P(C.c_double), P(C.c_double)]),
+            "orc_shade_steps": (C.c_int32, [C.c_void_p, C.c_int32] + [P(C.c_double)] * 3 + [P(C.c_int32)] * 3
+                                + [C.c_uint64, P(C.c_uint64), P(C.c_uint64), P(C.c_int32), P(C.c_int32)]
+                                + [P(C.c_double)] * 5 + [P(C.c_int32), P(C.c_double)]),
             "orc_render_tile_netrandom": (C.c_int32, [C.c_void_p] + [C.c_int32] * 6 + [P(rt_color), P(C.c_uint32),
                                                                                    P(C.c_uint32), P(C.c_uint64)]),
             "orc_render_frame": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, P(rt_color), P(C.c_uint32),
@@ -204,6 +211,53 @@ class OracleScene:
         miss = lib().orc_sample_trace(self.h, x, y, seed, sample, C.byref(c), tr)
         path = [(tr[2 * i], tr[2 * i + 1]) for i in range(recursion + 1) if tr[2 * i] != -2]
         return (c.r, c.g, c.b), bool(miss), path
+
+    def sample_path(self, x, y, seed=0, sample=0, recursion=32):
+        """Diagnostic: one sample's colour and, per bounce, what the bounce step was fed (oracle.h):
+        dict of direction, normal, position, tint [n, 3] and prim, type, inside [n]."""
+        c = rt_color()
+        rows = np.zeros((recursion + 1, 12), np.float64)
+        irows = np.zeros((recursion + 1, 3), np.int32)
+        n = lib().orc_sample_path(self.h, x, y, seed, sample, C.byref(c), rows.ctypes.data_as(C.POINTER(C.c_double)),
+                                  irows.ctypes.data_as(C.POINTER(C.c_int32)))
+        assert 0 <= n <= recursion + 1
+        rows, irows = rows[:n], irows[:n]
+        return (c.r, c.g, c.b), {"direction": rows[:, 0:3], "normal": rows[:, 3:6], "position": rows[:, 6:9],
+                                 "tint": rows[:, 9:12], "prim": irows[:, 0], "type": irows[:, 1],
+                                 "inside": irows[:, 2]}
+
+    def camera_sample_ray(self, x, y, seed=0, sample=0):
+        """GetCameraRay on the keyed stream as bounce 0 traces it: (origin, direction, draws used)."""
+        o, d = np.zeros(3), np.zeros(3)
+        k = lib().orc_camera_sample_ray(self.h, x, y, seed, sample, o.ctypes.data_as(C.POINTER(C.c_double)),
+                                        d.ctypes.data_as(C.POINTER(C.c_double)))
+        assert k >= 0
+        return o, d, k
+
+    def shade_steps(self, direction, normal, position, inside, prim, bounce, seed, pixel, sample, cursor):
+        """The bounce step of GetColor on n caller-supplied hits (orc_shade_steps, oracle.h).  Returns a
+        dict: type, cos, fresnel, origin [n, 3], direction [n, 3], factor [n, 3], draws, margins [n, 4] (lobe, sin_out,
+        cos, specular side)."""
+        f8 = lambda a, m: np.ascontiguousarray(np.asarray(a, np.float64).reshape(-1, m))
+        direction, normal, position = f8(direction, 3), f8(normal, 3), f8(position, 3)
+        n = len(direction)
+        i4 = lambda a: np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.int32), (n,)))
+        u8 = lambda a: np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.uint64), (n,)))
+        inside, prim, bounce, cursor, pixel, sample = i4(inside), i4(prim), i4(bounce), i4(cursor), u8(pixel), u8(sample)
+        assert len(normal) == n and len(position) == n
+        out = {"type": np.zeros(n, np.int32), "cos": np.zeros(n), "fresnel": np.zeros(n), "origin": np.zeros((n, 3)),
+               "direction": np.zeros((n, 3)),
+               "factor": np.zeros((n, 3)), "draws": np.zeros(n, np.int32), "margins": np.zeros((n, 4))}
+        pd = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        pi = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        pu = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
+        rc = lib().orc_shade_steps(self.h, n, pd(direction), pd(normal), pd(position), pi(inside), pi(prim), pi(bounce),
+                                   int(seed), pu(pixel), pu(sample), pi(cursor), pi(out["type"]), pd(out["cos"]),
+                                   pd(out["fresnel"]), pd(out["origin"]), pd(out["direction"]), pd(out["factor"]), pi(out["draws"]),
+                                   pd(out["margins"]))
+        if rc != 0:
+            raise ValueError("orc_shade_steps: bad argument")
+        return out
 
     def render_tile_netrandom(self, x0, y0, w, h, spp, seed=0):
         """Diagnostic: the draws of one reference worker (.NET System.Random(seed), passes row by row)."""

@@ -981,6 +981,7 @@ __device__ __forceinline__ int shade(const SceneT& s, const PrimF* __restrict__ 
     V3 pos = madd(S.d, b.t, S.o);
     const bool sph = (s.facts & FACT_SPHERE) && kind == RT_PRIM_SPHERE;
     V3 n;
+    float nk; // 1 / |n| of a sphere's normal, applied with the turn toward the ray (below)
     if (SLOT) { // the BVH kernels (records in global memory: the three rows a, b, d only)
         const uint32_t axis = (fl & F_AXIS_MASK) >> F_AXIS_SHIFT; // axis-aligned rectangle: on its plane
         if (axis | (fl & F_FRAME_RECT)) gin = dot(S.d, xyz(P.d)) > 0.0f;
@@ -988,6 +989,7 @@ __device__ __forceinline__ int shade(const SceneT& s, const PrimF* __restrict__ 
         pos.y = axis == 2 ? P.a.y : pos.y;
         pos.z = axis == 3 ? P.a.z : pos.z;
         n = sph ? (pos - xyz(P.a)) * P.b.y : xyz(P.d);
+        nk = sph ? fmaf(-0.5f, dot(n, n), 1.5f) : 1.0f;
     } else { // the brute-force kernels (records in LDS): the same by arithmetic on the shading row c
         // c.xyz: one-hot plane axis of an axis-aligned rectangle (the hit point moves onto the plane
         // through v0 = P.a), c.w: 1/r of a sphere, whose P.d holds -centre/r (normal = p/r - c/r), 0
@@ -995,22 +997,36 @@ __device__ __forceinline__ int shade(const SceneT& s, const PrimF* __restrict__ 
         const float4 Pc = prims[b.sg >> 1].c;
         pos = v3(fmaf(Pc.x, P.a.x - pos.x, pos.x), fmaf(Pc.y, P.a.y - pos.y, pos.y), fmaf(Pc.z, P.a.z - pos.z, pos.z));
         n = madd(pos, Pc.w, xyz(P.d));
+        // No select here, which rests on what scene_records.cpp puts into row d of a flat kind: a
+        // triangle's face normal, normalised in fp64 and rounded (|n|^2 within 2e-7 of 1, so nk is 1 or 1
+        // -+ an ulp; the BVH form above takes exactly 1), a plane's Normal, unit by the ABI (rtcore.h), or
+        // zero (a vertex-normal triangle, a transformed sphere: nk = 1.5 on n = 0, both replaced below).
+        nk = fmaf(-0.5f, dot(n, n), 1.5f);
         if (fl & (F_AXIS_MASK | F_FRAME_RECT)) gin = dot(S.d, xyz(P.d)) > 0.0f;
     }
+    // The sphere test takes |d| = 1 as Sphere.cs does, and between the renormalising bounces an fp32
+    // direction drifts from unit length by up to 5e-6 (most after a refraction near the critical
+    // angle).  The hit point then lies off the sphere (the self-hit's far root -2 oc.d by 2 |oc.d| times
+    // the drift) and p/r - c/r is off unit length by up to 2e-5, which cos_in carries and the Fresnel
+    // ratio and the refracted ray magnify near the critical angle (measured 2e-4 and 3e-4 against the
+    // fp64 step).  One Newton step of 1/|n| (relative error (|n|^2 - 1)^2) brings it back: nk, which
+    // multiplies n together with the sign that turns it toward the ray.
     float bu = 0.0f, bv = 0.0f; // vertex-normal triangle: the barycentrics of the hit
     if ((s.facts & (FACT_XF | FACT_VN)) && (fl & (F_TRANSFORMED | F_HASNORMALS))) {
         if (sph) { // ellipsoid: the world normal is an affine map of the world hit point
             n = normalize(xf_point(xfs[__float_as_int(P.b.z)].normal, pos));
+            nk = 1.0f;
         } else if (s.facts & FACT_VN) { // Triangle.GetNormal quirk: Normal is never set -> NaN when inside
             const VnP vn = vnormals + 3 * id;
             const TestRec R = tests[b.sg >> 1]; // barycentrics (u, v) = rows 0, 1 of M (p, 1)
             bu = dot4(R.r0, pos);
             bv = dot4(R.r1, pos);
             n = normalize(madd(xyz(vn[2]), bu + bv, madd(xyz(vn[1]), bv, xyz(vn[0]) * bu)));
+            nk = 1.0f;
             if (gin) n = v3(__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""));
         }
     }
-    const V3 nrm = gin ? -n : n;
+    const V3 nrm = n * (gin ? -nk : nk);
     const bool inside = gin ^ ((fl & F_INVERT) != 0);
     if constexpr (REC) {
         rec->prim_id = id;
@@ -2310,6 +2326,7 @@ __device__ __forceinline__ void query_hit(uint32_t facts, const PrimF* __restric
     V3 pos = madd(d, b.t, o);
     const bool sph = (facts & FACT_SPHERE) && kind == RT_PRIM_SPHERE;
     V3 n;
+    float nk; // (as shade(): a sphere's normal back to unit length)
     if (SLOT) {
         const uint32_t axis = (fl & F_AXIS_MASK) >> F_AXIS_SHIFT;
         if (axis | (fl & F_FRAME_RECT)) gin = dot(d, xyz(Pd)) > 0.0f;
@@ -2317,25 +2334,29 @@ __device__ __forceinline__ void query_hit(uint32_t facts, const PrimF* __restric
         pos.y = axis == 2 ? Pa.y : pos.y;
         pos.z = axis == 3 ? Pa.z : pos.z;
         n = sph ? (pos - xyz(Pa)) * Pb.y : xyz(Pd);
+        nk = sph ? fmaf(-0.5f, dot(n, n), 1.5f) : 1.0f;
     } else {
         const float4 Pc = P.c;
         pos = v3(fmaf(Pc.x, Pa.x - pos.x, pos.x), fmaf(Pc.y, Pa.y - pos.y, pos.y), fmaf(Pc.z, Pa.z - pos.z, pos.z));
         n = madd(pos, Pc.w, xyz(Pd));
+        nk = fmaf(-0.5f, dot(n, n), 1.5f); // (no select: row d of a flat kind is unit or zero, see shade())
         if (fl & (F_AXIS_MASK | F_FRAME_RECT)) gin = dot(d, xyz(Pd)) > 0.0f;
     }
     if ((facts & (FACT_XF | FACT_VN)) && (fl & (F_TRANSFORMED | F_HASNORMALS))) {
         if (sph) {
             n = normalize(xf_point(xfs[__float_as_int(Pb.z)].normal, pos));
+            nk = 1.0f;
         } else if (facts & FACT_VN) {
             const VnP vn = vnormals + 3 * id;
             const TestRec R = tests[b.sg >> 1];
             const float bu = dot4(R.r0, pos);
             const float bv = dot4(R.r1, pos);
             n = normalize(madd(xyz(vn[2]), bu + bv, madd(xyz(vn[1]), bv, xyz(vn[0]) * bu)));
+            nk = 1.0f;
             if (gin) n = v3(__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""));
         }
     }
-    const V3 nrm = gin ? -n : n;
+    const V3 nrm = n * (gin ? -nk : nk);
     const bool inside = gin ^ ((fl & F_INVERT) != 0);
     const unsigned long long tb = (unsigned long long)__double_as_longlong((double)b.t); // fp32 widened exactly
     out[0] = make_float4(__int_as_float(id), __int_as_float(inside ? 1 : 0), __uint_as_float((unsigned)tb),

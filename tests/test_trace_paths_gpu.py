@@ -281,6 +281,7 @@ def test_paths_against_oracle(rc, scenes):
 
     Measured on an MI355X (bounce.txt 128x128, 715 samples): see DESIGN.md, "Path inspection".
     """
+    # (whole paths only: the check of every bounce, diverged paths included, is tests/test_bounce_step_gpu.py)
     from oracle.oracle import OracleScene, fresnel as orc_fresnel
 
     scene = scenes["bounce.txt"]
