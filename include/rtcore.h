@@ -49,7 +49,8 @@ extern "C" {
                                    rt_render_rays and rt_render_rays_device, and rt_occluded_rays and
                                    rt_occluded_rays_device, and rt_render_pixels, rt_render_pixels_device,
                                    rt_adaptive_select_device and rt_debug_adaptive_select, and
-                                   rt_primary_hits_device, rt_denoise_device and rt_debug_denoise */
+                                   rt_primary_hits_device, rt_denoise_device and rt_debug_denoise, and
+                                   rt_reproject_device and rt_debug_reproject */
 
 typedef enum rt_status {
     RT_OK = 0,
@@ -826,6 +827,85 @@ int rt_denoise_device(const rt_denoise_params* params, const double* d_sum, cons
 int rt_debug_denoise(const rt_denoise_params* params, const double* sum, const uint32_t* samples,
                      const uint32_t* misses, const double* q, const uint32_t* batches, uint64_t plane,
                      const rt_hit* hits, int32_t width, int32_t height, double* out_sum, float* out_var);
+
+/* ------------------------------------------------------- temporal reprojection --- */
+/*
+ * rt_reproject_device: carries whole-frame accumulators with moments from the pixels of a previous camera
+ * to the pixels of the scene's current one (the temporal half of SVGF's history, for a static scene and a
+ * moving camera), so that an adaptive render continues from them instead of from zero.  A nearest-pixel
+ * gather: each current pixel takes the five accumulators of at most one previous pixel, so (Y, N, Q, J)
+ * stays the sample set of one pixel and the estimate of "adaptive sampling" keeps its meaning; mixing the
+ * moments of several pixels would not.  The definition is normative; the device pass and the host twin
+ * rt_debug_reproject compile it from one set of functions and agree bit for bit.  Every operation is
+ * rounded on its own (no contraction), division is IEEE on both sides, no library function is called on
+ * the device.
+ *
+ * The host runs Camera.InitRender on prev_camera for (width, height) once -- position, look, side, up, w2,
+ * h2, tan_x, tan_y, h_mult, v_mult in fp64, as the exact kernels hold them -- and hands the result to the
+ * pass.  For the current pixel p = (x, y) with H = d_hits[y * width + x]:
+ *  1. Invalid: H.prim_id < 0 or a component of H.position not finite -- p is empty (6).
+ *  2. Projection, in fp64: X = H.position widened, v = X - position, z = v . look, a = v . side, b = v . up
+ *     (dot products left to right).  Empty unless z > 0.
+ *       frustum: fx = w2 + w2 * ((a / z) / tan_x),  fy = h2 + h2 * ((b / z) / tan_y)
+ *       ortho:   fx = w2 + a / h_mult,              fy = h2 + b / v_mult
+ *     the inverse of FrustumCamera.GetRay (offX = tanFOVX2 * ((x - w2) / w2)) and OrthoCamera.GetRay.  Pixel
+ *     centres are the integer coordinates (rt_camera_rays traces GetRay(x, y)).  Empty unless
+ *     fx >= -0.5 && fx < width - 0.5 && fy >= -0.5 && fy < height - 0.5 (a NaN fails).  qx = (int)(fx + 0.5),
+ *     qy = (int)(fy + 0.5), a floor here; held to width - 1 and height - 1 (only a frame one pixel wide
+ *     or high can reach them, by the sum's rounding).
+ *  3. Validation against G = d_prev_hits[qy * width + qx]; p is empty unless all of
+ *       G.prim_id >= 0;  with RT_REPROJECT_SAME_PRIM, G.prim_id == H.prim_id;  G.inside == H.inside;
+ *       n_H . n_G >= normal_cos_min                                  (fp32, left to right; a NaN rejects)
+ *       |n_H . (x_G - x_H)| <= sigma_z * (float)H.distance           (fp32, as rt_denoise_device's w_z: the
+ *                                                                     differences first; a NaN rejects)
+ *  4. History: N = samples + misses of the source pixel (64-bit).  Empty if N == 0.  If N <= max_history
+ *     the five accumulators are copied bit for bit.
+ *  5. The cap, N > max_history: N' = max_history, samples' = (uint32)((uint64)samples * N' / N), misses' =
+ *     N' - samples'; per channel sum' = sum * ((double)samples' / (double)samples) for samples > 0, else
+ *     sum; with Y, Y' the luminances of sum, sum' (0.299 r + 0.587 g + 0.114 b, fp64, left to right):
+ *       J >= 2: J' = min(J, N'), D = Q - Y * Y / N, Q' = D * ((double)(J' - 1) / (double)(J - 1)) + Y' * Y' / N'
+ *       J <  2: J' = J, Q' = Q * ((double)N' / (double)N)
+ *     The mean colour sum / samples is kept to rounding and the per-sample variance s2 by construction,
+ *     (Q' - Y'^2 / N') / (J' - 1) = D / (J - 1); only the history's weight drops, so that samples of the
+ *     new view outvote it and view-dependent shading recovers.
+ *  6. An empty pixel gets 0 in all five accumulators and out_src = -1; an accepted one out_src =
+ *     qy * width + qx.
+ * Miss pixels are not reprojected.  A depth-of-field camera is accepted: the hits are the pinhole
+ * centre's, so the history is that footprint's.
+ *
+ * d_prev_hits is rt_primary_hits_device's whole-frame output under prev_camera, d_hits the same under the
+ * current camera; the pass itself needs no scene.  Inputs and outputs in rt_render_pixels_device's layout
+ * (index y * width + x, sum planes `plane` elements apart, 0 = width * height); d_out_src (width * height
+ * int32) may be NULL.  No output may overlap an input: the pass is a gather, an overlap would be a race.
+ * Runs on the calling thread's current device, asynchronous on `stream`; no scratch memory.
+ * RT_ERR_ARG, before anything is launched, for a null pointer (d_out_src excepted), a frame of no pixels
+ * or of 2^32 or more, a plane smaller than the frame, d_out_sum overlapping d_sum, an unknown camera kind,
+ * sigma_z not above 0 (NaN included), normal_cos_min outside [-1, 1] or NaN, max_history == 0, unknown
+ * flag bits or non-zero reserved fields.
+ * rt_debug_reproject: the host twin (host only, no device needed), the same arguments on host arrays.
+ */
+#define RT_REPROJECT_SAME_PRIM 1u
+typedef struct rt_reproject_params {   /* 32 B */
+    float    sigma_z;         /* > 0: plane-distance stop, relative to the current hit's distance */
+    float    normal_cos_min;  /* in [-1, 1]: the two normals' dot product must be >= this          */
+    uint32_t max_history;     /* >= 1: a carried pixel has at most this many samples + misses      */
+    uint32_t flags;           /* RT_REPROJECT_SAME_PRIM: the source must show the same prim_id     */
+    uint32_t reserved[4];     /* 0 */
+} rt_reproject_params;
+int rt_reproject_device(const rt_reproject_params* params, const rt_camera* prev_camera,
+                        const rt_hit* d_prev_hits, const rt_hit* d_hits,
+                        const double* d_sum, const uint32_t* d_samples, const uint32_t* d_misses,
+                        const double* d_q, const uint32_t* d_batches, uint64_t plane,
+                        int32_t width, int32_t height,
+                        double* d_out_sum, uint32_t* d_out_samples, uint32_t* d_out_misses,
+                        double* d_out_q, uint32_t* d_out_batches, int32_t* d_out_src, void* stream);
+int rt_debug_reproject(const rt_reproject_params* params, const rt_camera* prev_camera,
+                       const rt_hit* prev_hits, const rt_hit* hits,
+                       const double* sum, const uint32_t* samples, const uint32_t* misses,
+                       const double* q, const uint32_t* batches, uint64_t plane,
+                       int32_t width, int32_t height,
+                       double* out_sum, uint32_t* out_samples, uint32_t* out_misses,
+                       double* out_q, uint32_t* out_batches, int32_t* out_src);
 
 /* Device-side DebugRaycaster Primitives pass: d_ids[y*w + x].  Asynchronous. */
 int rt_primary_ids_device(rt_scene* scene, int32_t x0, int32_t y0, int32_t w, int32_t h,

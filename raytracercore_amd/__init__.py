@@ -195,6 +195,29 @@ def denoise_params(**kw) -> rt_denoise_params:
                              int(v["iterations"]), int(v["flags"]))
 
 
+RT_REPROJECT_SAME_PRIM = 1  # rt_reproject_params.flags: the source pixel must show the same prim_id
+
+
+class rt_reproject_params(C.Structure):
+    """The temporal reprojection's parameters (rt_reproject_device), 32 B."""
+    _fields_ = [("sigma_z", C.c_float), ("normal_cos_min", C.c_float), ("max_history", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
+# what GpuRaytracer.reproject uses where the caller names no value (DESIGN.md 4.8, profiles/reproject/README.md)
+REPROJECT_DEFAULTS = dict(sigma_z=0.05, normal_cos_min=0.9, max_history=32, flags=RT_REPROJECT_SAME_PRIM)
+
+
+def reproject_params(**kw) -> rt_reproject_params:
+    """rt_reproject_params from keywords, REPROJECT_DEFAULTS for the rest."""
+    v = dict(REPROJECT_DEFAULTS)
+    unknown = set(kw) - set(v)
+    if unknown:
+        raise TypeError(f"unknown reproject parameter(s): {sorted(unknown)}")
+    v.update(kw)
+    return rt_reproject_params(float(v["sigma_z"]), float(v["normal_cos_min"]), int(v["max_history"]), int(v["flags"]))
+
+
 SELECT_ITEM_DTYPE = np.dtype([("kind", np.int32), ("index", np.int32)])
 SELECTION_DTYPE = np.dtype([("item", np.int32), ("reserved", np.int32), ("distance", np.float64)])
 
@@ -210,7 +233,7 @@ HIT_DTYPE = np.dtype([
 _OPTIONAL = ("rt_query_rays", "rt_query_rays_device", "rt_camera_rays", "rt_select_pixels", "rt_select_pixels_device",
              "rt_select_rays", "rt_select_rays_device", "rt_render_rays", "rt_render_rays_device",
              "rt_occluded_rays", "rt_occluded_rays_device", "rt_render_pixels", "rt_render_pixels_device",
-             "rt_adaptive_select_device", "rt_primary_hits_device", "rt_denoise_device")
+             "rt_adaptive_select_device", "rt_primary_hits_device", "rt_denoise_device", "rt_reproject_device")
 
 _lib: Optional[C.CDLL] = None
 
@@ -335,6 +358,10 @@ def load_library(path: str = "") -> C.CDLL:
                                         C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
         "rt_debug_denoise": (C.c_int, [P(rt_denoise_params)] + [C.c_void_p] * 5 + [C.c_uint64, C.c_void_p, C.c_int32,
                                        C.c_int32, C.c_void_p, C.c_void_p]),
+        "rt_reproject_device": (C.c_int, [P(rt_reproject_params), P(rt_camera)] + [C.c_void_p] * 7 +
+                                [C.c_uint64, C.c_int32, C.c_int32] + [C.c_void_p] * 7),
+        "rt_debug_reproject": (C.c_int, [P(rt_reproject_params), P(rt_camera)] + [C.c_void_p] * 7 +
+                               [C.c_uint64, C.c_int32, C.c_int32] + [C.c_void_p] * 6),
     }
     for name, (res, args) in sig.items():
         if (name.startswith("rt_debug_") or name in _OPTIONAL) and not hasattr(lib, name):
@@ -918,7 +945,7 @@ class GpuRaytracer:
                                                 C.c_void_p(stream)))
 
     def render_adaptive(self, rel_tol: float, min_spp: int, max_spp: int, batch_spp: int, seed: int = 0,
-                        lum_floor: float = 1e-3):
+                        lum_floor: float = 1e-3, history: Optional[dict] = None, sample_base: int = 0):
         """Render until every pixel's standard error is at most rel_tol of its luminance (rtcore.h, "adaptive
         sampling"), with the accumulators and the pixel list held as torch tensors on this scene's device.
         Each iteration: rt_adaptive_select_device builds the list of pixels that still need samples, the
@@ -930,6 +957,15 @@ class GpuRaytracer:
         every listed pixel has therefore been in every earlier list and has the same N = iteration *
         batch_spp, which is why one sample_base per iteration is right.  min_spp and max_spp are rounded up
         to multiples of batch_spp.
+        history: a dict with sum, samples, misses, q, batches in this method's own layout (reproject's
+        result): the loop starts from clones of them instead of from zeros, so the caller's tensors are
+        untouched.  The listed pixels then no longer share one N -- a carried pixel starts with up to
+        max_history samples, an empty one with none -- but the stop argument still holds: a pixel that
+        leaves the list never changes again, so the lists only shrink and the loop ends at the latest when
+        every pixel has max_spp.  Iteration i draws at sample_base + i * batch_spp; the caller gives each
+        frame its own sample_base range (or its own seed), so that a pixel that maps to itself does not
+        draw the stream twice that its history already holds.  With both left out the result is bit for bit
+        what it was without them.
         Returns a dict: sum (3, H, W) f64, samples, misses, batches (H, W) i32 (the uint32 bits), q (H, W) f64
         -- device tensors in render_device's layout -- spp (H, W) i64 = samples + misses, counts (the list
         sizes per iteration), lists (the lists themselves, device tensors), rays, params."""
@@ -947,6 +983,12 @@ class GpuRaytracer:
                    "misses": torch.zeros((H, W), dtype=torch.int32, device=dev),
                    "q": torch.zeros((H, W), dtype=torch.float64, device=dev),
                    "batches": torch.zeros((H, W), dtype=torch.int32, device=dev)}
+            if history is not None:
+                for k, z in acc.items():
+                    t = history[k]
+                    if t.shape != z.shape or t.dtype != z.dtype or t.device != z.device:
+                        raise ValueError(f"render_adaptive: history[{k!r}] is not a {tuple(z.shape)} {z.dtype} tensor on {dev}")
+                    acc[k] = t.clone(memory_format=torch.contiguous_format)
             d_count = torch.zeros(1, dtype=torch.int32, device=dev)
             d_rays = torch.zeros(1, dtype=torch.int64, device=dev)
             stream = torch.cuda.current_stream(dev).cuda_stream
@@ -962,7 +1004,7 @@ class GpuRaytracer:
                 if n > lst.numel():
                     raise RtError("render_adaptive: the list of active pixels grew")
                 lst = lst[:n]
-                self.render_pixels_device(lst.data_ptr(), n, batch_spp, seed, len(counts) * batch_spp,
+                self.render_pixels_device(lst.data_ptr(), n, batch_spp, seed, int(sample_base) + len(counts) * batch_spp,
                                           acc["sum"].data_ptr(), acc["samples"].data_ptr(), acc["misses"].data_ptr(),
                                           acc["q"].data_ptr(), acc["batches"].data_ptr(), 0, d_rays.data_ptr(), stream)
                 counts.append(n)
@@ -981,10 +1023,76 @@ class GpuRaytracer:
         h = self.height - y0 if h is None else h
         _check(self.lib.rt_primary_hits_device(self.handle, x0, y0, w, h, C.c_void_p(d_hits), C.c_void_p(stream)))
 
-    def denoise(self, res: dict, return_var: bool = False, **params):
+    def primary_hits(self):
+        """The whole frame's first hits under the scene's current camera (rt_primary_hits_device on torch's
+        current stream, waited for): a (H * W, 48) uint8 device tensor of rt_hit records, row-major, which
+        denoise and reproject take as `hits`; .cpu().numpy().reshape(-1).view(HIT_DTYPE) reads it."""
+        import torch
+
+        W, H = self.width, self.height
+        dev = torch.device("cuda", self.device)
+        with torch.cuda.device(dev):
+            hits = torch.empty((H * W, HIT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+            self.primary_hits_device(hits.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream)
+            torch.cuda.synchronize(dev)
+        return hits
+
+    def _check_hits(self, hits, name: str) -> None:
+        import torch
+
+        if (hits.dtype != torch.uint8 or hits.numel() != self.width * self.height * HIT_DTYPE.itemsize or
+                not hits.is_contiguous() or hits.device != torch.device("cuda", self.device)):
+            raise ValueError(f"{name}: not primary_hits' tensor for this frame and device")
+
+    def reproject(self, res: dict, prev_camera: rt_camera, prev_hits, hits=None, **params):
+        """Temporal reprojection (rtcore.h, "temporal reprojection"): the accumulators of `res`,
+        render_adaptive's result under prev_camera, carried to the pixels of the scene's camera, which is
+        already the new one.  prev_hits: primary_hits() taken under prev_camera; hits: primary_hits() under
+        the current camera (made here when None).  params: the fields of rt_reproject_params
+        (REPROJECT_DEFAULTS for the rest).  One rt_reproject_device call on torch's current stream.
+        Returns a dict: sum, samples, misses, q, batches in render_adaptive's layout -- its `history`
+        argument takes the dict as it is --, src (H, W) i32, the source pixel's frame index or -1 for a
+        pixel that starts again, and hits, the current camera's, for denoise(..., hits=)."""
+        import torch
+
+        W, H = self.width, self.height
+        par = reproject_params(**params)
+        dev = torch.device("cuda", self.device)
+        if hits is None:
+            hits = self.primary_hits()
+        self._check_hits(prev_hits, "reproject: prev_hits")
+        self._check_hits(hits, "reproject: hits")
+        src_t = {}
+        for k, shape, dt in (("sum", (3, H, W), torch.float64), ("samples", (H, W), torch.int32), ("misses", (H, W), torch.int32),
+                             ("q", (H, W), torch.float64), ("batches", (H, W), torch.int32)):
+            t = res[k]
+            if tuple(t.shape) != shape or t.dtype != dt or t.device != dev:
+                raise ValueError(f"reproject: res[{k!r}] is not a {shape} {dt} tensor on {dev}")
+            src_t[k] = t.contiguous()
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            out = {"sum": torch.empty((3, H, W), dtype=torch.float64, device=dev),
+                   "samples": torch.empty((H, W), dtype=torch.int32, device=dev),
+                   "misses": torch.empty((H, W), dtype=torch.int32, device=dev),
+                   "q": torch.empty((H, W), dtype=torch.float64, device=dev),
+                   "batches": torch.empty((H, W), dtype=torch.int32, device=dev),
+                   "src": torch.empty((H, W), dtype=torch.int32, device=dev)}
+            reproject_device(par, prev_camera, prev_hits.data_ptr(), hits.data_ptr(), src_t["sum"].data_ptr(),
+                             src_t["samples"].data_ptr(), src_t["misses"].data_ptr(), src_t["q"].data_ptr(),
+                             src_t["batches"].data_ptr(), W, H, out["sum"].data_ptr(), out["samples"].data_ptr(),
+                             out["misses"].data_ptr(), out["q"].data_ptr(), out["batches"].data_ptr(), out["src"].data_ptr(),
+                             stream=stream)
+            torch.cuda.synchronize(dev)  # (the inputs' contiguous copies, if any, are released on return)
+        out["hits"] = hits
+        out["params"] = par
+        return out
+
+    def denoise(self, res: dict, return_var: bool = False, hits=None, **params):
         """The a-trous filter (rtcore.h, "denoising") over render_adaptive's result `res`: one
         rt_primary_hits_device pass for the frame's guides, then rt_denoise_device, on torch's current
-        stream.  params: the fields of rt_denoise_params (DENOISE_DEFAULTS for the rest, and
+        stream.  hits: primary_hits() of the scene's camera (reproject's result has it), so that a frame's
+        guide pass runs once; None: the pass runs here into a private tensor.  params: the fields of
+        rt_denoise_params (DENOISE_DEFAULTS for the rest, and
         denoise_iterations of the frame for the levels).  Returns the filtered sums as a (3, H, W) f64 device
         tensor in res["sum"]'s layout -- tonemap_device takes it with res["samples"] and res["misses"] -- and
         with return_var also the filtered variance, (H, W) f32."""
@@ -994,12 +1102,15 @@ class GpuRaytracer:
         params.setdefault("iterations", denoise_iterations(W, H))
         par = denoise_params(**params)
         dev = torch.device("cuda", self.device)
+        if hits is not None:
+            self._check_hits(hits, "denoise: hits")
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            hits = torch.empty((H * W, HIT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
             out = torch.empty((3, H, W), dtype=torch.float64, device=dev)
             var = torch.empty((H, W), dtype=torch.float32, device=dev) if return_var else None
-            self.primary_hits_device(hits.data_ptr(), stream=stream)
+            if hits is None:
+                hits = torch.empty((H * W, HIT_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+                self.primary_hits_device(hits.data_ptr(), stream=stream)
             denoise_device(par, res["sum"].data_ptr(), res["samples"].data_ptr(), res["misses"].data_ptr(),
                            res["q"].data_ptr(), res["batches"].data_ptr(), hits.data_ptr(), W, H, out.data_ptr(),
                            var.data_ptr() if return_var else 0, stream=stream)
@@ -1155,6 +1266,47 @@ def denoise_host(params: rt_denoise_params, sum_planes: np.ndarray, samples: np.
     _check(load_library().rt_debug_denoise(C.byref(params), ptr(s), ptr(arrs[0]), ptr(arrs[1]), ptr(arrs[2]), ptr(arrs[3]),
                                            plane, ptr(arrs[4]), width, height, ptr(out), ptr(var)))
     return out, var
+
+
+def reproject_device(params: rt_reproject_params, prev_camera: rt_camera, d_prev_hits: int, d_hits: int, d_sum: int,
+                     d_samples: int, d_misses: int, d_q: int, d_batches: int, width: int, height: int, d_out_sum: int,
+                     d_out_samples: int, d_out_misses: int, d_out_q: int, d_out_batches: int, d_out_src: int = 0,
+                     plane: int = 0, stream: int = 0) -> None:
+    """rt_reproject_device: whole-frame device accumulators with moments (render_pixels_device's layout) under
+    prev_camera, carried to the pixels of the camera whose first hits are at d_hits (d_prev_hits: the first
+    hits under prev_camera; both from primary_hits_device), into the d_out_* arrays of the same layout, which
+    overlap no input, and, unless 0, width * height int32 source indices at d_out_src.  Works on the current
+    device; asynchronous on `stream`."""
+    _check(load_library().rt_reproject_device(C.byref(params), C.byref(prev_camera), d_prev_hits, d_hits, d_sum, d_samples,
+                                              d_misses, d_q, d_batches, plane, width, height, d_out_sum, d_out_samples,
+                                              d_out_misses, d_out_q, d_out_batches, d_out_src or None, stream or None))
+
+
+def reproject_host(params: rt_reproject_params, prev_camera: rt_camera, prev_hits: np.ndarray, hits: np.ndarray,
+                   sum_planes: np.ndarray, samples: np.ndarray, misses: np.ndarray, q: np.ndarray, batches: np.ndarray,
+                   width: int, height: int, plane: int = 0, fill: float = 0.0) -> dict:
+    """rt_debug_reproject, the host twin of reproject_device (no GPU): host arrays in the device layout (sum:
+    three planes `plane` doubles apart, 0 = width * height; the others and the hits, HIT_DTYPE arrays,
+    row-major y * width + x).  Returns a dict: sum, a flat f64 array of sum_planes' size whose elements
+    outside the three planes keep `fill`, samples, misses, batches u32 and q f64 (height, width), and src
+    i32 (height, width)."""
+    npix = width * height
+    pl = plane or npix
+    s = np.ascontiguousarray(sum_planes, np.float64).reshape(-1)
+    arrs = [np.ascontiguousarray(a, dt).reshape(-1) for a, dt in
+            ((samples, np.uint32), (misses, np.uint32), (q, np.float64), (batches, np.uint32), (prev_hits, HIT_DTYPE),
+             (hits, HIT_DTYPE))]
+    if pl < npix or s.size < 2 * pl + npix or any(a.size < npix for a in arrs):
+        raise ValueError("accumulator arrays smaller than the frame")
+    out = {"sum": np.full(s.size, fill, np.float64), "samples": np.zeros((height, width), np.uint32),
+           "misses": np.zeros((height, width), np.uint32), "q": np.zeros((height, width), np.float64),
+           "batches": np.zeros((height, width), np.uint32), "src": np.zeros((height, width), np.int32)}
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    _check(load_library().rt_debug_reproject(C.byref(params), C.byref(prev_camera), ptr(arrs[4]), ptr(arrs[5]), ptr(s),
+                                             ptr(arrs[0]), ptr(arrs[1]), ptr(arrs[2]), ptr(arrs[3]), plane, width, height,
+                                             ptr(out["sum"]), ptr(out["samples"]), ptr(out["misses"]), ptr(out["q"]),
+                                             ptr(out["batches"]), ptr(out["src"])))
+    return out
 
 
 def pixels_plan(kernel: int, n: int, spp: int) -> dict:
