@@ -50,7 +50,8 @@ extern "C" {
                                    rt_occluded_rays_device, and rt_render_pixels, rt_render_pixels_device,
                                    rt_adaptive_select_device and rt_debug_adaptive_select, and
                                    rt_primary_hits_device, rt_denoise_device and rt_debug_denoise, and
-                                   rt_reproject_device and rt_debug_reproject */
+                                   rt_reproject_device and rt_debug_reproject, and rt_beam, rt_render_beams,
+                                   rt_render_beams_device, rt_debug_beam_rays and rt_camera_beams */
 
 typedef enum rt_status {
     RT_OK = 0,
@@ -643,6 +644,71 @@ int rt_render_rays(rt_scene* scene, const rt_ray* rays, int64_t n, int32_t spp, 
 int rt_render_rays_device(rt_scene* scene, const rt_ray* d_rays, int64_t n, int32_t spp, uint64_t seed,
                           uint64_t sample_base, uint64_t stream_base, double* d_sum, uint32_t* d_samples,
                           uint32_t* d_misses, unsigned long long* d_rays_count, void* stream);
+
+/*
+ * Beams: rt_render_rays with anti-aliasing.  All spp samples of a ray of rt_render_rays follow the same
+ * ray, so a host's own camera gets converged shading and aliased geometry.  A beam is a ray plus a
+ * first-order footprint, how its origin and its direction move across the pixel (or texel, or probe
+ * cell) it stands for, and every sample takes its own point (u, v) of the footprint from the two draws
+ * GetCameraRay spends on subX and subY, which rt_render_rays discards.  A frustum camera's unnormalised
+ * direction and an orthographic camera's origin are linear in the sample point, so both of the library's
+ * cameras are beams exactly (rt_camera_beams); for any other camera the beam is its first-order model.
+ */
+/* 192 B, twelve 16-byte rows.  w components are ignored but must be finite. */
+typedef struct rt_beam {
+    rt_vec4d origin, direction;          /* the ray at the footprint's corner (u, v) = (0, 0); direction need NOT be unit */
+    rt_vec4d origin_du, origin_dv;       /* origin(u, v)    = origin    + u * origin_du    + v * origin_dv    */
+    rt_vec4d direction_du, direction_dv; /* direction(u, v) = direction + u * direction_du + v * direction_dv, then normalised */
+} rt_beam;
+/*
+ * Sample k of beam i (normative; F = round to nearest fp32; every fp32 operation is rounded on its own,
+ * nothing is contracted into a fused multiply-add):
+ *   rng = rt_rng_init(seed, stream_base + i, sample_base + k); u = the first draw * 2^-24, v = the second
+ *   draw * 2^-24, both exact in fp32: the draws GetCameraRay spends on subX, subY.
+ *   per component c of x, y, z:
+ *     o_c = (F(origin_c)    + u * F(origin_du_c))    + v * F(origin_dv_c)
+ *     w_c = (F(direction_c) + u * F(direction_du_c)) + v * F(direction_dv_c)
+ *   n2 = (w_x * w_x + w_y * w_y) + w_z * w_z
+ *   The sample is degenerate if n2 is 0 or not finite, or a component of o is not finite: a primary miss
+ *   (misses += 1, nothing added to the sum, no ray counted); the beam's other samples are unaffected.
+ *   Otherwise d_c = w_c / sqrt(n2), IEEE square root and IEEE division, and the path is traced from (o, d)
+ *   as bounce 0 with the bounce draws following from the third draw on.
+ * A beam is invalid if one of its 24 doubles is not finite, or one of the 18 used ones is not after F:
+ * all spp samples are then primary misses and no ray is counted (rt_render_rays' rule for a bad ray).
+ * So sample k of beam i is, bit for bit, what rt_render_rays returns at spp = 1, sample_base + k and
+ * stream_base + i for the ray rt_debug_beam_rays reports for it.
+ *
+ * Everything else is rt_render_rays' contract with "ray" replaced by "beam": the accumulation into sum,
+ * samples, misses and the ray count; the independence of n, list position, chunking and wave (the
+ * samples per work item are a function of spp alone); the coherence note; the bound on n of the device
+ * entry; always the generic kernels; RT_ERR_STATE on a BVH2 scene; the argument errors, and n == 0
+ * returning RT_OK and touching nothing; the counters of rt_scene_get_stats, an armed rt_debug_ray_log,
+ * rt_kernel_times and the scene-specialised kernels left as they were; no camera needed.
+ * rt_render_beams works in chunks of at most 2^18 beams (RTCORE_QUERY_CHUNK sets a smaller size; fewer
+ * when spp is large, as for rt_render_rays), two of them resident: 112 MiB of beams and records on the
+ * device and as much pinned staging, in the buffers rt_render_rays uses (there 96 MiB each).
+ * Depth of field is not part of a beam: it would take two more draws.
+ */
+int rt_render_beams(rt_scene* scene, const rt_beam* beams, int64_t n, int32_t spp, uint64_t seed, uint64_t sample_base,
+                    uint64_t stream_base, rt_color* sum_rgb, uint32_t* samples, uint32_t* misses, uint64_t* rays_out);
+int rt_render_beams_device(rt_scene* scene, const rt_beam* d_beams, int64_t n, int32_t spp, uint64_t seed,
+                           uint64_t sample_base, uint64_t stream_base, double* d_sum, uint32_t* d_samples,
+                           uint32_t* d_misses, unsigned long long* d_rays_count, void* stream);
+/* Host only, no device: the twin.  rays_out[i * spp + k] = the fp32 ray of sample k of beam i, widened
+   (origin.w = 1, direction.w = 0); a degenerate sample or invalid beam gives an all-zero origin and direction
+   (a miss by rt_render_rays' rule).  uv_out (may be NULL) gets u, v per sample, uv_out[2 * (i * spp + k)]
+   and the entry after it.  Returns RT_OK / RT_ERR_ARG (a null pointer with n > 0, n < 0, spp <= 0). */
+int rt_debug_beam_rays(const rt_beam* beams, int64_t n, int32_t spp, uint64_t seed, uint64_t sample_base,
+                       uint64_t stream_base, rt_ray* rays_out, double* uv_out);
+/* Host only, no device: the beams of the pixels of a tile for the library's own cameras, out[x*h + y], in fp64
+   from Camera.InitRender's state (the function rt_camera_rays uses).
+   frustum: origin = position, direction = look + side*offX(x) + up*offY(y)  (GetRay's vector before
+            normalisation), direction_du = side * (tanX / w2), direction_dv = up * (tanY / h2), origin_d* = 0;
+   ortho:   origin = GetRay(x, y)'s origin, origin_du / origin_dv its step per pixel, direction = look, direction_d* = 0.
+   The pinhole footprint: image_plane and depth of field are not represented (documented, not an error).
+   RT_ERR_ARG as rt_camera_rays. */
+int rt_camera_beams(const rt_camera* camera, int32_t width, int32_t height, int32_t x0, int32_t y0, int32_t w,
+                    int32_t h, rt_beam* out);
 
 /* ----------------------------------------------------------- adaptive sampling --- */
 /*

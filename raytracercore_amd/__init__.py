@@ -139,6 +139,12 @@ class rt_ray(C.Structure):
     _fields_ = [("origin", rt_vec4d), ("direction", rt_vec4d)]
 
 
+class rt_beam(C.Structure):
+    """A ray and its first-order footprint (rt_render_beams): 192 B, twelve 16-byte rows."""
+    _fields_ = [("origin", rt_vec4d), ("direction", rt_vec4d), ("origin_du", rt_vec4d), ("origin_dv", rt_vec4d),
+                ("direction_du", rt_vec4d), ("direction_dv", rt_vec4d)]
+
+
 class rt_hit(C.Structure):
     """One answer of rt_query_rays (Hit.cs): 48 B, offsets in include/rtcore.h."""
     _fields_ = [
@@ -223,6 +229,8 @@ SELECTION_DTYPE = np.dtype([("item", np.int32), ("reserved", np.int32), ("distan
 
 # the same records as numpy structured dtypes (GpuRaytracer.query_rays, camera_rays)
 RAY_DTYPE = np.dtype([("origin", np.float64, (4,)), ("direction", np.float64, (4,))])
+BEAM_DTYPE = np.dtype([(f, np.float64, (4,)) for f in
+                       ("origin", "direction", "origin_du", "origin_dv", "direction_du", "direction_dv")])
 HIT_DTYPE = np.dtype([
     ("prim_id", np.int32), ("inside", np.int32), ("distance", np.float64),
     ("position", np.float32, (3,)), ("normal", np.float32, (3,)), ("reserved", np.int32, (2,)),
@@ -233,7 +241,8 @@ HIT_DTYPE = np.dtype([
 _OPTIONAL = ("rt_query_rays", "rt_query_rays_device", "rt_camera_rays", "rt_select_pixels", "rt_select_pixels_device",
              "rt_select_rays", "rt_select_rays_device", "rt_render_rays", "rt_render_rays_device",
              "rt_occluded_rays", "rt_occluded_rays_device", "rt_render_pixels", "rt_render_pixels_device",
-             "rt_adaptive_select_device", "rt_primary_hits_device", "rt_denoise_device", "rt_reproject_device")
+             "rt_adaptive_select_device", "rt_primary_hits_device", "rt_denoise_device", "rt_reproject_device",
+             "rt_render_beams", "rt_render_beams_device", "rt_camera_beams")
 
 _lib: Optional[C.CDLL] = None
 
@@ -340,6 +349,13 @@ def load_library(path: str = "") -> C.CDLL:
                                      P(rt_color), P(C.c_uint32), P(C.c_uint32), P(C.c_uint64)]),
         "rt_render_rays_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64,
                                             C.c_uint64] + [C.c_void_p] * 4 + [C.c_void_p]),
+        "rt_render_beams": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64,
+                                      P(rt_color), P(C.c_uint32), P(C.c_uint32), P(C.c_uint64)]),
+        "rt_render_beams_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64,
+                                             C.c_uint64] + [C.c_void_p] * 4 + [C.c_void_p]),
+        "rt_debug_beam_rays": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64,
+                                         C.c_void_p, C.c_void_p]),
+        "rt_camera_beams": (C.c_int, [P(rt_camera)] + [C.c_int32] * 6 + [C.c_void_p]),
         "rt_occluded_rays": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
         "rt_occluded_rays_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                               C.c_void_p]),
@@ -578,6 +594,60 @@ def _pack_rays(origins, directions) -> np.ndarray:
     rays["origin"][:, :o.shape[1]] = o
     rays["direction"][:, :d.shape[1]] = d
     return rays
+
+
+def _pack_beams(origins, directions, origin_du, origin_dv, direction_du, direction_dv) -> np.ndarray:
+    """Six (n, 3) or (n, 4) arrays -> a contiguous BEAM_DTYPE array (origin w = 1, every other w = 0); or
+    one BEAM_DTYPE array as camera_beams returns it, with the other five None."""
+    rest = (directions, origin_du, origin_dv, direction_du, direction_dv)
+    if all(a is None for a in rest):
+        return np.ascontiguousarray(origins, BEAM_DTYPE).reshape(-1)
+    if any(a is None for a in rest):
+        raise ValueError("beams: six arrays, or one BEAM_DTYPE array and None for the other five")
+    parts = [np.asarray(a, np.float64) for a in (origins,) + rest]
+    n = parts[0].shape[0] if parts[0].ndim == 2 else -1
+    if any(a.ndim != 2 or a.shape[0] != n or a.shape[1] not in (3, 4) for a in parts):
+        raise ValueError("origins, directions and the four footprint arrays must be (n, 3) or (n, 4) arrays of the same n")
+    beams = np.zeros(n, BEAM_DTYPE)
+    beams["origin"][:, 3] = 1.0
+    for name, a in zip(BEAM_DTYPE.names, parts):
+        beams[name][:, :a.shape[1]] = a
+    return beams
+
+
+def beam_rays_host(origins, directions, origin_du, origin_dv, direction_du, direction_dv, spp: int, seed: int,
+                   sample_base: int = 0, stream_base: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    """rt_debug_beam_rays (host code, no GPU): the kernels' sample start compiled for the CPU.  Returns
+    (rays [n, spp] of RAY_DTYPE, uv [n, spp, 2] f64): the fp32 ray of sample k of beam i, widened (all zero
+    for a degenerate sample or an invalid beam), and its point in the footprint.  render_rays of rays[:, k]
+    at spp 1, sample_base + k and the same stream_base gives render_beams' sample k, bit for bit."""
+    lib = load_library()
+    if not hasattr(lib, "rt_debug_beam_rays"):
+        raise RtError("this build of the library has no rt_debug_beam_rays")
+    beams = _pack_beams(origins, directions, origin_du, origin_dv, direction_du, direction_dv)
+    n = beams.shape[0]
+    rays = np.zeros((n, max(spp, 0)), RAY_DTYPE)
+    uv = np.zeros((n, max(spp, 0), 2), np.float64)
+    _check(lib.rt_debug_beam_rays(beams.ctypes.data_as(C.c_void_p), n, spp, seed, sample_base, stream_base,
+                                  rays.ctypes.data_as(C.c_void_p), uv.ctypes.data_as(C.c_void_p)))
+    return rays, uv
+
+
+def camera_beams(camera: rt_camera, size: Tuple[int, int], x0: int = 0, y0: int = 0, w: Optional[int] = None,
+                 h: Optional[int] = None) -> np.ndarray:
+    """rt_camera_beams (host code, no GPU): the beams of the pixels of a tile of a size[0] x size[1] frame
+    for the library's own cameras, as a BEAM_DTYPE array indexed [x, y] (the pinhole footprint: no image
+    plane offset, no depth of field)."""
+    lib = load_library()
+    if not hasattr(lib, "rt_camera_beams"):
+        raise RtError("this build of the library has no rt_camera_beams")
+    W, H = int(size[0]), int(size[1])
+    w = W - x0 if w is None else w
+    h = H - y0 if h is None else h
+    out = np.zeros((max(w, 0), max(h, 0)), BEAM_DTYPE)
+    cam = rt_camera.from_buffer_copy(camera)
+    _check(lib.rt_camera_beams(C.byref(cam), W, H, x0, y0, w, h, out.ctypes.data_as(C.c_void_p)))
+    return out
 
 
 def _pack_items(items) -> np.ndarray:
@@ -892,6 +962,34 @@ class GpuRaytracer:
         _check(self.lib.rt_render_rays_device(self.handle, C.c_void_p(d_ray_list), n, spp, seed, sample_base,
                                               stream_base, C.c_void_p(d_sum), C.c_void_p(d_samples),
                                               C.c_void_p(d_misses), C.c_void_p(d_rays), C.c_void_p(stream)))
+
+    def render_beams(self, origins, directions, origin_du, origin_dv, direction_du, direction_dv, spp: int, seed: int,
+                     sample_base: int = 0, stream_base: int = 0, out=None):
+        """rt_render_beams: render_rays with each sample at its own point of the beam's footprint,
+        origin + u origin_du + v origin_dv and direction + u direction_du + v direction_dv (normalised on the
+        device), (u, v) from the two draws render_rays discards.  Six (n, 3) or (n, 4) arrays, or one
+        BEAM_DTYPE array (camera_beams) with the other five None.  Returns and `out` as render_rays."""
+        beams = _pack_beams(origins, directions, origin_du, origin_dv, direction_du, direction_dv)
+        n = beams.shape[0]
+        if out is None:
+            out = (np.zeros((n, 3), np.float64), np.zeros(n, np.uint32), np.zeros(n, np.uint32))
+        s, ns, ms = out
+        for a, shape, dt in ((s, (n, 3), np.float64), (ns, (n,), np.uint32), (ms, (n,), np.uint32)):
+            if a.shape != shape or a.dtype != dt or not a.flags.c_contiguous:
+                raise ValueError("out must be C-contiguous (sum f64 [n, 3], samples u32 [n], misses u32 [n])")
+        count = C.c_uint64(0)
+        _check(self.lib.rt_render_beams(self.handle, beams.ctypes.data_as(C.c_void_p), n, spp, seed, sample_base,
+                                        stream_base, s.ctypes.data_as(C.POINTER(rt_color)),
+                                        ns.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                        ms.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(count)))
+        return s, ns, ms, count.value
+
+    def render_beams_device(self, d_beam_list: int, n: int, spp: int, seed: int, sample_base: int, stream_base: int,
+                            d_sum: int, d_samples: int, d_misses: int, d_rays: int = 0, stream: int = 0) -> None:
+        """rt_render_beams_device: render_rays_device for n rt_beam (192 B each) at device pointer d_beam_list."""
+        _check(self.lib.rt_render_beams_device(self.handle, C.c_void_p(d_beam_list), n, spp, seed, sample_base,
+                                               stream_base, C.c_void_p(d_sum), C.c_void_p(d_samples),
+                                               C.c_void_p(d_misses), C.c_void_p(d_rays), C.c_void_p(stream)))
 
     def _pixel_list(self, pixels) -> np.ndarray:
         p = np.asarray(pixels)

@@ -1,6 +1,8 @@
 // api_render_rays.hip -- the C ABI's radiance queries (include/rtcore.h, "radiance queries"):
 // Raytracer.GetColor(ray) (Raytracer.cs:248-252) for rays the caller brings, by the RAYS instances of
-// the path kernels (kernels_path.hip, refill), accumulated as SampleSet accumulates a pixel.
+// the path kernels (kernels_path.hip, refill), accumulated as SampleSet accumulates a pixel.  The
+// launch, the argument check and the two entry points' bodies serve rt_render_beams as well
+// (api_render_beams.hip, the BEAMS instances): a RenderList says which records a list holds.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -11,17 +13,19 @@ namespace {
 
 constexpr int64_t kRaysChunk = 1 << 19;      // rays of one chunk of rt_render_rays (rt_query_rays' size and variable)
 constexpr uint64_t kChunkItems = 1ull << 26; // most work items of one chunk: 1 GiB of 16-B partials
+constexpr RenderList kRays = {ITEMS_RAYS, sizeof(rt_ray), kRaysChunk, "rays"};
 
-// The path kernel of the scene's variant, RAYS instance, over n rays at d_rays, and nothing after
-// it: the caller folds p's partials.  run_path without what rt_render_rays leaves alone: no timing
-// slot, no counters, no ray log, never the scene-specialised kernel.
-int run_rays(rt_scene* s, PathParams& p, const rt_ray* d_rays, unsigned long long* d_count, hipStream_t stream)
+// The path kernel of the scene's variant, the list's instance (RAYS or BEAMS), over the p.n_rays
+// records at d_list, and nothing after it: the caller folds p's partials.  run_path without what
+// rt_render_rays leaves alone: no timing slot, no counters, no ray log, never the scene-specialised kernel.
+int run_rays(rt_scene* s, const RenderList& kind, PathParams& p, const void* d_list, unsigned long long* d_count,
+             hipStream_t stream)
 {
     const size_t need = (size_t)p.n_chunks * (size_t)p.n_pad;
     uint64_t tickets = 0;
     for (int g = 0; g < p.n_split; g++) tickets += p.split_tickets[g];
     if (need > 0xF0000000ull || tickets > need / 64) { // (run_path's bound; the entry points check n first)
-        set_error("rt_render_rays: n x spp too large for one launch");
+        set_error(std::string("rt_render_") + kind.what + ": n x spp too large for one launch");
         return RT_ERR_ARG;
     }
     HIP_TRY(s->partial.reserve(need));
@@ -29,20 +33,23 @@ int run_rays(rt_scene* s, PathParams& p, const rt_ray* d_rays, unsigned long lon
     p.partial = s->partial.p;
     p.counter = s->counter.p;
     p.rays = d_count;
-    p.ray_list = reinterpret_cast<const double2*>(d_rays);
+    p.ray_list = reinterpret_cast<const double2*>(d_list); // (beam_list is the same storage)
     if (s->any_op && stream != s->last_stream) HIP_TRY(hipStreamWaitEvent(stream, s->done_ev, 0));
     HIP_TRY(hipMemsetAsync(p.counter, 0, sizeof(unsigned int) * kSplitStride * p.n_split, stream));
     const size_t dyn = path_dyn_lds(s->dev, s->variant);
-    if (s->rays_variant != s->variant) {
-        s->rays_blocks_per_cu = path_blocks_per_cu(s->variant, dyn, false, s->dev.n_vn > 0, ITEMS_RAYS);
-        s->rays_variant = s->variant;
+    const bool beams = kind.src == ITEMS_BEAMS;
+    int& cached_variant = beams ? s->beams_variant : s->rays_variant;
+    int& blocks_per_cu = beams ? s->beams_blocks_per_cu : s->rays_blocks_per_cu;
+    if (cached_variant != s->variant) {
+        blocks_per_cu = path_blocks_per_cu(s->variant, dyn, false, s->dev.n_vn > 0, kind.src);
+        cached_variant = s->variant;
     }
-    int grid = s->n_cu * s->rays_blocks_per_cu;
+    int grid = s->n_cu * blocks_per_cu;
     if ((s->variant >> 1) < 2) { // a small brute-force launch runs fewer blocks per CU (see run_path)
         const double samples = (double)p.n_rays * (double)p.spp;
         int cap = (int)std::ceil(samples / ((double)s->n_cu * 256.0 * 6.0));
         if (const char* e = getenv("RTCORE_GRID_BPC")) cap = atoi(e);
-        grid = s->n_cu * std::min(s->rays_blocks_per_cu, std::max(1, cap));
+        grid = s->n_cu * std::min(blocks_per_cu, std::max(1, cap));
     } else {
         HIP_TRY(s->stack_ovf.reserve((size_t)grid * 256 * kStackOverflow));
         p.stack_ovf = s->stack_ovf.p;
@@ -51,7 +58,7 @@ int run_rays(rt_scene* s, PathParams& p, const rt_ray* d_rays, unsigned long lon
     const PathParams* pa = nullptr;
     const int rc = upload_params(s, p, stream, &pa);
     if (rc != RT_OK) return rc;
-    HIP_TRY(launch_path(s->dev, s->camf_d.p, pa, s->variant, grid, stream, false, ITEMS_RAYS));
+    HIP_TRY(launch_path(s->dev, s->camf_d.p, pa, s->variant, grid, stream, false, kind.src));
     return RT_OK;
 }
 
@@ -80,24 +87,25 @@ int check_render_rays(rt_scene* s, const void* rays, int64_t n, int32_t spp, con
 
 } // namespace
 
-extern "C" {
+namespace rtc {
 
-int rt_render_rays_device(rt_scene* s, const rt_ray* d_rays, int64_t n, int32_t spp, uint64_t seed, uint64_t sample_base,
-                          uint64_t stream_base, double* d_sum, uint32_t* d_samples, uint32_t* d_misses,
-                          unsigned long long* d_count, void* stream)
+int render_list_device(rt_scene* s, const RenderList& kind, const char* name, const void* d_list, int64_t n, int32_t spp,
+                       uint64_t seed, uint64_t sample_base, uint64_t stream_base, double* d_sum, uint32_t* d_samples,
+                       uint32_t* d_misses, unsigned long long* d_count, void* stream)
 {
     bool empty;
-    int rc = check_render_rays(s, d_rays, n, spp, d_sum, d_samples, d_misses, "rt_render_rays_device", &empty);
+    int rc = check_render_rays(s, d_list, n, spp, d_sum, d_samples, d_misses, name, &empty);
     if (rc != RT_OK || empty) return rc;
     const int kernel = s->variant >> 1;
     if (n > render_rays_max_n(kernel, spp)) {
-        set_error("rt_render_rays_device: more rays than one launch's 32-bit work items hold at this spp; split the list");
+        set_error(std::string(name) + ": more " + kind.what +
+                  " than one launch's 32-bit work items hold at this spp; split the list");
         return RT_ERR_ARG;
     }
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     PathParams p = make_params_rays(kernel, n, spp, seed, sample_base, stream_base);
-    rc = run_rays(s, p, d_rays, d_count ? d_count : s->rays.p, st); // (no count wanted: the scene's scratch word)
+    rc = run_rays(s, kind, p, d_list, d_count ? d_count : s->rays.p, st); // (no count wanted: the scene's scratch word)
     if (rc != RT_OK) return rc;
     HIP_TRY(launch_accumulate_rays(p, d_sum, d_samples, d_misses, nullptr, st));
     return end_op(s, st);
@@ -107,21 +115,25 @@ int rt_render_rays_device(rt_scene* s, const rt_ray* d_rays, int64_t n, int32_t 
 // through pinned staging to device slot k & 1 on copy_stream, its launch runs on the scene's stream once
 // they have landed, and its records (one TileRec per ray, folded from zero) come back on copy_stream
 // into the staging slot the host pool then adds into the caller's arrays.  The partials are one
-// buffer: launch k + 1 follows fold k on the scene's stream.
-int rt_render_rays(rt_scene* s, const rt_ray* rays, int64_t n, int32_t spp, uint64_t seed, uint64_t sample_base,
-                   uint64_t stream_base, rt_color* sum_rgb, uint32_t* samples, uint32_t* misses, uint64_t* rays_out)
+// buffer: launch k + 1 follows fold k on the scene's stream.  A record of the list takes R =
+// rec_bytes / sizeof(rt_ray) entries of query_rays and of the staging's ray slots (a beam: 3).
+int render_list_host(rt_scene* s, const RenderList& kind, const char* name, const void* list, int64_t n, int32_t spp,
+                     uint64_t seed, uint64_t sample_base, uint64_t stream_base, rt_color* sum_rgb, uint32_t* samples,
+                     uint32_t* misses, uint64_t* rays_out)
 {
     bool empty;
-    int rc = check_render_rays(s, rays, n, spp, sum_rgb, samples, misses, "rt_render_rays", &empty);
+    int rc = check_render_rays(s, list, n, spp, sum_rgb, samples, misses, name, &empty);
     if (rc != RT_OK || empty) return rc;
     const int kernel = s->variant >> 1;
-    int64_t chunk = kRaysChunk;
-    if (const char* e = getenv("RTCORE_QUERY_CHUNK")) chunk = std::max<int64_t>(1, std::min<int64_t>(kRaysChunk, atoll(e)));
+    const size_t R = kind.rec_bytes / sizeof(rt_ray);
+    const rt_ray* rays = static_cast<const rt_ray*>(list);
+    int64_t chunk = kind.chunk;
+    if (const char* e = getenv("RTCORE_QUERY_CHUNK")) chunk = std::max<int64_t>(1, std::min<int64_t>(kind.chunk, atoll(e)));
     // a chunk's partials stay below kChunkItems items (whole blocks of 64 rays), whatever spp is
     const PathParams probe = make_params_rays(kernel, 64, spp, seed, sample_base, stream_base);
     const int64_t fit = (int64_t)(kChunkItems / ((uint64_t)probe.n_chunks * 64u)) * 64;
     if (fit < 64) {
-        set_error("rt_render_rays: spp too large for one launch; render it in several calls (sample_base)");
+        set_error(std::string(name) + ": spp too large for one launch; render it in several calls (sample_base)");
         return RT_ERR_ARG;
     }
     chunk = std::min(std::min(chunk, fit), n);
@@ -129,10 +141,10 @@ int rt_render_rays(rt_scene* s, const rt_ray* rays, int64_t n, int32_t spp, uint
     if (!s->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
     HIP_TRY(hipStreamSynchronize(s->copy_stream)); // (copies a failed call left behind: see rt_render_tile)
     const size_t C = (size_t)chunk;
-    HIP_TRY(s->query_rays.reserve(2 * C));
+    HIP_TRY(s->query_rays.reserve(2 * C * R));
     HIP_TRY(s->render_rays_recs.reserve(2 * C));
     // pinned staging: the two record slots (at the offsets queue_copy gives them), then the two ray slots
-    HIP_TRY(s->stage.reserve(2 * C * (sizeof(TileRec) + sizeof(rt_ray))));
+    HIP_TRY(s->stage.reserve(2 * C * (sizeof(TileRec) + kind.rec_bytes)));
     HIP_TRY(s->rays_h.reserve(1));
     rt_ray* stage_rays = reinterpret_cast<rt_ray*>(s->stage.p + 2 * C * sizeof(TileRec));
     for (int j = 0; j < 2; j++) {
@@ -145,8 +157,8 @@ int rt_render_rays(rt_scene* s, const rt_ray* rays, int64_t n, int32_t spp, uint
     const int64_t K = (n + chunk - 1) / chunk;
     auto count = [&](int64_t k) { return (size_t)std::min(chunk, n - k * chunk); };
     auto upload = [&](int64_t k) -> int {
-        const size_t m = count(k), slot = (size_t)(k & 1) * C;
-        const rt_ray* src = rays + k * chunk;
+        const size_t m = count(k) * R, slot = (size_t)(k & 1) * C * R; // in rt_ray entries
+        const rt_ray* src = rays + (size_t)(k * chunk) * R;
         parallel_ranges(m, 65536, [&](size_t a, size_t b) { std::memcpy(stage_rays + slot + a, src + a, (b - a) * sizeof(rt_ray)); });
         HIP_TRY(hipMemcpyAsync(s->query_rays.p + slot, stage_rays + slot, m * sizeof(rt_ray), hipMemcpyHostToDevice,
                                s->copy_stream));
@@ -174,7 +186,7 @@ int rt_render_rays(rt_scene* s, const rt_ray* rays, int64_t n, int32_t spp, uint
         const size_t m = count(k), slot = (size_t)(k & 1) * C;
         HIP_TRY(hipStreamWaitEvent(st, s->query_up_ev[k & 1], 0));
         PathParams p = make_params_rays(kernel, (int64_t)m, spp, seed, sample_base, stream_base + (uint64_t)(k * chunk));
-        rc = run_rays(s, p, s->query_rays.p + slot, s->rays.p, st);
+        rc = run_rays(s, kind, p, s->query_rays.p + slot * R, s->rays.p, st);
         if (rc != RT_OK) return rc;
         HIP_TRY(launch_accumulate_rays(p, nullptr, nullptr, nullptr, s->render_rays_recs.p + slot, st));
         HIP_TRY(hipEventRecord(s->band_ev[k & 1], st));
@@ -201,6 +213,25 @@ int rt_render_rays(rt_scene* s, const rt_ray* rays, int64_t n, int32_t spp, uint
     if (rc != RT_OK) return rc;
     if (rays_out) *rays_out += s->rays_h.p[0];
     return RT_OK;
+}
+
+} // namespace rtc
+
+extern "C" {
+
+int rt_render_rays_device(rt_scene* s, const rt_ray* d_rays, int64_t n, int32_t spp, uint64_t seed, uint64_t sample_base,
+                          uint64_t stream_base, double* d_sum, uint32_t* d_samples, uint32_t* d_misses,
+                          unsigned long long* d_count, void* stream)
+{
+    return render_list_device(s, kRays, "rt_render_rays_device", d_rays, n, spp, seed, sample_base, stream_base, d_sum,
+                              d_samples, d_misses, d_count, stream);
+}
+
+int rt_render_rays(rt_scene* s, const rt_ray* rays, int64_t n, int32_t spp, uint64_t seed, uint64_t sample_base,
+                   uint64_t stream_base, rt_color* sum_rgb, uint32_t* samples, uint32_t* misses, uint64_t* rays_out)
+{
+    return render_list_host(s, kRays, "rt_render_rays", rays, n, spp, seed, sample_base, stream_base, sum_rgb, samples,
+                            misses, rays_out);
 }
 
 } // extern "C"

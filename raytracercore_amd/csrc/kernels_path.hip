@@ -24,6 +24,7 @@
 // primitive branch-free.  BVH traversal keeps a per-lane stack in LDS.
 #include "../../include/rtcore_rng.h"
 #include "rt_kernels.h"
+#include "rt_beam.h"
 #ifdef RT_SCENE_CONST
 // rt_jit.cpp generates this header per scene (and camera, for the grouped order): the launch's
 // PathScene and its brute-force records as 32-bit words (kSceneW, kGroupsW, kRectsW, kFramesW,
@@ -1357,6 +1358,11 @@ __device__ __forceinline__ int item_sample(const Lane& L, const ParT& p)
 // two draws GetCameraRay would have spent discarded; the camera is never read.  The brute-force
 // kernels keep the ray index in L.fx; every kernel loads the ray's rows again at each sample start
 // (they stay in the cache between an item's samples) instead of holding six more registers.
+// ITEMS_BEAMS (rt_render_beams' instances): the RAYS instances with an rt_beam of p.beam_list in the
+// ray's place.  An item opens as a ray's does; a sample start loads the beam's twelve rows again and
+// builds the sample's ray at the point (u, v) of the footprint that the two GetCameraRay draws name
+// (beam_sample, rt_beam.h: the copy the host twin compiles too).  A degenerate sample closes as one
+// primary miss without a query, an invalid beam closes all the item has left.
 // ITEMS_PIXELS (rt_render_pixels' instances): an item names entry item_ray(item) of p.pixel_list, a
 // frame pixel index fy * width + fx, and from there on the lane does what a tile launch does for that
 // frame pixel: its key from the table or the hash, the rng of sample_base + sample, start_sample with
@@ -1515,7 +1521,7 @@ __device__ __forceinline__ void refill(Lane& L, Sample& S, const ParT& p, const 
                         }
                     }
                 }
-            } else if constexpr (SRC == ITEMS_RAYS) {
+            } else if constexpr (SRC == ITEMS_RAYS || SRC == ITEMS_BEAMS) {
                 const unsigned ri = item_ray(L.item, p);
                 const int s0 = (int)((L.item >> 6) & (unsigned)(p.n_chunks - 1)) * p.chunk;
                 if (ri < p.n_rays && s0 < p.spp) {
@@ -1590,6 +1596,32 @@ __device__ __forceinline__ void refill(Lane& L, Sample& S, const ParT& p, const 
             } else { // every sample the item has left is a primary miss; no query, so no ray counted
                 const unsigned left = L.cnt >> 16;
                 L.cnt = (L.cnt & 0xFFFFu) + (left << 8);
+                if (!NT) L.s_next += (int)left;
+            }
+        }
+        return;
+    }
+    if constexpr (SRC == ITEMS_BEAMS) {
+        if (L.active && L.item_open && !L.live && L.cnt >= 65536u) {
+            const unsigned bi = NT ? item_ray(L.item, p) : (unsigned)L.fx;
+            if (NT) L.pkey = rt_rng_pixel_key(p.seed_key, p.stream_base + (unsigned long long)bi);
+            S.rng = rt_rng_from_pixel_key(L.pkey, p.sample_base + (unsigned long long)item_sample<NT>(L, p));
+            // GetCameraRay's subX and subY (Raytracer.cs:264-265): the sample's point in the footprint
+            const float u = (float)rt_rng_next24(&S.rng) * 0x1p-24f;
+            const float v = (float)rt_rng_next24(&S.rng) * 0x1p-24f;
+            BeamV o, d;
+            const BeamSample r = beam_sample(p.beam_list + (size_t)kBeamRows * (size_t)bi, u, v, o, d);
+            if (r == BEAM_RAY) {
+                S.o = v3(o.x, o.y, o.z);
+                S.d = v3(d.x, d.y, d.z);
+                S.tint = v3(1.0f, 1.0f, 1.0f);
+                S.bounce = 0;
+                S.prev = -1;
+                L.live = true;
+            } else { // no query, so no ray counted: one primary miss, and the lane asks again for its next
+                     // sample; or, for an invalid beam, every sample the item has left (the rays' rule)
+                const unsigned left = r == BEAM_INVALID ? L.cnt >> 16 : 1u;
+                L.cnt += left * (256u - 65536u);
                 if (!NT) L.s_next += (int)left;
             }
         }
@@ -1851,8 +1883,8 @@ __device__ __forceinline__ void path_body(const CameraF* __restrict__ camp, cons
     flush_counts<STATS>(wave_rays, cnt, *(const ParamsC*)pp, lane);
 }
 
-// SRC: ITEMS_RAYS / ITEMS_PIXELS, rt_render_rays' / rt_render_pixels' instances (refill); the tile
-// instances are as they were without the switch.
+// SRC: ITEMS_RAYS / ITEMS_PIXELS / ITEMS_BEAMS, rt_render_rays' / rt_render_pixels' / rt_render_beams'
+// instances (refill); the tile instances are as they were without the switch.
 template <bool CULL, bool LDS, bool STATS, bool VN, int SRC = ITEMS_TILE>
 __global__ void __launch_bounds__(256, CULL ? RT_GROUPED_WAVES : RT_PATH_WAVES)
     path_kernel(PathScene, const CameraF* __restrict__ camp, const PathParams* __restrict__ pp, const TestRec*,
@@ -2868,6 +2900,8 @@ PathKernel pick_brute(bool stats, bool vn, ItemSource src)
         return vn ? path_kernel<CULL, LDS, false, true, ITEMS_PIXELS> : path_kernel<CULL, LDS, false, false, ITEMS_PIXELS>;
     if (src == ITEMS_RAYS)
         return vn ? path_kernel<CULL, LDS, false, true, ITEMS_RAYS> : path_kernel<CULL, LDS, false, false, ITEMS_RAYS>;
+    if (src == ITEMS_BEAMS)
+        return vn ? path_kernel<CULL, LDS, false, true, ITEMS_BEAMS> : path_kernel<CULL, LDS, false, false, ITEMS_BEAMS>;
     if (vn) return stats ? path_kernel<CULL, LDS, true, true> : path_kernel<CULL, LDS, false, true>;
     return stats ? path_kernel<CULL, LDS, true, false> : path_kernel<CULL, LDS, false, false>;
 }
@@ -2886,14 +2920,20 @@ PathKernel pick_bvh(bool stats, bool vn, ItemSource src)
                       : path_kernel_bvh<WIDTH, STACK, LDS, false, false, ITEMS_RAYS>;
         return nullptr;
     }
+    if (src == ITEMS_BEAMS) { // (the wide kernel only, as for the rays)
+        if constexpr (WIDTH == 4)
+            return vn ? path_kernel_bvh<WIDTH, STACK, LDS, false, true, ITEMS_BEAMS>
+                      : path_kernel_bvh<WIDTH, STACK, LDS, false, false, ITEMS_BEAMS>;
+        return nullptr;
+    }
     if (vn) return stats ? path_kernel_bvh<WIDTH, STACK, LDS, true, true> : path_kernel_bvh<WIDTH, STACK, LDS, false, true>;
     return stats ? path_kernel_bvh<WIDTH, STACK, LDS, true, false> : path_kernel_bvh<WIDTH, STACK, LDS, false, false>;
 }
 
 // variant = kernel * 2 + lds; kernel 0 brute force (flat), 1 brute force (grouped, culled),
 // 2 BVH2 (24-entry LDS stack), 3 wide BVH (RT_WIDE_STACK-entry LDS stack); both overflow to global memory.
-// src: ITEMS_RAYS / ITEMS_PIXELS, rt_render_rays' / rt_render_pixels' instance of the variant (never
-// instrumented; none for the BVH2 kernel)
+// src: ITEMS_RAYS / ITEMS_PIXELS / ITEMS_BEAMS, rt_render_rays' / rt_render_pixels' / rt_render_beams'
+// instance of the variant (never instrumented; none for the BVH2 kernel)
 PathKernel pick(int variant, bool stats, bool vn, ItemSource src = ITEMS_TILE)
 {
     switch (variant) {

@@ -9,8 +9,9 @@ constexpr int kMaxSplit = 8;     // item ranges of a launch: one per XCD of the 
 constexpr int kSplitStride = 32; // dispenser words apart (one 128-B line each)
 
 // Where the work items of a path launch come from (refill, kernels_path.hip): the pixels of a window,
-// a caller's rays (rt_render_rays) or a list of frame pixels (rt_render_pixels).
-enum ItemSource : int { ITEMS_TILE = 0, ITEMS_RAYS = 1, ITEMS_PIXELS = 2 };
+// a caller's rays (rt_render_rays), a list of frame pixels (rt_render_pixels) or a caller's beams
+// (rt_render_beams).
+enum ItemSource : int { ITEMS_TILE = 0, ITEMS_RAYS = 1, ITEMS_PIXELS = 2, ITEMS_BEAMS = 3 };
 
 // Work decomposition of one path-tracing launch over a w x h tile.
 struct PathParams {
@@ -100,6 +101,8 @@ struct PathParams {
     // pixel_list[i] = fy * scene.width + fx, and an entry at or past n_frame_px is skipped.  The list's
     // fields share the rays' storage, so that the record keeps its size and no field moves: the kernels
     // that take it by value are as they were.
+    // rt_render_beams, the BEAMS instances only: the launch is planned as for the rays, and entry i of
+    // beam_list is an rt_beam as twelve rows (rt_beam.h); the pointer shares the rays' storage too.
     // Start rows, the brute-force tile instances only (run_path plans them, plan_start_rows; null / 0:
     // off): float4 starts[wave][start_rows][64], wave = blockIdx.x * 4 + threadIdx.x / 64 of the
     // persistent grid, start_rows = chunk.  A wave that opens items writes every camera sample of a
@@ -110,6 +113,7 @@ struct PathParams {
     union {
         const double2* ray_list;    // four 16-B rows per ray (origin xy, origin zw, direction xy, direction zw)
         const uint32_t* pixel_list; // frame pixel indices
+        const double2* beam_list;   // twelve 16-B rows per beam (rt_beam: origin, direction, their steps in u and v)
         float4* starts;
     };
     unsigned int n_rays;        // rays or list entries of the launch (the items of the last block past it stay closed)
@@ -287,8 +291,9 @@ size_t path_dyn_lds(const DevScene& s, int variant); // all dynamic LDS of a var
 // Launch the persistent kernel; stats counts node visits / primitive tests (slower build).
 // The camera and the launch parameters are read from device memory (d_cam, d_params).
 // src: ITEMS_RAYS, rt_render_rays' instance of the variant (PathParams::ray_list), which does not read
-// the camera; ITEMS_PIXELS, rt_render_pixels' (PathParams::pixel_list).  Both exist for the brute-force
-// and the wide BVH kernels and are never instrumented.
+// the camera; ITEMS_PIXELS, rt_render_pixels' (PathParams::pixel_list); ITEMS_BEAMS, rt_render_beams'
+// (PathParams::beam_list, no camera either).  All exist for the brute-force and the wide BVH kernels
+// and are never instrumented.
 hipError_t launch_path(const DevScene& s, const CameraF* d_cam, const PathParams* d_params, int variant,
                        int grid_blocks, hipStream_t stream, bool stats, ItemSource src = ITEMS_TILE);
 // vn: scene has vertex-normal triangles
