@@ -283,6 +283,26 @@ int rt_debug_scene_bound(const rt_prim* prims, int32_t n_prims, float* lo, float
 int rt_debug_block_cull(const rt_prim* prims, int32_t n_prims, const rt_camera* camera, int32_t width, int32_t height,
                         int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t band, int32_t band_stride,
                         int32_t band_offset, uint8_t* dead, int64_t cap, int32_t* info);
+/* Host only (no device needed): the first bounce of a flat brute-force launch -- the test units of the
+   flat order (each world rectangle, each world box, each frame with its rectangles and its box, each
+   triangle record, each sphere record, in the order the kernel tests them) and, for every live 8x8 block
+   of the window, a 64-bit mask whose bit u is clear when no camera ray of the block's pixels can meet
+   unit u, by the block cull's own test and margins on the unit's padded box.  A wave whose live lanes
+   all hold camera rays of one block tests those units alone; the results are the same bit for bit
+   (RTCORE_FIRST_BOUNCE=0 turns it off).  The window and the band set as rt_debug_block_cull takes them.
+   unit_first (optional, 65 entries) gets the first entry of each unit in unit_ids and the total after
+   the last; unit_ids the primitive IDs the units stand for, while they fit in cap_ids; unit_box
+   (optional, 6 floats per unit, 64 units) each unit's padded box, lo then hi; dead one byte per block
+   and masks one word per live block, in the blocks' order, while they fit in cap_blocks; info
+   (optional, 6 entries) {blocks per row, block rows, live blocks, 1 when the masks are in use, entries
+   of unit_ids, the pad as float bits}.  The masks are all ones and not in use when the scene has
+   planes, vertex-normal triangles, more than 64 units or no finite bound, or when the launch has no
+   cull record: no block is dead (a camera inside the bound, depth of field).  Returns the number of
+   units or a negative rt_status. */
+int rt_debug_block_units(const rt_prim* prims, int32_t n_prims, const rt_camera* camera, int32_t width, int32_t height,
+                         int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t band, int32_t band_stride,
+                         int32_t band_offset, int32_t* unit_first, int32_t* unit_ids, int64_t cap_ids, float* unit_box,
+                         uint8_t* dead, uint64_t* masks, int64_t cap_blocks, int32_t* info);
 /* Host only (no device needed): the start rows of a brute-force launch -- a wave that opens work items
    builds every camera ray of those items with all its lanes and keeps them as 16-B rows in a buffer
    of its own, and a lane's sample start loads its row instead of building the ray; the results are

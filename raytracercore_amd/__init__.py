@@ -329,6 +329,9 @@ def load_library(path: str = "") -> C.CDLL:
         "rt_debug_scene_bound": (C.c_int, [P(rt_prim), C.c_int32, P(C.c_float), P(C.c_float), P(C.c_float)]),
         "rt_debug_block_cull": (C.c_int, [P(rt_prim), C.c_int32, P(rt_camera)] + [C.c_int32] * 9 +
                                 [P(C.c_uint8), C.c_int64, P(C.c_int32)]),
+        "rt_debug_block_units": (C.c_int, [P(rt_prim), C.c_int32, P(rt_camera)] + [C.c_int32] * 9 +
+                                 [P(C.c_int32), P(C.c_int32), C.c_int64, P(C.c_float), P(C.c_uint8), P(C.c_uint64),
+                                  C.c_int64, P(C.c_int32)]),
         "rt_debug_start_rows": (C.c_int, [C.c_int32, P(rt_camera)] + [C.c_int32] * 6 + [P(C.c_int64)]),
         "rt_debug_ray_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
         "rt_debug_vn_rehit": (C.c_int, [P(C.c_double), P(C.c_double), P(C.c_double), C.c_int32, C.c_double,
@@ -525,6 +528,45 @@ def block_cull(prims: Sequence[rt_prim], camera: rt_camera, size: Tuple[int, int
     if live < 0:
         _check(live)
     return dead[:bx * by].reshape(by, bx).astype(bool), int(live)
+
+
+def block_units(prims: Sequence[rt_prim], camera: rt_camera, size: Tuple[int, int],
+                window: Optional[Tuple[int, int, int, int]] = None,
+                bands: Optional[Tuple[int, int, int]] = None) -> dict:
+    """rt_debug_block_units (host code, no GPU): the flat order's test units and, per live 8x8 block of a
+    brute-force launch, the units its camera rays can meet.  Arguments as block_cull's.  Returns n_units,
+    ids (per unit, the primitive IDs it stands for), box (float32 [n_units, 2, 3]: each unit's padded box;
+    empty past 64 units), pad, dead (bool [block rows, blocks per row]), live, masks (uint64 per live
+    block, in the blocks' order; bit u clear: unit u cannot be met) and on (the masks are in use)."""
+    lib = load_library()
+    n = len(prims)
+    arr = (rt_prim * max(1, n))(*prims)
+    cam = rt_camera.from_buffer_copy(camera)
+    b = bands or (0, 0, 0)
+    W, H = size
+    rows = lib.rt_band_rows(H, b[0], b[1], b[2]) if bands else H
+    x0, y0, w, h = window or (0, 0, W, rows)
+    bx, by = (w + 7) // 8, (h + 7) // 8
+    dead = np.zeros(max(1, bx * by), np.uint8)
+    masks = np.zeros(max(1, bx * by), np.uint64)
+    cap_ids = 8 * max(1, n) + 64
+    first = np.zeros(65, np.int32)
+    ids = np.zeros(cap_ids, np.int32)
+    box = np.zeros((64, 2, 3), np.float32)
+    info = (C.c_int32 * 6)()
+    nu = lib.rt_debug_block_units(arr, n, C.byref(cam), W, H, x0, y0, w, h, b[0], b[1], b[2],
+                                  first.ctypes.data_as(C.POINTER(C.c_int32)), ids.ctypes.data_as(C.POINTER(C.c_int32)),
+                                  cap_ids, box.ctypes.data_as(C.POINTER(C.c_float)),
+                                  dead.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                  masks.ctypes.data_as(C.POINTER(C.c_uint64)), bx * by, info)
+    if nu < 0:
+        _check(nu)
+    live = int(info[2])
+    per_unit = [ids[first[u]:first[u + 1]].tolist() for u in range(nu)] if nu <= 64 and info[4] <= cap_ids else []
+    return {"n_units": int(nu), "ids": per_unit, "box": box[:nu] if nu <= 64 else box[:0],
+            "pad": float(np.array([info[5]], np.int32).view(np.float32)[0]),
+            "dead": dead[:bx * by].reshape(by, bx).astype(bool), "live": live, "masks": masks[:live].copy(),
+            "on": bool(info[3])}
 
 
 def start_rows(kernel: int, camera: rt_camera, w: int, h: int, spp: int, chunks: int = 0, grid_blocks: int = 1792,

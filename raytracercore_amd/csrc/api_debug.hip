@@ -534,6 +534,68 @@ int rt_debug_block_cull(const rt_prim* prims, int32_t n_prims, const rt_camera* 
     return live;
 }
 
+// Host only: the first bounce's test units and the unit masks run_path would add to the cull record of such a
+// launch (make_flat_units, unit_masks).
+int rt_debug_block_units(const rt_prim* prims, int32_t n_prims, const rt_camera* camera, int32_t width, int32_t height,
+                         int32_t x0, int32_t y0, int32_t w, int32_t h, int32_t band, int32_t band_stride,
+                         int32_t band_offset, int32_t* unit_first, int32_t* unit_ids, int64_t cap_ids, float* unit_box,
+                         uint8_t* dead, uint64_t* masks, int64_t cap_blocks, int32_t* info)
+{
+    const bool banded = band > 0;
+    if (n_prims < 0 || (n_prims > 0 && !prims) || !camera || width <= 0 || height <= 0 || w <= 0 || h <= 0 || x0 < 0 ||
+        y0 < 0 || x0 + w > width || cap_ids < 0 || (cap_ids > 0 && !unit_ids) || cap_blocks < 0 ||
+        (cap_blocks > 0 && (!dead || !masks)) || band < 0 ||
+        (camera->kind != RT_CAMERA_FRUSTUM && camera->kind != RT_CAMERA_ORTHO) ||
+        (banded && (band_stride <= 0 || band_offset < 0 || band_offset >= band_stride)) || (!banded && y0 + h > height)) {
+        set_error("rt_debug_block_units: bad argument");
+        return RT_ERR_ARG;
+    }
+    for (int i = 0; i < n_prims; i++)
+        if (prims[i].kind < 0 || prims[i].kind > 2) {
+            set_error("rt_debug_block_units: unknown primitive kind at index " + std::to_string(i));
+            return RT_ERR_ARG;
+        }
+    const std::vector<HostPrim> H = prepare_prims(prims, n_prims);
+    const HostRecords rec = report_records(H);
+    const SceneBound b = make_scene_bound(H);
+    const FlatUnits U = make_flat_units(H, rec.orders.flat, b, rec.n_planes, rec.n_vn);
+    CameraD camd;
+    CameraF camf;
+    camera_init(*camera, width, height, camd, camf);
+    const CullWindow win{x0, y0, w, h, banded ? band : 0, banded ? band_stride : 0, banded ? band_offset : 0};
+    std::vector<unsigned char> flags;
+    const int live = cull_blocks(camf, b, rec.n_planes, win, flags);
+    // run_path keeps a cull record, and with it the masks, only when some block is dead
+    std::vector<uint64_t> m((size_t)live, ~0ull);
+    const bool on = U.on && live > 0 && live < (int)flags.size() &&
+                    unit_masks(camf, b, U.n, U.lo.data(), U.hi.data(), win, flags, m);
+    int64_t n_ids = 0;
+    for (int u = 0; u < U.n; u++) {
+        if (unit_first && u < kMaxUnits) unit_first[u] = (int32_t)n_ids;
+        for (int id : U.ids[(size_t)u]) {
+            if (n_ids < cap_ids) unit_ids[n_ids] = id;
+            n_ids++;
+        }
+        if (unit_box && u < kMaxUnits)
+            for (int k = 0; k < 3; k++) {
+                unit_box[6 * u + k] = U.lo[(size_t)u * 3 + k];
+                unit_box[6 * u + 3 + k] = U.hi[(size_t)u * 3 + k];
+            }
+    }
+    if (unit_first && U.n <= kMaxUnits) unit_first[U.n] = (int32_t)n_ids;
+    for (size_t i = 0; i < flags.size() && (int64_t)i < cap_blocks; i++) dead[i] = flags[i];
+    for (size_t i = 0; i < m.size() && (int64_t)i < cap_blocks; i++) masks[i] = m[i];
+    if (info) {
+        info[0] = (w + 7) / 8;
+        info[1] = (h + 7) / 8;
+        info[2] = live;
+        info[3] = on ? 1 : 0;
+        info[4] = (int32_t)std::min<int64_t>(n_ids, INT32_MAX);
+        std::memcpy(&info[5], &b.pad, 4);
+    }
+    return U.n;
+}
+
 // Host only: the start rows run_path would plan for such a launch (make_params_for, plan_start_rows).
 int rt_debug_start_rows(int32_t kernel, const rt_camera* camera, int32_t w, int32_t h, int32_t spp, int32_t chunks,
                         int32_t grid_blocks, int32_t flags, int64_t* info)

@@ -185,7 +185,78 @@ bool project_bound(const CameraF& c, const SceneBound& b, int frame_w, Hull& hul
     return true;
 }
 
+// Block row by's runs of consecutive frame rows (one run without a band set, or when the band length
+// is a multiple of 8).
+int block_runs(const CullWindow& win, int by, int run_a[8], int run_b[8])
+{
+    int runs = 0;
+    for (int py = by * 8; py < std::min(win.h, by * 8 + 8); py++) {
+        int fy = win.y0 + py;
+        if (win.band > 0) fy = win.y0 + ((py / win.band) * win.band_stride + win.band_offset) * win.band + py % win.band;
+        if (runs > 0 && fy == run_b[runs - 1] + 1) run_b[runs - 1] = fy;
+        else {
+            run_a[runs] = run_b[runs] = fy;
+            runs++;
+        }
+    }
+    return runs;
+}
+
+// Is block (bx, by)'s sample rectangle, widened by kMargin, disjoint from the hull?
+bool block_misses(const Hull& hull, const CullWindow& win, int bx, int runs, const int run_a[8], const int run_b[8])
+{
+    const double xa = (double)(win.x0 + bx * 8) - kMargin;
+    const double xb = (double)(win.x0 + std::min(win.w, bx * 8 + 8)) + kMargin; // last pixel + 1
+    bool miss = true;
+    for (int r = 0; r < runs && miss; r++)
+        miss = separated(hull, xa, xb, (double)run_a[r] - kMargin, (double)(run_b[r] + 1) + kMargin);
+    return miss;
+}
+
 } // namespace
+
+// The unit masks (block_cull.h).  Each unit's box goes through the cull's own projection: grown by the
+// bound's pad once more, every corner ahead of the camera plane by kAhead, the fp32 error of the
+// kernel's ray below kMargin / 8 at the unit's own nearest corner.  What the cull's argument says of the
+// scene bound it then says of the unit: a camera ray of a block whose widened sample rectangle is
+// disjoint from that hull passes the unit's padded box, and the pad covers the fp32 tests of the
+// unit's primitives (make_flat_units), so each of them answers "miss" for it, run or not.
+bool unit_masks(const CameraF& cam, const SceneBound& bound, int n_units, const float* unit_lo, const float* unit_hi,
+                const CullWindow& win, const std::vector<unsigned char>& dead, std::vector<uint64_t>& masks)
+{
+    const int bxn = (win.w + 7) / 8, byn = (win.h + 7) / 8;
+    size_t n_live = 0;
+    for (unsigned char d : dead) n_live += d ? 0 : 1;
+    masks.assign(n_live, ~0ull);
+    Hull scene_hull;
+    if (n_units < 0 || n_units > 64 || bound.empty || !(bound.limit >= 0.0f) || dead.size() != (size_t)bxn * byn ||
+        !project_bound(cam, bound, (int)(2.0f * cam.w2), scene_hull))
+        return false;
+    std::vector<Hull> hulls((size_t)n_units);
+    uint64_t proven = 0; // units with a hull
+    for (int u = 0; u < n_units; u++) {
+        SceneBound ub = bound; // the scene's limit and pad
+        for (int k = 0; k < 3; k++) {
+            ub.lo[k] = unit_lo[3 * u + k];
+            ub.hi[k] = unit_hi[3 * u + k];
+        }
+        if (project_bound(cam, ub, (int)(2.0f * cam.w2), hulls[(size_t)u])) proven |= 1ull << u;
+    }
+    const uint64_t all = n_units == 64 ? ~0ull : (1ull << n_units) - 1ull;
+    size_t live = 0;
+    for (int by = 0; by < byn; by++) {
+        int run_a[8], run_b[8];
+        const int runs = block_runs(win, by, run_a, run_b);
+        for (int bx = 0; bx < bxn; bx++) {
+            if (dead[(size_t)by * bxn + bx]) continue;
+            uint64_t m = all;
+            for (int u = 0; u < n_units; u++)
+                if (((proven >> u) & 1ull) && block_misses(hulls[(size_t)u], win, bx, runs, run_a, run_b)) m &= ~(1ull << u);
+            masks[live++] = m;
+        }
+    }
+    return true;
+}
 
 int cull_blocks(const CameraF& cam, const SceneBound& bound, int n_planes, const CullWindow& win,
                 std::vector<unsigned char>& dead)
@@ -203,24 +274,10 @@ int cull_blocks(const CameraF& cam, const SceneBound& bound, int n_planes, const
     if (!project_bound(cam, bound, (int)(2.0f * cam.w2), hull)) return n;
     int live = 0;
     for (int by = 0; by < byn; by++) {
-        // the block's runs of consecutive frame rows (one run without a band set, or when the band
-        // length is a multiple of 8)
-        int run_a[8], run_b[8], runs = 0;
-        for (int py = by * 8; py < std::min(win.h, by * 8 + 8); py++) {
-            int fy = win.y0 + py;
-            if (win.band > 0) fy = win.y0 + ((py / win.band) * win.band_stride + win.band_offset) * win.band + py % win.band;
-            if (runs > 0 && fy == run_b[runs - 1] + 1) run_b[runs - 1] = fy;
-            else {
-                run_a[runs] = run_b[runs] = fy;
-                runs++;
-            }
-        }
+        int run_a[8], run_b[8];
+        const int runs = block_runs(win, by, run_a, run_b);
         for (int bx = 0; bx < bxn; bx++) {
-            const double xa = (double)(win.x0 + bx * 8) - kMargin;
-            const double xb = (double)(win.x0 + std::min(win.w, bx * 8 + 8)) + kMargin; // last pixel + 1
-            bool is_dead = true;
-            for (int r = 0; r < runs && is_dead; r++)
-                is_dead = separated(hull, xa, xb, (double)run_a[r] - kMargin, (double)(run_b[r] + 1) + kMargin);
+            const bool is_dead = block_misses(hull, win, bx, runs, run_a, run_b);
             dead[(size_t)by * bxn + bx] = is_dead ? 1 : 0;
             live += is_dead ? 0 : 1;
         }

@@ -23,6 +23,15 @@ struct CullWindow {
 int cull_blocks(const CameraF& cam, const SceneBound& bound, int n_planes, const CullWindow& win,
                 std::vector<unsigned char>& dead);
 
+// The first bounce's unit masks: masks[i], for live block i of `dead` in its order, has bit u clear
+// exactly when the block's sample rectangle is disjoint from the projected hull of unit u's box
+// (n_units boxes, 3 floats each in unit_lo / unit_hi, padded as the bound is: FlatUnits), by the cull's
+// own test and margins.  A unit whose box the proof does not serve (not wholly ahead of the camera
+// plane, or past the error bound) keeps its bit in every block.  false, and every mask all ones: the
+// cull itself has no proof for this camera.
+bool unit_masks(const CameraF& cam, const SceneBound& bound, int n_units, const float* unit_lo, const float* unit_hi,
+                const CullWindow& win, const std::vector<unsigned char>& dead, std::vector<uint64_t>& masks);
+
 // Real pixels (px < w, py < h) of the dead blocks.
 uint64_t dead_pixels(const CullWindow& win, const std::vector<unsigned char>& dead);
 

@@ -473,6 +473,89 @@ __device__ __forceinline__ void trace_brute(const SceneT& s, GroupP groups, Test
     }
 }
 
+// The flat order's query for a wave of camera rays of one 8x8 block (path_body, first bounce): trace_brute's
+// one group with each test unit (rt_kernels.h, flat_unit_count) behind a scalar test of its bit in the
+// block's mask.  The tests, their order and their operands are trace_brute's, so the units that run
+// leave b as they do there; the units left out cannot be met by these rays (unit_masks).
+#ifdef RT_SCENE_CONST
+#define RT_UNROLL_UNITS _Pragma("unroll")
+#else
+#define RT_UNROLL_UNITS
+#endif
+template <class GroupP, class TestP, class RectP, class FrameP, class BoxP, class XfP>
+__device__ __forceinline__ void trace_units(GroupP groups, TestP tests, RectP rects, FrameP frames, BoxP boxes, XfP xf,
+                                            V3 o, V3 d, int prev, Best& b, unsigned long long mask)
+{
+    const V3 id = v3(slab_rcp_lean(d.x), slab_rcp_lean(d.y), slab_rcp_lean(d.z));
+    const V3 oi = o * id;
+    const GroupRec G = groups[0];
+    auto on = [&]() { // the next unit's bit (wave-uniform): the units come in the mask's order
+        const bool t = (mask & 1ull) != 0ull;
+        mask >>= 1;
+        return t;
+    };
+    RectP r = rects + __float_as_int(G.lo.w);
+    RT_UNROLL_UNITS
+    for (int k = 0; k < G.n_rect[0]; k++)
+        if (on()) {
+            const RectRec r0 = r[k];
+            hit_rect<0>(r0, r0.sg, o, d, id, oi, prev, b);
+        }
+    r += G.n_rect[0];
+    RT_UNROLL_UNITS
+    for (int k = 0; k < G.n_rect[1]; k++)
+        if (on()) {
+            const RectRec r0 = r[k];
+            hit_rect<1>(r0, r0.sg, o, d, id, oi, prev, b);
+        }
+    r += G.n_rect[1];
+    RT_UNROLL_UNITS
+    for (int k = 0; k < G.n_rect[2]; k++)
+        if (on()) {
+            const RectRec r0 = r[k];
+            hit_rect<2>(r0, r0.sg, o, d, id, oi, prev, b);
+        }
+    RT_UNROLL_UNITS
+    for (int j = G.frame_first + G.n_frames; j < G.frame_first + G.n_frames + G.n_boxes; j++)
+        if (on()) {
+            const BoxRec B = boxes[j];
+            hit_box<false>(B, o, d, id, oi, prev, b);
+        }
+    RT_UNROLL_UNITS
+    for (int f = G.frame_first; f < G.frame_first + G.n_frames; f++)
+        if (on()) {
+            const FrameRec F = frames[f];
+            const V3 lo = v3(dot4(F.r0, o), dot4(F.r1, o), dot4(F.r2, o));
+            const V3 ld = v3(dot3(F.r0, d), dot3(F.r1, d), dot3(F.r2, d));
+            const V3 lid = v3(rcp(ld.x), rcp(ld.y), rcp(ld.z));
+            RectP fr = rects + F.rect_first;
+            rect_group<0, true>(fr, F.n_rect[0], lo, ld, lid, lo, prev, b);
+            fr += F.n_rect[0];
+            rect_group<1, true>(fr, F.n_rect[1], lo, ld, lid, lo, prev, b);
+            fr += F.n_rect[1];
+            rect_group<2, true>(fr, F.n_rect[2], lo, ld, lid, lo, prev, b);
+            if (F.box >= 0) {
+                const BoxRec B = boxes[F.box];
+                hit_box<true>(B, lo, ld, lid, lo, prev, b);
+            }
+        }
+    int i = __float_as_int(G.hi.w);
+    const int tri_end = i + (G.n_tri_sph & 0xFFFF);
+    RT_UNROLL_UNITS
+    for (; i < tri_end; i++)
+        if (on()) {
+            const TestRec cur = tests[i];
+            hit_tri<true>(cur, i, o, d, prev, b);
+        }
+    const int sph_end = i + (G.n_tri_sph >> 16);
+    RT_UNROLL_UNITS
+    for (; i < sph_end; i++)
+        if (on()) {
+            const TestRec cur = tests[i];
+            hit_sph<true, RT_SPH_WAVE_SKIP < 0 ? false : RT_SPH_WAVE_SKIP != 0>(cur, i, o, d, prev, xf, b);
+        }
+}
+
 template <bool SLOT = false, class XfP>
 __device__ __forceinline__ void hit_any(const TestRec& R, int slot, V3 o, V3 d, int prev, XfP xf, Best& b)
 {
@@ -1782,6 +1865,8 @@ __device__ __forceinline__ void path_body(const CameraF* __restrict__ camp, cons
     const ShadeRecs R = stage_scene<LDS>(P0.scene, P0.prims, P0.mats, P0.xf, lds_scene);
     const int lane = threadIdx.x & 63;
     const unsigned total = (unsigned)P0.n_chunks * (unsigned)P0.n_pad;
+    // the first bounce's code: the flat order's tile instances that run sample rounds
+    constexpr bool FIRST = !STATS && !VN && !CULL && SRC == ITEMS_TILE;
     Lane L;
     lane_init(L);
     Sample S;
@@ -1791,7 +1876,8 @@ __device__ __forceinline__ void path_body(const CameraF* __restrict__ camp, cons
     unsigned long long wave_rays = 0; // wave-uniform
     // the scene bound's switch, read once (one SGPR pair for the whole kernel): the lanes that keep a
     // wave from the bound test, every lane when the switch is off
-    const unsigned long long bound_off = P0.scene_bound != 0 ? 0ull : ~0ull;
+    // (bit 0 of the field; kFirstBounce and kFirstMasks are read where they are used)
+    const unsigned long long bound_off = (P0.scene_bound & 1) != 0 ? 0ull : ~0ull;
 
     while (true) {
         unsigned long long t0 = 0, t1 = 0, t2 = 0;
@@ -1850,9 +1936,37 @@ __device__ __forceinline__ void path_body(const CameraF* __restrict__ camp, cons
             // instrumented instances do not take it, so their counters keep their meaning: the
             // primitives a ray segment's query answers for.
             bool query = true;
-            if (!STATS && (!CULL || RT_BOUND_GROUPED) &&
-                __builtin_expect((__ballot(L.live && S.bounce != 0) | bound_off) == 0ull, 0))
-                query = __any(L.live && scene_meets(sc, S.o, S.d));
+            // First bounce (FIRST; every other instance has the guard as it was).  The predicate is the
+            // guard's: no live lane past bounce 0, asked of the lanes.  (A scalar count of the round's
+            // iterations answered the same in a rounds ticket and measured slower: DESIGN appendix A.)
+            if constexpr (FIRST) {
+                const bool camera_rays = __ballot(L.live && S.bounce != 0) == 0ull; // wave-uniform
+                if (__builtin_expect(camera_rays, 0)) {
+                    const int fb = pq->scene_bound; // (read here, once per round, not held across the loop)
+                    if (fb & 1) query = __any(L.live && scene_meets(sc, S.o, S.d));
+                    // The block's unit mask (block_cull.h, unit_masks): the camera rays of one 8x8 block can
+                    // meet only the units whose bit is set, so the query runs those alone; a wave whose
+                    // live lanes are of several blocks runs them all.  A unit left out leaves b as it was,
+                    // which is what its test would have done.  The other iterations' query has no part in this.
+                    if (query && (fb & kFirstMasks)) {
+                        const unsigned sh = 6u + (unsigned)pq->log2_chunks;
+                        const unsigned blk = (unsigned)__builtin_amdgcn_readfirstlane((int)L.item) >> sh;
+                        unsigned long long mask = ~0ull;
+                        if (__ballot(L.live && (L.item >> sh) != blk) == 0ull) {
+                            const unsigned n_live = (unsigned)pq->n_pad >> 6;
+                            const auto cw = (const RT_AS_CONST unsigned int*)pq->cull;
+                            const unsigned at = cull_masks_at(n_live, cw[3]) + 2u * blk;
+                            mask = (unsigned long long)cw[at] | (unsigned long long)cw[at + 1] << 32;
+                        }
+                        trace_units(groups, tests, rects, frames, boxes, xf, S.o, S.d, S.prev, b, mask);
+                        query = false;
+                    }
+                }
+            } else {
+                if (!STATS && (!CULL || RT_BOUND_GROUPED) &&
+                    __builtin_expect((__ballot(L.live && S.bounce != 0) | bound_off) == 0ull, 0))
+                    query = __any(L.live && scene_meets(sc, S.o, S.d));
+            }
             if (query)
                 trace_brute<CULL, STATS>(sc, groups, tests, rects, frames, boxes, xf, S.o, S.d, S.prev, b, cnt.tris,
                                          cnt.sphs, cnt.nodes);

@@ -165,6 +165,12 @@ PathParams make_params_for(int kernel, int chunks_over, int pool_over, int x0, i
     // Kernel ms, one call, three rounds: C2 16.01-16.05 -> 14.97-15.00.
     p.scene_bound = 1;
     if (const char* e = getenv("RTCORE_SCENE_BOUND")) p.scene_bound = atoi(e) != 0 ? 1 : 0;
+    // First bounce (rt_kernels.h, kFirstBounce / kFirstMasks; path_body): a wave of camera rays of one 8x8
+    // block runs its query over the units the block can see.  The result is the same either way;
+    // RTCORE_FIRST_BOUNCE=0 turns it off (run_path then sets no kFirstMasks), read per launch.
+    bool first_bounce = true;
+    if (const char* e = getenv("RTCORE_FIRST_BOUNCE")) first_bounce = atoi(e) != 0;
+    if (first_bounce) p.scene_bound |= kFirstBounce;
     // Brute-force tile kernels: sample rounds (refill; ticket_rounds in rt_kernels.h has the rule).  The
     // result is the same either way: only when a lane starts its next sample changes.
     // RTCORE_SAMPLE_ROUNDS=0 turns them off, 2 runs every ticket in rounds, 1 (the default) lets each

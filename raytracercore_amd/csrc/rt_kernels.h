@@ -148,6 +148,26 @@ static_assert(__builtin_offsetof(PathParams, sample_rounds) == __builtin_offseto
                   __builtin_offsetof(PathParams, cull) == __builtin_offsetof(PathParams, scene_bound) + 8,
               "sample_rounds takes the padding after scene_bound");
 constexpr int kCullTable = 4;  // first table word of PathParams::cull
+
+// First bounce (path_body, the flat brute-force tile instances that run sample rounds; RTCORE_FIRST_BOUNCE,
+// make_params_for).  Two more bits of PathParams::scene_bound, whose bit 0 is the scene bound's switch:
+//   kFirstBounce  the switch: the launch may use unit masks
+//   kFirstMasks   it has them: its cull record ends with one 64-bit unit mask per live block (run_path)
+// The flat order's test units, in the order trace_brute runs its one group: each world rectangle (x | y |
+// z), each world box, each frame (its rectangles and its box together), each triangle record, each
+// sphere record.  Bit u of a block's mask is clear when no camera ray of the block can meet unit u
+// (unit_masks, block_cull.h); the masks follow the cull record's two tables, on an 8-byte boundary.
+constexpr int kFirstBounce = 2, kFirstMasks = 4;
+constexpr int kMaxUnits = 64;
+template <class GroupT>
+__host__ __device__ inline int flat_unit_count(const GroupT& G)
+{
+    return G.n_rect[0] + G.n_rect[1] + G.n_rect[2] + G.n_boxes + G.n_frames + (G.n_tri_sph & 0xFFFF) + (G.n_tri_sph >> 16);
+}
+__host__ __device__ inline unsigned cull_masks_at(unsigned n_live, unsigned n_blocks) // first mask word
+{
+    return ((unsigned)kCullTable + n_live + n_blocks + 1u) & ~1u;
+}
 constexpr int kRecRows = 6;    // sizeof(rt_debug_ray) / 16
 
 // Ticket t of item range g -> the items it covers, [first, first + len) in the item numbering

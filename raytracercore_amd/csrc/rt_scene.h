@@ -244,6 +244,7 @@ struct rt_scene {
         unsigned cam_gen = 0;
         CullWindow win{};
         int n_live = 0, n_blocks = 0;
+        bool masks = false; // the record ends with the live blocks' unit masks (cull_masks_at, rt_kernels.h)
         uint64_t dead_px = 0, used = 0;
         DevBuf<unsigned int> dev;
         HostBuf<unsigned int> host;
@@ -252,6 +253,7 @@ struct rt_scene {
     static constexpr int kCullEntries = 4;
     std::array<CullEntry, kCullEntries> cull_cache;
     uint64_t cull_clock = 0;
+    FlatUnits units;            // the flat order's test units and their boxes (scene_records.h), with the bound
     unsigned cam_gen = 0;
     bool has_camera = false;
     bool flat_overflow = false; // the flat brute-force order exceeds GroupRec's counts (BruteOrder::overflow)

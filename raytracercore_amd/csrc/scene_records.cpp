@@ -2,6 +2,8 @@
 // fills the PODs of rt_internal.h, and links into the host-only checks as well as the library.
 #include "scene_records.h"
 
+#include "rt_kernels.h"
+
 #include <algorithm>
 #include <array>
 #include <cmath>
@@ -954,38 +956,68 @@ uint32_t scene_facts(const std::vector<HostPrim>& H)
 // counts as meeting the box, as does a ray with a NaN or an infinity in it.
 // No bounded primitive: an empty bound, which no ray meets.  A NaN or infinite extent: limit = -1,
 // so every origin is past it and the skip is off for the scene.
+// One primitive's extent on the three axes (fp64), as the bounds take it; false for a plane.
+static bool prim_extent(const HostPrim& p, double lo[3], double hi[3])
+{
+    for (int k = 0; k < 3; k++) {
+        lo[k] = INFINITY;
+        hi[k] = -INFINITY;
+    }
+    if (p.kind == RT_PRIM_TRIANGLE) {
+        const Vec4d v3 = add(add(p.v[0], p.e01), p.e02); // a parallelogram's fourth vertex
+        const int nv = (p.flags & F_MIRROR) ? 4 : 3;
+        bool bad = false; // (min and max drop a NaN)
+        for (int j = 0; j < nv; j++) {
+            const Vec4d& v = j < 3 ? p.v[j] : v3;
+            const double c[3] = {v.x, v.y, v.z};
+            for (int k = 0; k < 3; k++) {
+                bad |= !std::isfinite(c[k]);
+                lo[k] = std::min(lo[k], c[k]);
+                hi[k] = std::max(hi[k], c[k]);
+            }
+        }
+        if (bad) lo[0] = hi[0] = NAN;
+        return true;
+    }
+    if (p.kind == RT_PRIM_SPHERE) {
+        const double c[3] = {p.center.x, p.center.y, p.center.z};
+        for (int k = 0; k < 3; k++) {
+            double mid = c[k], half = std::fabs(p.radius);
+            if (p.flags & F_TRANSFORMED) {
+                const double* m = p.to_obj + 4 * k;
+                mid = m[0] * c[0] + m[1] * c[1] + m[2] * c[2] + m[3];
+                half = std::fabs(p.radius) * std::sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]);
+            }
+            // (the fp64 rounding of mid and half is 2^-52 relative: far inside the pad)
+            lo[k] = mid - half;
+            hi[k] = mid + half;
+        }
+        return true;
+    }
+    return false;
+}
+// [a - pad, c + pad] in fp32, rounded outward
+static void pad_outward(double a, double c, double pad, float& lo, float& hi)
+{
+    a -= pad;
+    c += pad;
+    lo = (float)a;
+    if ((double)lo > a) lo = std::nextafterf(lo, -INFINITY);
+    hi = (float)c;
+    if ((double)hi < c) hi = std::nextafterf(hi, INFINITY);
+}
+
 SceneBound make_scene_bound(const std::vector<HostPrim>& H)
 {
     double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     bool any = false, bad = false;
-    auto grow = [&](int k, double a, double b) {
-        if (!(std::isfinite(a) && std::isfinite(b))) bad = true;
-        lo[k] = std::min(lo[k], a);
-        hi[k] = std::max(hi[k], b);
-    };
     for (const HostPrim& p : H) {
-        if (p.kind == RT_PRIM_TRIANGLE) {
-            const Vec4d v3 = add(add(p.v[0], p.e01), p.e02); // a parallelogram's fourth vertex
-            const int nv = (p.flags & F_MIRROR) ? 4 : 3;
-            for (int j = 0; j < nv; j++) {
-                const Vec4d& v = j < 3 ? p.v[j] : v3;
-                const double c[3] = {v.x, v.y, v.z};
-                for (int k = 0; k < 3; k++) grow(k, c[k], c[k]);
-            }
-        } else if (p.kind == RT_PRIM_SPHERE) {
-            const double c[3] = {p.center.x, p.center.y, p.center.z};
-            for (int k = 0; k < 3; k++) {
-                double mid = c[k], half = std::fabs(p.radius);
-                if (p.flags & F_TRANSFORMED) {
-                    const double* m = p.to_obj + 4 * k;
-                    mid = m[0] * c[0] + m[1] * c[1] + m[2] * c[2] + m[3];
-                    half = std::fabs(p.radius) * std::sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]);
-                }
-                // (the fp64 rounding of mid and half is 2^-52 relative: far inside the pad)
-                grow(k, mid - half, mid + half);
-            }
-        } else {
-            continue;
+        double a[3], c[3];
+        if (!prim_extent(p, a, c)) continue;
+        for (int k = 0; k < 3; k++) {
+            if (!(std::isfinite(a[k]) && std::isfinite(c[k]))) bad = true;
+            lo[k] = std::min(lo[k], a[k]);
+            hi[k] = std::max(hi[k], c[k]);
         }
         any = true;
     }
@@ -1002,17 +1034,77 @@ SceneBound make_scene_bound(const std::vector<HostPrim>& H)
         b.limit = -1.0f; // the skip is off
         return b;
     }
-    for (int k = 0; k < 3; k++) {
-        const double a = lo[k] - pad, c = hi[k] + pad;
-        b.lo[k] = (float)a;
-        if ((double)b.lo[k] > a) b.lo[k] = std::nextafterf(b.lo[k], -INFINITY);
-        b.hi[k] = (float)c;
-        if ((double)b.hi[k] < c) b.hi[k] = std::nextafterf(b.hi[k], INFINITY);
-    }
+    for (int k = 0; k < 3; k++) pad_outward(lo[k], hi[k], pad, b.lo[k], b.hi[k]);
     b.limit = (float)limit;
     if ((double)b.limit > limit) b.limit = std::nextafterf(b.limit, 0.0f); // never above what the pad covers
     b.pad = (float)pad;
     return b;
+}
+
+// The flat order's test units and their boxes (scene_records.h).  A unit's slots name its primitives
+// (PrimF::a.w; a box's missing face has the slot of one of its other faces), and its box is the scene
+// bound's construction over those primitives alone: the same extents, the same pad, so the argument
+// that a ray past the padded box fails the fp32 tests of what is inside it holds unit by unit, for the
+// origins the scene bound serves (its limit).
+FlatUnits make_flat_units(const std::vector<HostPrim>& H, const BruteOrder& flat, const SceneBound& bound, int n_planes,
+                          int n_vn)
+{
+    FlatUnits U;
+    if (flat.groups.empty() || flat.overflow) return U;
+    const GroupRec& G = flat.groups[0];
+    auto slot_id = [&](int slot) {
+        int id;
+        std::memcpy(&id, &flat.prims[(size_t)slot].a.w, 4);
+        return id;
+    };
+    auto box_ids = [&](const FrameRec& R, std::vector<int>& out) {
+        BoxRec B;
+        std::memcpy(&B, &R, sizeof B);
+        for (int f = 0; f < 6; f++) out.push_back(slot_id((B.sg0 >> 1) + f));
+    };
+    int rect_first, tri_slot;
+    std::memcpy(&rect_first, &G.lo.w, 4);
+    std::memcpy(&tri_slot, &G.hi.w, 4);
+    const int n_rects = G.n_rect[0] + G.n_rect[1] + G.n_rect[2];
+    for (int k = 0; k < n_rects; k++) U.ids.push_back({slot_id(flat.rects[(size_t)(rect_first + k)].sg >> 1)});
+    for (int j = 0; j < G.n_boxes; j++) {
+        U.ids.emplace_back();
+        box_ids(flat.frames[(size_t)(G.frame_first + G.n_frames + j)], U.ids.back());
+    }
+    for (int f = 0; f < G.n_frames; f++) {
+        const FrameRec& F = flat.frames[(size_t)(G.frame_first + f)];
+        U.ids.emplace_back();
+        for (int k = 0; k < F.n_rect[0] + F.n_rect[1] + F.n_rect[2]; k++)
+            U.ids.back().push_back(slot_id(flat.rects[(size_t)(F.rect_first + k)].sg >> 1));
+        if (F.box >= 0) box_ids(flat.frames[(size_t)F.box], U.ids.back());
+    }
+    const int n_ts = (G.n_tri_sph & 0xFFFF) + (G.n_tri_sph >> 16);
+    for (int i = 0; i < n_ts; i++) U.ids.push_back({slot_id(tri_slot + i)});
+    U.n = (int)U.ids.size();
+    bool ok = U.n == flat_unit_count(G) && U.n <= kMaxUnits && n_planes == 0 && n_vn == 0 && !bound.empty &&
+              bound.limit >= 0.0f;
+    U.lo.assign((size_t)U.n * 3, -INFINITY);
+    U.hi.assign((size_t)U.n * 3, INFINITY);
+    for (int u = 0; u < U.n && ok; u++) {
+        double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (int id : U.ids[(size_t)u]) {
+            double a[3], c[3];
+            if (id < 0 || id >= (int)H.size() || !prim_extent(H[(size_t)id], a, c)) {
+                ok = false;
+                break;
+            }
+            for (int k = 0; k < 3; k++) {
+                lo[k] = std::min(lo[k], a[k]);
+                hi[k] = std::max(hi[k], c[k]);
+            }
+        }
+        for (int k = 0; k < 3 && ok; k++) {
+            if (!(std::isfinite(lo[k]) && std::isfinite(hi[k]))) ok = false;
+            else pad_outward(lo[k], hi[k], (double)bound.pad, U.lo[(size_t)u * 3 + k], U.hi[(size_t)u * 3 + k]);
+        }
+    }
+    U.on = ok;
+    return U;
 }
 
 // Which axis-aligned rectangles become outer records.  Only large ones pay: a wall whose box

@@ -86,6 +86,20 @@ XformF make_xformf(const HostPrim& p);
 uint32_t scene_facts(const std::vector<HostPrim>& H); // FACT_*
 // The padded box over every primitive but the planes, and the origin limit its pad covers.
 SceneBound make_scene_bound(const std::vector<HostPrim>& H);
+// The flat order's test units (rt_kernels.h, flat_unit_count: world rectangles, world boxes, frames,
+// triangle records, sphere records, as trace_brute runs them) and one box per unit over the primitives
+// it stands for, built as the scene bound is and padded with the scene bound's own pad, fp32, rounded
+// outward.  ids: the primitive IDs of a unit's slots.  on = false (n and ids still filled where the
+// order has them): the scene has planes, vertex-normal triangles, more than kMaxUnits units, an order
+// past GroupRec's counts, or no finite bound.
+struct FlatUnits {
+    bool on = false;
+    int n = 0;
+    std::vector<std::vector<int>> ids;
+    std::vector<float> lo, hi; // 3 per unit
+};
+FlatUnits make_flat_units(const std::vector<HostPrim>& H, const BruteOrder& flat, const SceneBound& bound, int n_planes,
+                          int n_vn);
 // Which axis-aligned rectangles become outer records (out: per primitive, or empty for none).
 void select_outer(const std::vector<HostPrim>& H, std::vector<char>& out);
 

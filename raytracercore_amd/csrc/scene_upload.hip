@@ -373,6 +373,7 @@ int upload_scene(rt_scene* s)
     d.ambient = make_float3((float)a.r, (float)a.g, (float)a.b);
     d.ambient_miss = (a.r == -1 && a.g == -1 && a.b == -1) ? 1 : 0; // AmbientRGB == Placeholder
     d.bound = make_scene_bound(H);
+    s->units = make_flat_units(H, orders.flat, d.bound, np, rec.n_vn);
     return RT_OK;
 }
 
@@ -658,8 +659,16 @@ static int plan_block_cull(rt_scene* s, const PathParams& p, rt_scene::CullEntry
         c->dead_px = dead_pixels(win, dead);
         c->cam_gen = s->cam_gen;
         c->win = win;
+        c->masks = false;
         if (c->n_live < n_blocks) {
-            const size_t words = (size_t)kCullTable + (size_t)c->n_live + (size_t)n_blocks;
+            // the first bounce's unit masks (unit_masks, block_cull.h) after the two tables: they depend
+            // on what the record depends on, and are cached with it
+            std::vector<uint64_t> masks;
+            c->masks = s->units.on && c->n_live > 0 &&
+                       unit_masks(s->camf, s->dev.bound, s->units.n, s->units.lo.data(), s->units.hi.data(), win, dead, masks);
+            const size_t masks_at = cull_masks_at((unsigned)c->n_live, (unsigned)n_blocks);
+            const size_t words = c->masks ? masks_at + 2 * (size_t)c->n_live
+                                          : (size_t)kCullTable + (size_t)c->n_live + (size_t)n_blocks;
             HIP_TRY(c->host.reserve(words));
             HIP_TRY(c->dev.reserve(words));
             unsigned int* h = c->host.p;
@@ -672,6 +681,14 @@ static int plan_block_cull(rt_scene* s, const PathParams& p, rt_scene::CullEntry
                 if (!dead[(size_t)b]) h[kCullTable + live] = (unsigned)(b % p.blocks_x) | (unsigned)(b / p.blocks_x) << 16;
                 h[kCullTable + c->n_live + b] = dead[(size_t)b] ? 0xFFFFFFFFu : live;
                 live += dead[(size_t)b] ? 0u : 1u;
+            }
+            if (c->masks) {
+                // (the word that aligns them, when there is one: otherwise that is the table's last entry)
+                if (masks_at > (size_t)kCullTable + (size_t)c->n_live + (size_t)n_blocks) h[masks_at - 1] = 0;
+                for (size_t i = 0; i < (size_t)c->n_live; i++) {
+                    h[masks_at + 2 * i] = (unsigned)(masks[i] & 0xFFFFFFFFull);
+                    h[masks_at + 2 * i + 1] = (unsigned)(masks[i] >> 32);
+                }
             }
             fresh = true; // valid once the upload is queued (run_path)
         } else {
@@ -701,6 +718,7 @@ int run_path(rt_scene* s, PathParams& p, unsigned long long* d_rays, hipStream_t
     if (cull) {
         set_blocks(p, cull->n_live);
         p.cull = cull->dev.p;
+        if ((p.scene_bound & kFirstBounce) && cull->masks) p.scene_bound |= kFirstMasks;
     }
     const size_t need = (size_t)p.n_chunks * (size_t)p.n_pad;
     // 32-bit item indices: the end-of-work sentinel is `need` itself and a pool's end is at most
@@ -727,7 +745,8 @@ int run_path(rt_scene* s, PathParams& p, unsigned long long* d_rays, hipStream_t
     // order after the previous operation when it ran on another stream (shared scratch)
     if (s->any_op && stream != s->last_stream) HIP_TRY(hipStreamWaitEvent(stream, s->done_ev, 0));
     if (cull && cull_fresh) { // a new record: after the operations that read the entry's previous one
-        const size_t words = (size_t)kCullTable + (size_t)cull->n_live + (size_t)cull->n_blocks;
+        const size_t words = cull->masks ? cull_masks_at((unsigned)cull->n_live, (unsigned)cull->n_blocks) + 2 * (size_t)cull->n_live
+                                         : (size_t)kCullTable + (size_t)cull->n_live + (size_t)cull->n_blocks;
         HIP_TRY(hipMemcpyAsync(cull->dev.p, cull->host.p, words * sizeof(unsigned int), hipMemcpyHostToDevice, stream));
         HIP_TRY(hipEventRecord(cull->up, stream));
         cull->valid = true;
