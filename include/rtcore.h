@@ -51,7 +51,9 @@ extern "C" {
                                    rt_adaptive_select_device and rt_debug_adaptive_select, and
                                    rt_primary_hits_device, rt_denoise_device and rt_debug_denoise, and
                                    rt_reproject_device and rt_debug_reproject, and rt_beam, rt_render_beams,
-                                   rt_render_beams_device, rt_debug_beam_rays and rt_camera_beams */
+                                   rt_render_beams_device, rt_debug_beam_rays and rt_camera_beams, and
+                                   rt_surfel, rt_gather_mode, rt_render_surfels, rt_render_surfels_device and
+                                   rt_debug_surfel_rays_device */
 
 typedef enum rt_status {
     RT_OK = 0,
@@ -729,6 +731,78 @@ int rt_debug_beam_rays(const rt_beam* beams, int64_t n, int32_t spp, uint64_t se
    RT_ERR_ARG as rt_camera_rays. */
 int rt_camera_beams(const rt_camera* camera, int32_t width, int32_t height, int32_t x0, int32_t y0, int32_t w,
                     int32_t h, rt_beam* out);
+
+/*
+ * Surfels: the radiance arriving at a surface point, for a lightmap texel, a vertex bake or a light
+ * probe.  That is the mean of GetColor over a distribution of directions about a normal; with
+ * rt_render_rays the host draws those directions itself and brings one rt_ray per sample.  A surfel is a
+ * position and a normal, and every sample draws its own direction on the device from the two draws
+ * GetCameraRay spends on subX and subY, which rt_render_rays discards, by the functions the kernels'
+ * diffuse bounce runs: one 64-byte record per point instead of one per sample.
+ */
+/* 64 B, four 16-byte rows.  w components are ignored but must be finite.  The normal need NOT be unit. */
+typedef struct rt_surfel {
+    rt_vec4d position, normal;
+} rt_surfel;
+typedef enum rt_gather_mode {
+    RT_GATHER_DIFFUSE = 0, /* the reference's diffuse bounce: z = 2 acos(U1) / pi  (Raytracer.cs:215) */
+    RT_GATHER_COSINE = 1,  /* Lambert: z = sqrt(1 - U1); the mean is irradiance / pi                  */
+    RT_GATHER_SPHERE = 2   /* uniform over the sphere: z = 1 - 2 U1 (a probe; the normal only fixes the frame) */
+} rt_gather_mode;
+/*
+ * Sample k of surfel i (normative; F = round to nearest fp32; fp32 throughout, every operation rounded on
+ * its own, and a fused multiply-add only where the kernels' bounce has one):
+ *   rng = rt_rng_init(seed, stream_base + i, sample_base + k); U1 = the first draw * 2^-24, U2 = the second
+ *   draw * 2^-24, both exact in fp32: the draws rt_render_rays discards.  The bounce draws follow from the
+ *   third draw on, as for a ray.
+ *   o = F(position), component by component.
+ *   n^ = F(normal) / sqrt(n2), n2 = (x * x + y * y) + z * z of F(normal), IEEE square root and IEEE division.
+ *   z by mode (above); 2 acos(U1) / pi by the kernels' polynomial, the square roots by the hardware's.
+ *   s = sqrt(max(0, 1 - z^2)), 1 - z^2 as one fused multiply-add.
+ *   d = n^ z + s (c cos 2 pi U2 + (n^ x c) sin 2 pi U2), c = normalize(n^.y, -n^.x, 0), or (1, 0, 0) when
+ *   both components are 0: Vec4D.CreateHorizon in the Rodrigues form of the kernels' diffuse bounce, with
+ *   the hardware's sine and cosine (their argument in turns: U2 itself) and reciprocal square root.
+ *   Then one Newton step of the normalisation, d (1.5 - 0.5 |d|^2), as a renormalised bounce gets: the ray
+ *   meets rt_ray's "already normalised" contract.
+ *   The path is traced from (o, d) as bounce 0 with tint 1 and no skip primitive: a caller that leaves a
+ *   surface offsets the position itself, as for rt_occluded_rays.
+ * A surfel is invalid if one of its 8 doubles is not finite, or one of the 6 used ones is not after F, or
+ * n2 is zero or not finite: all spp samples are then primary misses and no ray is counted (rt_render_rays'
+ * rule for a bad ray).
+ * Two promises:
+ *  (a) rt_debug_surfel_rays_device reports the fp32 ray of every sample, and sample k of surfel i is, bit
+ *      for bit, what rt_render_rays returns at spp = 1, sample_base + k and stream_base + i for that ray.
+ *  (b) that ray is the fp64 evaluation of the formulas above to within the bounds the kernels' bounce
+ *      directions are held to (3e-5 per direction component, 5e-7 in length; origin exact).
+ *
+ * A gather sample that meets nothing is a PRIMARY miss: it is counted in misses and not added to sum.  The
+ * reference returns the untinted AmbientRGB for a bounce that misses (Raytracer.cs:90), so the gathered
+ * mean is (sum + misses * ambient) / (samples + misses).
+ * A gather path has Recursion + 1 segments, one more than the continuation of a rendered diffuse bounce.
+ *
+ * Everything else is rt_render_rays' contract with "ray" replaced by "surfel": the accumulation into sum,
+ * samples, misses and the ray count; the independence of n, list position, chunking and wave (the
+ * samples per work item are a function of spp alone); the coherence note; the bound on n of the device
+ * entry; always the generic kernels; RT_ERR_STATE on a BVH2 scene; the argument errors, plus RT_ERR_ARG
+ * for an unknown mode (checked first), and n == 0 returning RT_OK and touching nothing; the counters of
+ * rt_scene_get_stats, an armed rt_debug_ray_log, rt_kernel_times and the scene-specialised kernels left
+ * as they were; no camera needed.  rt_render_surfels works in rt_render_rays' chunks (2^19 surfels,
+ * RTCORE_QUERY_CHUNK) in rt_render_rays' buffers: a surfel has an rt_ray's size.
+ * Not part of a surfel: a footprint (list several surfels per texel) and a primitive to skip.
+ */
+int rt_render_surfels(rt_scene* scene, int32_t mode, const rt_surfel* surfels, int64_t n, int32_t spp, uint64_t seed,
+                      uint64_t sample_base, uint64_t stream_base, rt_color* sum_rgb, uint32_t* samples,
+                      uint32_t* misses, uint64_t* rays_out);
+int rt_render_surfels_device(rt_scene* scene, int32_t mode, const rt_surfel* d_surfels, int64_t n, int32_t spp,
+                             uint64_t seed, uint64_t sample_base, uint64_t stream_base, double* d_sum,
+                             uint32_t* d_samples, uint32_t* d_misses, unsigned long long* d_rays_count, void* stream);
+/* The sample rays, by a second compilation of the kernels' function.  No scene: it runs on the calling
+   thread's current device, as rt_tonemap_device does, asynchronous on `stream`.  d_rays_out[i * spp + k] =
+   the fp32 ray of sample k of surfel i, widened (origin.w = 1, direction.w = 0); an invalid surfel gets all
+   zeros (a miss by rt_render_rays' rule).  Returns RT_OK / RT_ERR_ARG (an unknown mode, a null pointer with
+   n > 0, n < 0, spp <= 0) / RT_ERR_HIP. */
+int rt_debug_surfel_rays_device(int32_t mode, const rt_surfel* d_surfels, int64_t n, int32_t spp, uint64_t seed,
+                                uint64_t sample_base, uint64_t stream_base, rt_ray* d_rays_out, void* stream);
 
 /* ----------------------------------------------------------- adaptive sampling --- */
 /*

@@ -36,6 +36,8 @@ RT_BVH_BUILDER_AUTO, RT_BVH_BUILDER_HOST, RT_BVH_BUILDER_GPU = 0, 1, 2
 BOUNCE_TYPE_NAMES = ("Skipped", "Diffuse", "Specular", "SpecularFail", "Transmitted", "Emission", "PureBlack",
                      "RecursionComplete", "Missed", "Debug")
 RT_TRACE_MAX_RECORDS = 1 << 20  # records of one rt_trace_paths call
+# rt_gather_mode (rt_render_surfels): the reference's diffuse bounce, Lambert's cosine, the uniform sphere
+RT_GATHER_DIFFUSE, RT_GATHER_COSINE, RT_GATHER_SPHERE = 0, 1, 2
 
 
 class rt_query_mode(enum.IntEnum):
@@ -145,6 +147,11 @@ class rt_beam(C.Structure):
                 ("direction_du", rt_vec4d), ("direction_dv", rt_vec4d)]
 
 
+class rt_surfel(C.Structure):
+    """A surface point and its normal (rt_render_surfels): 64 B, four 16-byte rows."""
+    _fields_ = [("position", rt_vec4d), ("normal", rt_vec4d)]
+
+
 class rt_hit(C.Structure):
     """One answer of rt_query_rays (Hit.cs): 48 B, offsets in include/rtcore.h."""
     _fields_ = [
@@ -231,6 +238,7 @@ SELECTION_DTYPE = np.dtype([("item", np.int32), ("reserved", np.int32), ("distan
 RAY_DTYPE = np.dtype([("origin", np.float64, (4,)), ("direction", np.float64, (4,))])
 BEAM_DTYPE = np.dtype([(f, np.float64, (4,)) for f in
                        ("origin", "direction", "origin_du", "origin_dv", "direction_du", "direction_dv")])
+SURFEL_DTYPE = np.dtype([("position", np.float64, (4,)), ("normal", np.float64, (4,))])
 HIT_DTYPE = np.dtype([
     ("prim_id", np.int32), ("inside", np.int32), ("distance", np.float64),
     ("position", np.float32, (3,)), ("normal", np.float32, (3,)), ("reserved", np.int32, (2,)),
@@ -242,7 +250,8 @@ _OPTIONAL = ("rt_query_rays", "rt_query_rays_device", "rt_camera_rays", "rt_sele
              "rt_select_rays", "rt_select_rays_device", "rt_render_rays", "rt_render_rays_device",
              "rt_occluded_rays", "rt_occluded_rays_device", "rt_render_pixels", "rt_render_pixels_device",
              "rt_adaptive_select_device", "rt_primary_hits_device", "rt_denoise_device", "rt_reproject_device",
-             "rt_render_beams", "rt_render_beams_device", "rt_camera_beams")
+             "rt_render_beams", "rt_render_beams_device", "rt_camera_beams",
+             "rt_render_surfels", "rt_render_surfels_device")
 
 _lib: Optional[C.CDLL] = None
 
@@ -359,6 +368,12 @@ def load_library(path: str = "") -> C.CDLL:
         "rt_debug_beam_rays": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64,
                                          C.c_void_p, C.c_void_p]),
         "rt_camera_beams": (C.c_int, [P(rt_camera)] + [C.c_int32] * 6 + [C.c_void_p]),
+        "rt_render_surfels": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64,
+                                        C.c_uint64, P(rt_color), P(C.c_uint32), P(C.c_uint32), P(C.c_uint64)]),
+        "rt_render_surfels_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_uint64,
+                                               C.c_uint64, C.c_uint64] + [C.c_void_p] * 4 + [C.c_void_p]),
+        "rt_debug_surfel_rays_device": (C.c_int, [C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64,
+                                                  C.c_uint64, C.c_void_p, C.c_void_p]),
         "rt_occluded_rays": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
         "rt_occluded_rays_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                               C.c_void_p]),
@@ -690,6 +705,59 @@ def camera_beams(camera: rt_camera, size: Tuple[int, int], x0: int = 0, y0: int 
     cam = rt_camera.from_buffer_copy(camera)
     _check(lib.rt_camera_beams(C.byref(cam), W, H, x0, y0, w, h, out.ctypes.data_as(C.c_void_p)))
     return out
+
+
+def _pack_surfels(positions, normals) -> np.ndarray:
+    """(n, 3) or (n, 4) positions and normals -> a contiguous SURFEL_DTYPE array (position w = 1, normal
+    w = 0); or one SURFEL_DTYPE array with normals None."""
+    if normals is None:
+        return np.ascontiguousarray(positions, SURFEL_DTYPE).reshape(-1)
+    p, nrm = np.asarray(positions, np.float64), np.asarray(normals, np.float64)
+    if p.ndim != 2 or p.shape != nrm.shape or p.shape[1] not in (3, 4):
+        raise ValueError("positions and normals must be (n, 3) or (n, 4) arrays of the same shape")
+    surfels = np.zeros(p.shape[0], SURFEL_DTYPE)
+    surfels["position"][:, 3] = 1.0
+    surfels["position"][:, :p.shape[1]] = p
+    surfels["normal"][:, :p.shape[1]] = nrm
+    return surfels
+
+
+def gather_mean(sum_rgb, samples, misses, ambient) -> np.ndarray:
+    """The gathered mean of render_surfels' accumulators, (sum + misses * ambient) / (samples + misses) per
+    surfel: a gather sample that meets nothing is a primary miss, for which the reference returns the
+    untinted ambient colour (Raytracer.cs:90).  ambient: three floats or an rt_color.  NaN where a surfel
+    has no sample at all."""
+    amb = np.array([ambient.r, ambient.g, ambient.b] if isinstance(ambient, rt_color) else ambient, np.float64).reshape(3)
+    s = np.asarray(sum_rgb, np.float64)
+    ns, ms = np.asarray(samples, np.float64), np.asarray(misses, np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return (s + ms[..., None] * amb) / (ns + ms)[..., None]
+
+
+def prim_surfels(prim: rt_prim, width: int, height: int, offset: float, flip: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+    """The texel centres of a triangle primitive's parallelogram as surfels: with v0, e01, e02 = prim.p,
+    positions[i, j] = v0 + (i + 1/2) / width * e01 + (j + 1/2) / height * e02 pushed `offset` along the unit
+    normal, which is e01 x e02 normalised (negated with flip).  Returns (positions, normals), both
+    (width, height, 3) f64.  Raises for any other primitive kind."""
+    if prim.kind != RT_PRIM_TRIANGLE:
+        raise ValueError("prim_surfels: a triangle primitive (v0, e01, e02) is needed")
+    if width <= 0 or height <= 0:
+        raise ValueError("prim_surfels: width and height must be positive")
+    v0, e01, e02 = (np.array([v.x, v.y, v.z], np.float64) for v in prim.p)
+    nrm = np.cross(e01, e02)
+    length = np.sqrt(nrm @ nrm)
+    if not length > 0.0:
+        raise ValueError("prim_surfels: the triangle is degenerate")
+    nrm = nrm / length * (-1.0 if flip else 1.0)
+    u = ((np.arange(width) + 0.5) / width)[:, None, None]
+    v = ((np.arange(height) + 0.5) / height)[None, :, None]
+    positions = v0 + u * e01 + v * e02 + offset * nrm
+    return positions, np.broadcast_to(nrm, positions.shape).copy()
+
+
+def _ptr(a) -> int:
+    """A device pointer as an integer: a torch tensor's data_ptr(), or the integer itself."""
+    return int(a.data_ptr()) if hasattr(a, "data_ptr") else int(a)
 
 
 def _pack_items(items) -> np.ndarray:
@@ -1032,6 +1100,59 @@ class GpuRaytracer:
         _check(self.lib.rt_render_beams_device(self.handle, C.c_void_p(d_beam_list), n, spp, seed, sample_base,
                                                stream_base, C.c_void_p(d_sum), C.c_void_p(d_samples),
                                                C.c_void_p(d_misses), C.c_void_p(d_rays), C.c_void_p(stream)))
+
+    def render_surfels(self, positions, normals, spp: int, seed: int, mode: int = RT_GATHER_DIFFUSE, sample_base: int = 0,
+                       stream_base: int = 0, out=None):
+        """rt_render_surfels: the radiance arriving at surface points.  spp path-traced samples per surfel,
+        each along its own direction about the normal (need not be unit), drawn on the device from the two
+        draws render_rays discards: the reference's diffuse bounce (RT_GATHER_DIFFUSE), Lambert's cosine
+        (RT_GATHER_COSINE) or the uniform sphere (RT_GATHER_SPHERE).  positions and normals as (n, 3) or
+        (n, 4) arrays, or one SURFEL_DTYPE array with normals None.  A caller that leaves a surface offsets
+        the positions itself.  Returns and `out` as render_rays; gather_mean turns them into the mean."""
+        surfels = _pack_surfels(positions, normals)
+        n = surfels.shape[0]
+        if out is None:
+            out = (np.zeros((n, 3), np.float64), np.zeros(n, np.uint32), np.zeros(n, np.uint32))
+        s, ns, ms = out
+        for a, shape, dt in ((s, (n, 3), np.float64), (ns, (n,), np.uint32), (ms, (n,), np.uint32)):
+            if a.shape != shape or a.dtype != dt or not a.flags.c_contiguous:
+                raise ValueError("out must be C-contiguous (sum f64 [n, 3], samples u32 [n], misses u32 [n])")
+        count = C.c_uint64(0)
+        _check(self.lib.rt_render_surfels(self.handle, mode, surfels.ctypes.data_as(C.c_void_p), n, spp, seed, sample_base,
+                                          stream_base, s.ctypes.data_as(C.POINTER(rt_color)),
+                                          ns.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                          ms.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(count)))
+        return s, ns, ms, count.value
+
+    def render_surfels_device(self, d_surfel_list, n: int, spp: int, seed: int, mode: int, sample_base: int,
+                              stream_base: int, d_sum, d_samples, d_misses, d_rays=0, stream: int = 0) -> None:
+        """rt_render_surfels_device: render_rays_device for n rt_surfel (64 B each) at d_surfel_list.  The
+        device arrays as torch tensors or as pointers (integers)."""
+        _check(self.lib.rt_render_surfels_device(self.handle, mode, C.c_void_p(_ptr(d_surfel_list)), n, spp, seed,
+                                                 sample_base, stream_base, C.c_void_p(_ptr(d_sum)),
+                                                 C.c_void_p(_ptr(d_samples)), C.c_void_p(_ptr(d_misses)),
+                                                 C.c_void_p(_ptr(d_rays)), C.c_void_p(stream)))
+
+    def surfel_rays(self, positions, normals, spp: int, seed: int, mode: int = RT_GATHER_DIFFUSE, sample_base: int = 0,
+                    stream_base: int = 0) -> np.ndarray:
+        """rt_debug_surfel_rays_device on this scene's device: the fp32 ray of sample k of surfel i, widened,
+        as an (n, spp) RAY_DTYPE array (all zero for an invalid surfel).  render_rays of [:, k] at spp 1,
+        sample_base + k and the same stream_base gives render_surfels' sample k, bit for bit."""
+        import torch
+
+        surfels = _pack_surfels(positions, normals)
+        n = surfels.shape[0]
+        rays = np.zeros((n, max(spp, 0)), RAY_DTYPE)
+        with torch.cuda.device(self.device):
+            d_in = torch.from_numpy(surfels.view(np.uint8).copy()).cuda()
+            d_out = torch.zeros(max(rays.nbytes, 1), dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            _check(self.lib.rt_debug_surfel_rays_device(mode, C.c_void_p(d_in.data_ptr() if n else 0), n, spp, seed,
+                                                        sample_base, stream_base, C.c_void_p(d_out.data_ptr()), None))
+            torch.cuda.synchronize()
+            if rays.nbytes:
+                rays.view(np.uint8).reshape(-1)[:] = d_out.cpu().numpy()[:rays.nbytes]
+        return rays
 
     def _pixel_list(self, pixels) -> np.ndarray:
         p = np.asarray(pixels)

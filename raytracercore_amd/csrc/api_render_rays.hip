@@ -1,8 +1,9 @@
 // api_render_rays.hip -- the C ABI's radiance queries (include/rtcore.h, "radiance queries"):
 // Raytracer.GetColor(ray) (Raytracer.cs:248-252) for rays the caller brings, by the RAYS instances of
 // the path kernels (kernels_path.hip, refill), accumulated as SampleSet accumulates a pixel.  The
-// launch, the argument check and the two entry points' bodies serve rt_render_beams as well
-// (api_render_beams.hip, the BEAMS instances): a RenderList says which records a list holds.
+// launch, the argument check and the two entry points' bodies serve rt_render_beams and
+// rt_render_surfels as well (api_render_beams.hip, api_render_surfels.hip; the BEAMS and SURFELS
+// instances): a RenderList says which records a list holds.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -15,7 +16,7 @@ constexpr int64_t kRaysChunk = 1 << 19;      // rays of one chunk of rt_render_r
 constexpr uint64_t kChunkItems = 1ull << 26; // most work items of one chunk: 1 GiB of 16-B partials
 constexpr RenderList kRays = {ITEMS_RAYS, sizeof(rt_ray), kRaysChunk, "rays"};
 
-// The path kernel of the scene's variant, the list's instance (RAYS or BEAMS), over the p.n_rays
+// The path kernel of the scene's variant, the list's instance (RAYS, BEAMS or SURFELS), over the p.n_rays
 // records at d_list, and nothing after it: the caller folds p's partials.  run_path without what
 // rt_render_rays leaves alone: no timing slot, no counters, no ray log, never the scene-specialised kernel.
 int run_rays(rt_scene* s, const RenderList& kind, PathParams& p, const void* d_list, unsigned long long* d_count,
@@ -34,12 +35,13 @@ int run_rays(rt_scene* s, const RenderList& kind, PathParams& p, const void* d_l
     p.counter = s->counter.p;
     p.rays = d_count;
     p.ray_list = reinterpret_cast<const double2*>(d_list); // (beam_list is the same storage)
+    p.gather_mode = kind.gather_mode;                      // (start_rows' word: 0 but for the surfels)
     if (s->any_op && stream != s->last_stream) HIP_TRY(hipStreamWaitEvent(stream, s->done_ev, 0));
     HIP_TRY(hipMemsetAsync(p.counter, 0, sizeof(unsigned int) * kSplitStride * p.n_split, stream));
     const size_t dyn = path_dyn_lds(s->dev, s->variant);
-    const bool beams = kind.src == ITEMS_BEAMS;
-    int& cached_variant = beams ? s->beams_variant : s->rays_variant;
-    int& blocks_per_cu = beams ? s->beams_blocks_per_cu : s->rays_blocks_per_cu;
+    const bool beams = kind.src == ITEMS_BEAMS, surfels = kind.src == ITEMS_SURFELS;
+    int& cached_variant = beams ? s->beams_variant : surfels ? s->surfels_variant : s->rays_variant;
+    int& blocks_per_cu = beams ? s->beams_blocks_per_cu : surfels ? s->surfels_blocks_per_cu : s->rays_blocks_per_cu;
     if (cached_variant != s->variant) {
         blocks_per_cu = path_blocks_per_cu(s->variant, dyn, false, s->dev.n_vn > 0, kind.src);
         cached_variant = s->variant;

@@ -25,30 +25,7 @@
 #include "../../include/rtcore_rng.h"
 #include "rt_kernels.h"
 #include "rt_beam.h"
-#ifdef RT_SCENE_CONST
-// rt_jit.cpp generates this header per scene (and camera, for the grouped order): the launch's
-// PathScene and its brute-force records as 32-bit words (kSceneW, kGroupsW, kRectsW, kFramesW,
-// kTestsW, kXfW, kCameraW) and the camera switches (RT_SCENE_CAMERA_KIND / _DOF).  Every record
-// field then folds into the instructions (literal operands cost what a VGPR operand does on
-// gfx950, an SGPR operand twice that), the primitive loops unroll and the per-record flag branches
-// resolve at compile time.  Included first, so that every macro it defines is seen by the code.
-#include "rt_scene_const.h"
-#endif
-
 namespace rtc {
-namespace {
-
-struct V3 {
-    float x, y, z;
-};
-__device__ __forceinline__ V3 v3(float x, float y, float z) { return V3{x, y, z}; }
-__device__ __forceinline__ V3 xyz(float4 a) { return V3{a.x, a.y, a.z}; }
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 operator*(V3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
-__device__ __forceinline__ V3 operator*(V3 a, V3 b) { return {a.x * b.x, a.y * b.y, a.z * b.z}; }
-__device__ __forceinline__ V3 operator-(V3 a) { return {-a.x, -a.y, -a.z}; }
-__device__ __forceinline__ float dot(V3 a, V3 b) { return fmaf(a.x, b.x, fmaf(a.y, b.y, a.z * b.z)); }
 // Products with a scene or camera field.  In the scene-specialised build those fields are literals,
 // and IEEE rules keep fmaf(0, x, y) as an instruction (x could be infinite, and y + 0 is not y for
 // y = -0): axis-aligned cameras, rotation frames and two-sided rectangles carried ~20 such terms per
@@ -63,17 +40,32 @@ __device__ __forceinline__ bool known_zero(float c)
     return false;
 #endif
 }
-__device__ __forceinline__ float kfma(float a, float b, float c) { return (known_zero(a) || known_zero(b)) ? c : fmaf(a, b, c); }
+} // namespace rtc
+#define RT_HAVE_KNOWN_ZERO
+#include "rt_surfel.h"
+#ifdef RT_SCENE_CONST
+// rt_jit.cpp generates this header per scene (and camera, for the grouped order): the launch's
+// PathScene and its brute-force records as 32-bit words (kSceneW, kGroupsW, kRectsW, kFramesW,
+// kTestsW, kXfW, kCameraW) and the camera switches (RT_SCENE_CAMERA_KIND / _DOF).  Every record
+// field then folds into the instructions (literal operands cost what a VGPR operand does on
+// gfx950, an SGPR operand twice that), the primitive loops unroll and the per-record flag branches
+// resolve at compile time.  Included first, so that every macro it defines is seen by the code.
+#include "rt_scene_const.h"
+#endif
+
+namespace rtc {
+namespace {
+
+// (V3 with its scaling, dot, cross, madd, kfma and fsqrt: rt_surfel.h, which shares them; known_zero: above)
+__device__ __forceinline__ V3 xyz(float4 a) { return V3{a.x, a.y, a.z}; }
+__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
+__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ V3 operator*(V3 a, V3 b) { return {a.x * b.x, a.y * b.y, a.z * b.z}; }
+__device__ __forceinline__ V3 operator-(V3 a) { return {-a.x, -a.y, -a.z}; }
 __device__ __forceinline__ float kmul(float a, float b) { return (known_zero(a) || known_zero(b)) ? -0.0f : a * b; }
 __device__ __forceinline__ float dot4(float4 r, V3 p) { return kfma(r.x, p.x, kfma(r.y, p.y, kfma(r.z, p.z, r.w))); }
 __device__ __forceinline__ float dot3(float4 r, V3 p) { return kfma(r.x, p.x, kfma(r.y, p.y, kmul(r.z, p.z))); }
-__device__ __forceinline__ V3 cross(V3 a, V3 b)
-{
-    return {fmaf(a.y, b.z, -a.z * b.y), fmaf(a.z, b.x, -a.x * b.z), fmaf(a.x, b.y, -a.y * b.x)};
-}
-__device__ __forceinline__ V3 madd(V3 a, float s, V3 c) { return {kfma(a.x, s, c.x), kfma(a.y, s, c.y), kfma(a.z, s, c.z)}; }
 __device__ __forceinline__ float rcp(float x) { return __builtin_amdgcn_rcpf(x); }
-__device__ __forceinline__ float fsqrt(float x) { return __builtin_amdgcn_sqrtf(x); }
 __device__ __forceinline__ V3 normalize(V3 a) { return a * __builtin_amdgcn_rsqf(dot(a, a)); }
 __device__ __forceinline__ V3 xf_point(const float4* m, V3 p) { return {dot4(m[0], p), dot4(m[1], p), dot4(m[2], p)}; }
 __device__ __forceinline__ V3 xf_dir(const float4* m, V3 p) { return {dot3(m[0], p), dot3(m[1], p), dot3(m[2], p)}; }
@@ -812,41 +804,6 @@ struct Sample {
 
 __device__ __forceinline__ float next_u(rt_rng& r) { return rt_rng_next_float(&r); }
 
-// Vec4D.CreateHorizon(pole, z, theta) (Vec4D.cs:52-58) as the equivalent Rodrigues form:
-// pole*z + (c*cos(theta) + (pole x c)*sin(theta)) * s, c = normalize(pole x z^) or x^.
-// The frame (c, pole x c) depends on the pole only, so one bounce builds it once for both
-// the rough normal and the diffuse direction (both turn about the hit normal).
-struct Frame {
-    V3 c, bn;
-};
-__device__ __forceinline__ Frame make_frame(V3 pole)
-{
-    V3 c = v3(pole.y, -pole.x, 0.0f);
-    const float cl = fmaf(c.x, c.x, c.y * c.y);
-    c = (cl == 0.0f) ? v3(1.0f, 0.0f, 0.0f) : c * __builtin_amdgcn_rsqf(cl);
-    return Frame{c, cross(pole, c)};
-}
-__device__ __forceinline__ V3 horizon(const Frame& f, V3 pole, float z, float s, float turn)
-{
-    const float cs = __builtin_amdgcn_cosf(turn), sn = __builtin_amdgcn_sinf(turn); // argument in turns
-    const V3 h = madd(f.c, cs, f.bn * sn);
-    return madd(h, s, pole * z);
-}
-
-// 2 * acos(u) / pi for u in [0, 1): sqrt(1 - u) * P(u), the degree-7 fit of Abramowitz &
-// Stegun 4.4.46 (|error| <= 2e-8 rad) scaled by 2 / pi; as accurate as fp32 acosf here.
-__device__ __forceinline__ float acos_turn2(float u)
-{
-    float p = fmaf(u, -0.0008037268f, 0.0042463113f);
-    p = fmaf(u, p, -0.0108786384f);
-    p = fmaf(u, p, 0.0196663830f);
-    p = fmaf(u, p, -0.0319419540f);
-    p = fmaf(u, p, 0.0566457845f);
-    p = fmaf(u, p, -0.1366178393f);
-    p = fmaf(u, p, 1.0f);
-    return fsqrt(1.0f - u) * p;
-}
-
 struct Ray3 {
     V3 o, d;
 };
@@ -1446,6 +1403,11 @@ __device__ __forceinline__ int item_sample(const Lane& L, const ParT& p)
 // builds the sample's ray at the point (u, v) of the footprint that the two GetCameraRay draws name
 // (beam_sample, rt_beam.h: the copy the host twin compiles too).  A degenerate sample closes as one
 // primary miss without a query, an invalid beam closes all the item has left.
+// ITEMS_SURFELS (rt_render_surfels' instances): the RAYS instances with an rt_surfel of p.ray_list (the
+// same four rows) in the ray's place.  A sample start loads the rows again and draws the sample's
+// direction about the surfel's normal from the two GetCameraRay draws, by the functions of shade()'s
+// diffuse bounce (surfel_sample, rt_surfel.h: the copy rt_debug_surfel_rays_device's kernel compiles
+// too); p.gather_mode, a launch constant, picks the distribution.  An invalid surfel closes as a bad ray.
 // ITEMS_PIXELS (rt_render_pixels' instances): an item names entry item_ray(item) of p.pixel_list, a
 // frame pixel index fy * width + fx, and from there on the lane does what a tile launch does for that
 // frame pixel: its key from the table or the hash, the rng of sample_base + sample, start_sample with
@@ -1604,7 +1566,7 @@ __device__ __forceinline__ void refill(Lane& L, Sample& S, const ParT& p, const 
                         }
                     }
                 }
-            } else if constexpr (SRC == ITEMS_RAYS || SRC == ITEMS_BEAMS) {
+            } else if constexpr (SRC == ITEMS_RAYS || SRC == ITEMS_BEAMS || SRC == ITEMS_SURFELS) {
                 const unsigned ri = item_ray(L.item, p);
                 const int s0 = (int)((L.item >> 6) & (unsigned)(p.n_chunks - 1)) * p.chunk;
                 if (ri < p.n_rays && s0 < p.spp) {
@@ -1705,6 +1667,27 @@ __device__ __forceinline__ void refill(Lane& L, Sample& S, const ParT& p, const 
                      // sample; or, for an invalid beam, every sample the item has left (the rays' rule)
                 const unsigned left = r == BEAM_INVALID ? L.cnt >> 16 : 1u;
                 L.cnt += left * (256u - 65536u);
+                if (!NT) L.s_next += (int)left;
+            }
+        }
+        return;
+    }
+    if constexpr (SRC == ITEMS_SURFELS) {
+        if (L.active && L.item_open && !L.live && L.cnt >= 65536u) {
+            const unsigned si = NT ? item_ray(L.item, p) : (unsigned)L.fx;
+            if (NT) L.pkey = rt_rng_pixel_key(p.seed_key, p.stream_base + (unsigned long long)si);
+            S.rng = rt_rng_from_pixel_key(L.pkey, p.sample_base + (unsigned long long)item_sample<NT>(L, p));
+            // GetCameraRay's subX and subY (Raytracer.cs:264-265): the direction's cosine and turn
+            const float u1 = (float)rt_rng_next24(&S.rng) * 0x1p-24f;
+            const float u2 = (float)rt_rng_next24(&S.rng) * 0x1p-24f;
+            if (surfel_sample(p.ray_list + 4 * (size_t)si, p.gather_mode, u1, u2, S.o, S.d)) {
+                S.tint = v3(1.0f, 1.0f, 1.0f);
+                S.bounce = 0;
+                S.prev = -1;
+                L.live = true;
+            } else { // every sample the item has left is a primary miss; no query, so no ray counted
+                const unsigned left = L.cnt >> 16;
+                L.cnt = (L.cnt & 0xFFFFu) + (left << 8);
                 if (!NT) L.s_next += (int)left;
             }
         }
@@ -1997,8 +1980,9 @@ __device__ __forceinline__ void path_body(const CameraF* __restrict__ camp, cons
     flush_counts<STATS>(wave_rays, cnt, *(const ParamsC*)pp, lane);
 }
 
-// SRC: ITEMS_RAYS / ITEMS_PIXELS / ITEMS_BEAMS, rt_render_rays' / rt_render_pixels' / rt_render_beams'
-// instances (refill); the tile instances are as they were without the switch.
+// SRC: ITEMS_RAYS / ITEMS_PIXELS / ITEMS_BEAMS / ITEMS_SURFELS, rt_render_rays' / rt_render_pixels' /
+// rt_render_beams' / rt_render_surfels' instances (refill); the tile instances are as they were without
+// the switch.
 template <bool CULL, bool LDS, bool STATS, bool VN, int SRC = ITEMS_TILE>
 __global__ void __launch_bounds__(256, CULL ? RT_GROUPED_WAVES : RT_PATH_WAVES)
     path_kernel(PathScene, const CameraF* __restrict__ camp, const PathParams* __restrict__ pp, const TestRec*,
@@ -3016,6 +3000,8 @@ PathKernel pick_brute(bool stats, bool vn, ItemSource src)
         return vn ? path_kernel<CULL, LDS, false, true, ITEMS_RAYS> : path_kernel<CULL, LDS, false, false, ITEMS_RAYS>;
     if (src == ITEMS_BEAMS)
         return vn ? path_kernel<CULL, LDS, false, true, ITEMS_BEAMS> : path_kernel<CULL, LDS, false, false, ITEMS_BEAMS>;
+    if (src == ITEMS_SURFELS)
+        return vn ? path_kernel<CULL, LDS, false, true, ITEMS_SURFELS> : path_kernel<CULL, LDS, false, false, ITEMS_SURFELS>;
     if (vn) return stats ? path_kernel<CULL, LDS, true, true> : path_kernel<CULL, LDS, false, true>;
     return stats ? path_kernel<CULL, LDS, true, false> : path_kernel<CULL, LDS, false, false>;
 }
@@ -3040,14 +3026,20 @@ PathKernel pick_bvh(bool stats, bool vn, ItemSource src)
                       : path_kernel_bvh<WIDTH, STACK, LDS, false, false, ITEMS_BEAMS>;
         return nullptr;
     }
+    if (src == ITEMS_SURFELS) {
+        if constexpr (WIDTH == 4)
+            return vn ? path_kernel_bvh<WIDTH, STACK, LDS, false, true, ITEMS_SURFELS>
+                      : path_kernel_bvh<WIDTH, STACK, LDS, false, false, ITEMS_SURFELS>;
+        return nullptr;
+    }
     if (vn) return stats ? path_kernel_bvh<WIDTH, STACK, LDS, true, true> : path_kernel_bvh<WIDTH, STACK, LDS, false, true>;
     return stats ? path_kernel_bvh<WIDTH, STACK, LDS, true, false> : path_kernel_bvh<WIDTH, STACK, LDS, false, false>;
 }
 
 // variant = kernel * 2 + lds; kernel 0 brute force (flat), 1 brute force (grouped, culled),
 // 2 BVH2 (24-entry LDS stack), 3 wide BVH (RT_WIDE_STACK-entry LDS stack); both overflow to global memory.
-// src: ITEMS_RAYS / ITEMS_PIXELS / ITEMS_BEAMS, rt_render_rays' / rt_render_pixels' / rt_render_beams'
-// instance of the variant (never instrumented; none for the BVH2 kernel)
+// src: ITEMS_RAYS / ITEMS_PIXELS / ITEMS_BEAMS / ITEMS_SURFELS, rt_render_rays' / rt_render_pixels' /
+// rt_render_beams' / rt_render_surfels' instance of the variant (never instrumented; none for the BVH2 kernel)
 PathKernel pick(int variant, bool stats, bool vn, ItemSource src = ITEMS_TILE)
 {
     switch (variant) {

@@ -9,9 +9,9 @@ constexpr int kMaxSplit = 8;     // item ranges of a launch: one per XCD of the 
 constexpr int kSplitStride = 32; // dispenser words apart (one 128-B line each)
 
 // Where the work items of a path launch come from (refill, kernels_path.hip): the pixels of a window,
-// a caller's rays (rt_render_rays), a list of frame pixels (rt_render_pixels) or a caller's beams
-// (rt_render_beams).
-enum ItemSource : int { ITEMS_TILE = 0, ITEMS_RAYS = 1, ITEMS_PIXELS = 2, ITEMS_BEAMS = 3 };
+// a caller's rays (rt_render_rays), a list of frame pixels (rt_render_pixels), a caller's beams
+// (rt_render_beams) or a caller's surfels (rt_render_surfels).
+enum ItemSource : int { ITEMS_TILE = 0, ITEMS_RAYS = 1, ITEMS_PIXELS = 2, ITEMS_BEAMS = 3, ITEMS_SURFELS = 4 };
 
 // Work decomposition of one path-tracing launch over a w x h tile.
 struct PathParams {
@@ -103,6 +103,9 @@ struct PathParams {
     // that take it by value are as they were.
     // rt_render_beams, the BEAMS instances only: the launch is planned as for the rays, and entry i of
     // beam_list is an rt_beam as twelve rows (rt_beam.h); the pointer shares the rays' storage too.
+    // rt_render_surfels, the SURFELS instances only: the launch is planned as for the rays, and entry i
+    // of ray_list is an rt_surfel as four rows (position, normal; rt_surfel.h).  gather_mode, the
+    // rt_gather_mode of the launch, shares start_rows' word: a list launch has no start rows.
     // Start rows, the brute-force tile instances only (run_path plans them, plan_start_rows; null / 0:
     // off): float4 starts[wave][start_rows][64], wave = blockIdx.x * 4 + threadIdx.x / 64 of the
     // persistent grid, start_rows = chunk.  A wave that opens items writes every camera sample of a
@@ -117,7 +120,10 @@ struct PathParams {
         float4* starts;
     };
     unsigned int n_rays;        // rays or list entries of the launch (the items of the last block past it stay closed)
-    int start_rows;
+    union {
+        int start_rows;
+        int gather_mode;
+    };
     union {
         unsigned long long stream_base;
         struct {
@@ -312,7 +318,8 @@ size_t path_dyn_lds(const DevScene& s, int variant); // all dynamic LDS of a var
 // The camera and the launch parameters are read from device memory (d_cam, d_params).
 // src: ITEMS_RAYS, rt_render_rays' instance of the variant (PathParams::ray_list), which does not read
 // the camera; ITEMS_PIXELS, rt_render_pixels' (PathParams::pixel_list); ITEMS_BEAMS, rt_render_beams'
-// (PathParams::beam_list, no camera either).  All exist for the brute-force and the wide BVH kernels
+// (PathParams::beam_list, no camera either); ITEMS_SURFELS, rt_render_surfels' (ray_list as rt_surfel
+// rows and PathParams::gather_mode, no camera).  All exist for the brute-force and the wide BVH kernels
 // and are never instrumented.
 hipError_t launch_path(const DevScene& s, const CameraF* d_cam, const PathParams* d_params, int variant,
                        int grid_blocks, hipStream_t stream, bool stats, ItemSource src = ITEMS_TILE);

@@ -199,6 +199,9 @@ struct rt_scene {
     // rt_render_beams: its beams share query_rays (three rt_ray per beam) and its records
     // render_rays_recs; the blocks per CU of the BEAMS instance of `beams_variant`
     int beams_variant = -1, beams_blocks_per_cu = 1;
+    // rt_render_surfels: a surfel has an rt_ray's size and takes its place in query_rays and the staging;
+    // the blocks per CU of the SURFELS instance of `surfels_variant`
+    int surfels_variant = -1, surfels_blocks_per_cu = 1;
     // rt_render_pixels: two chunks of list entries and of per-entry records, and the blocks per CU of
     // the PIXELS instance of `pixels_variant`
     DevBuf<uint32_t> pixel_list;
@@ -328,16 +331,17 @@ int end_op(rt_scene* s, hipStream_t stream);
 int queue_copy(rt_scene* s, CopyPlan& plan, const void* d_src, size_t a, size_t b, size_t rec_bytes, int k,
                hipStream_t stream);
 int consume_copies(rt_scene* s, const CopyPlan& plan, const std::function<void(const unsigned char*, size_t, size_t)>& consume);
-// api_render_rays.hip: what rt_render_rays and rt_render_beams share, a radiance query over a list of
-// caller's records (rt_ray or rt_beam) by the src instances of the path kernels.  rec_bytes: one
-// record, a multiple of sizeof(rt_ray); chunk: most records of one chunk of the host entry; what:
-// the records' name in messages.  render_list_device / render_list_host are the two entry points'
+// api_render_rays.hip: what rt_render_rays, rt_render_beams and rt_render_surfels share, a radiance query
+// over a list of caller's records (rt_ray, rt_beam or rt_surfel) by the src instances of the path
+// kernels.  rec_bytes: one record, a multiple of sizeof(rt_ray); chunk: most records of one chunk of the
+// host entry; what: the records' name in messages; gather_mode: the surfels' rt_gather_mode (else 0).  render_list_device / render_list_host are the two entry points'
 // bodies, with the name of the entry point for messages.
 struct RenderList {
     ItemSource src;
     size_t rec_bytes;
     int64_t chunk;
     const char* what;
+    int gather_mode = 0;
 };
 int render_list_device(rt_scene* s, const RenderList& kind, const char* name, const void* d_list, int64_t n, int32_t spp,
                        uint64_t seed, uint64_t sample_base, uint64_t stream_base, double* d_sum, uint32_t* d_samples,

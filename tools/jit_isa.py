@@ -8,7 +8,7 @@ import sys
 
 CSRC = os.environ.get("RTCORE_CSRC") or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "raytracercore_amd", "csrc")
 NAMES = ["rt_jit_prelude.h", "kernels_path.hip", "../../include/rtcore_rng.h", "rt_kernels.h", "rt_internal.h",
-         "rt_beam.h", "../../include/rtcore.h"]
+         "rt_beam.h", "rt_surfel.h", "../../include/rtcore.h"]
 
 
 def main():
