@@ -53,7 +53,8 @@ extern "C" {
                                    rt_reproject_device and rt_debug_reproject, and rt_beam, rt_render_beams,
                                    rt_render_beams_device, rt_debug_beam_rays and rt_camera_beams, and
                                    rt_surfel, rt_gather_mode, rt_render_surfels, rt_render_surfels_device and
-                                   rt_debug_surfel_rays_device */
+                                   rt_debug_surfel_rays_device, and rt_list_kind, rt_render_list and
+                                   rt_render_list_device */
 
 typedef enum rt_status {
     RT_OK = 0,
@@ -803,6 +804,78 @@ int rt_render_surfels_device(rt_scene* scene, int32_t mode, const rt_surfel* d_s
    n > 0, n < 0, spp <= 0) / RT_ERR_HIP. */
 int rt_debug_surfel_rays_device(int32_t mode, const rt_surfel* d_surfels, int64_t n, int32_t spp, uint64_t seed,
                                 uint64_t sample_base, uint64_t stream_base, rt_ray* d_rays_out, void* stream);
+
+/* ---------------------------------------------------- indexed radiance queries --- */
+/*
+ * rt_render_list / rt_render_list_device: rt_render_rays, rt_render_beams or rt_render_surfels for a list
+ * of entry numbers into an array of records, added into accumulators indexed by entry, optionally with
+ * the moments of "adaptive sampling" below -- what rt_render_pixels is to a frame.  A caller that wants
+ * more samples of some entries only lists those: nothing is compacted, and no entry's stream changes.
+ * With rt_adaptive_select_device over the per-entry accumulators (a "frame" of n_records pixels) a
+ * lightmap, a probe grid or a panorama of the host's own is rendered until its error is below a bound.
+ *
+ * Records.  records holds n_records records of the type `kind` names: rt_ray, rt_beam or rt_surfel.
+ * gather_mode is the surfels' rt_gather_mode and must be 0 for rays and beams.
+ * The list.  index holds n entry numbers e = index[j]; index == NULL is the identity list, and n must
+ * then equal n_records.
+ * Sampling (normative).  Sample k of entry e is the sample the kind's own entry point defines for record
+ * e of the array: it draws from rt_rng_init(seed, stream_base + e, sample_base + k).  The stream is keyed
+ * by the entry number, not by the list position j.
+ * Accumulation.  Everything is added at index e.  sum, samples, misses and the ray count follow
+ * rt_render_rays' rule (a primary miss is counted in misses and not added to sum).
+ * Moments.  q and batches come both or neither, else RT_ERR_ARG, and follow rt_render_pixels' rule word
+ * for word: every work item j of an entry with t_j = samples + misses > 0 finished samples is one batch;
+ * Y_j is the fp64 luminance 0.299 r + 0.587 g + 0.114 b of the item's fp32 colour sums, left to right,
+ * each operation rounded on its own, a miss counting as luminance 0;
+ *     q[e] += sum over the call's batches of Y_j * Y_j / t_j            batches[e] += their number
+ * (the call's terms are summed in item order and added to q once).
+ * The estimate is that of "adaptive sampling": N = samples + misses, Y = 0.299 sum.r + 0.587 sum.g +
+ * 0.114 sum.b, J = batches, Q = q, s2 = max(0, (Q - Y * Y / N) / (J - 1)) for J >= 2 and se = sqrt(s2 / N),
+ * the standard error of the entry's mean luminance, and rt_adaptive_select_device's rule applies as it
+ * stands.  Its limit: it is the error of sum / N, misses counted as black.  For a gather that is the
+ * gathered mean (sum + misses * ambient) / N only where the ambient colour is black or the entry has no
+ * misses; elsewhere the misses' constant ambient term is counted as if it varied, and se over-estimates.
+ *
+ * What is promised (normative):
+ *   1. With index == NULL, plane == 0 and no moments, from equal accumulator contents, the result is
+ *      rt_render_rays_device's, rt_render_beams_device's or rt_render_surfels_device's bit for bit (and
+ *      rt_render_list's the host entries').
+ *   2. An entry's five accumulators depend on (seed, stream_base + e, the sample indices, the record, the
+ *      traversal mode) only: not on n, on n_records, on the entry's place in the list, on the host entry's
+ *      chunking or on the stream.  The samples per work item are s = min(64, ceil(spp / B)), B = 24 (BRUTE,
+ *      GROUPED) or 64 (BVH), a function of spp alone.
+ *   3. Coherence: entries 64 j .. 64 j + 63 of the list share a wave for every sample, so list neighbouring
+ *      records next to each other; rt_adaptive_select_device's block order over a texel grid does.
+ *
+ * rt_render_list_device: d_records resident on the scene's device; accumulators of n_records elements,
+ * the sum as planes R | G | B `plane` elements apart (0 = n_records).  Asynchronous on `stream`, ordered
+ * like the device-resident renders; one launch, RT_ERR_ARG for n above rt_render_rays_device's bound at
+ * this spp.  An entry >= n_records is skipped: not traced, nothing written.  An entry named twice is
+ * undefined (its accumulators are updated by two threads).
+ * rt_render_list (host): caller arrays of n_records elements (sum_rgb one rt_color per entry, as
+ * rt_render_rays), everything added to, every entry not in the list untouched.  Synchronous, on the
+ * scene's own stream; any n, in rt_render_rays' chunks (2^19 entries, 2^18 for beams; RTCORE_QUERY_CHUNK;
+ * fewer where spp makes a chunk's items pass 2^26), two of them resident, copies overlapping the kernels:
+ * the listed records and 4 B up, one 48-B record down per entry.  RT_ERR_ARG also for an entry >=
+ * n_records and for an entry named twice (checked with a bitmap before anything is launched).
+ *
+ * Errors, before anything is launched: RT_ERR_ARG for an unknown kind (checked first), then an unknown
+ * gather_mode (surfels) or a non-zero one (rays, beams), a null scene, n < 0, spp <= 0, only one of q /
+ * batches; then, for n > 0, a null records, sum, samples or misses pointer, n_records <= 0, n_records >=
+ * 2^32, plane non-zero and below n_records, a null index with n != n_records.  RT_ERR_STATE on a BVH2
+ * scene.  n == 0 (with arguments that pass the first group) returns RT_OK and touches nothing.  No camera
+ * is needed.  Always the generic kernels; the counters of rt_scene_get_stats, an armed rt_debug_ray_log,
+ * rt_kernel_times and the scene-specialised kernels are left as they were.
+ */
+typedef enum rt_list_kind { RT_LIST_RAYS = 0, RT_LIST_BEAMS = 1, RT_LIST_SURFELS = 2 } rt_list_kind;
+int rt_render_list_device(rt_scene* scene, int32_t kind, int32_t gather_mode, const void* d_records, int64_t n_records,
+                          const uint32_t* d_index, int64_t n, int32_t spp, uint64_t seed, uint64_t sample_base,
+                          uint64_t stream_base, double* d_sum, uint32_t* d_samples, uint32_t* d_misses, double* d_q,
+                          uint32_t* d_batches, uint64_t plane, unsigned long long* d_rays_count, void* stream);
+int rt_render_list(rt_scene* scene, int32_t kind, int32_t gather_mode, const void* records, int64_t n_records,
+                   const uint32_t* index, int64_t n, int32_t spp, uint64_t seed, uint64_t sample_base, uint64_t stream_base,
+                   rt_color* sum_rgb, uint32_t* samples, uint32_t* misses, double* q, uint32_t* batches,
+                   uint64_t* rays_out);
 
 /* ----------------------------------------------------------- adaptive sampling --- */
 /*

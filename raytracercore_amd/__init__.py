@@ -38,6 +38,7 @@ BOUNCE_TYPE_NAMES = ("Skipped", "Diffuse", "Specular", "SpecularFail", "Transmit
 RT_TRACE_MAX_RECORDS = 1 << 20  # records of one rt_trace_paths call
 # rt_gather_mode (rt_render_surfels): the reference's diffuse bounce, Lambert's cosine, the uniform sphere
 RT_GATHER_DIFFUSE, RT_GATHER_COSINE, RT_GATHER_SPHERE = 0, 1, 2
+RT_LIST_RAYS, RT_LIST_BEAMS, RT_LIST_SURFELS = 0, 1, 2  # rt_list_kind (rt_render_list)
 
 
 class rt_query_mode(enum.IntEnum):
@@ -251,7 +252,7 @@ _OPTIONAL = ("rt_query_rays", "rt_query_rays_device", "rt_camera_rays", "rt_sele
              "rt_occluded_rays", "rt_occluded_rays_device", "rt_render_pixels", "rt_render_pixels_device",
              "rt_adaptive_select_device", "rt_primary_hits_device", "rt_denoise_device", "rt_reproject_device",
              "rt_render_beams", "rt_render_beams_device", "rt_camera_beams",
-             "rt_render_surfels", "rt_render_surfels_device")
+             "rt_render_surfels", "rt_render_surfels_device", "rt_render_list", "rt_render_list_device")
 
 _lib: Optional[C.CDLL] = None
 
@@ -374,6 +375,12 @@ def load_library(path: str = "") -> C.CDLL:
                                                C.c_uint64, C.c_uint64] + [C.c_void_p] * 4 + [C.c_void_p]),
         "rt_debug_surfel_rays_device": (C.c_int, [C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64,
                                                   C.c_uint64, C.c_void_p, C.c_void_p]),
+        "rt_render_list": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                     C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, P(rt_color), P(C.c_uint32),
+                                     P(C.c_uint32), P(C.c_double), P(C.c_uint32), P(C.c_uint64)]),
+        "rt_render_list_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                            C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64] + [C.c_void_p] * 5 +
+                                  [C.c_uint64, C.c_void_p, C.c_void_p]),
         "rt_occluded_rays": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
         "rt_occluded_rays_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                               C.c_void_p]),
@@ -1154,6 +1161,134 @@ class GpuRaytracer:
                 rays.view(np.uint8).reshape(-1)[:] = d_out.cpu().numpy()[:rays.nbytes]
         return rays
 
+    def render_list(self, kind: int, records, index=None, spp: int = 1, seed: int = 0, mode: int = 0, sample_base: int = 0,
+                    stream_base: int = 0, out=None, moments: bool = False):
+        """rt_render_list: render_rays, render_beams or render_surfels (kind RT_LIST_RAYS, RT_LIST_BEAMS,
+        RT_LIST_SURFELS; mode: the surfels' gather mode, 0 otherwise) for the entries `index` lists of
+        `records`, one RAY_DTYPE, BEAM_DTYPE or SURFEL_DTYPE array as _pack_rays, _pack_beams or
+        _pack_surfels make it; index None lists every entry.  Sample k of entry e draws from (seed,
+        stream_base + e, sample_base + k) wherever e stands in the list, and everything is added at e, into
+        arrays over all n_records entries: new zeroed ones, or the caller's `out` = (sum, samples, misses),
+        with moments (sum, samples, misses, q, batches), which continues earlier calls as render_pixels' does.
+        Returns (sum[n_records, 3] f64, samples u32, misses u32, rays), with moments (.., q f64, batches u32):
+        the standard error of an entry's mean luminance follows from them (pixel_standard_error)."""
+        dtype = {RT_LIST_RAYS: RAY_DTYPE, RT_LIST_BEAMS: BEAM_DTYPE, RT_LIST_SURFELS: SURFEL_DTYPE}.get(kind)
+        if dtype is None:
+            raise ValueError("kind must be RT_LIST_RAYS, RT_LIST_BEAMS or RT_LIST_SURFELS")
+        recs = np.ascontiguousarray(records, dtype).reshape(-1)
+        n = recs.shape[0]
+        idx = None
+        if index is not None:
+            idx = np.asarray(index).reshape(-1)
+            if idx.size and (idx.min() < 0 or idx.max() >= 1 << 32):
+                raise ValueError("entry numbers must lie in [0, 2^32)")
+            idx = np.ascontiguousarray(idx, np.uint32)
+        if out is None:
+            out = (np.zeros((n, 3), np.float64), np.zeros(n, np.uint32), np.zeros(n, np.uint32))
+            if moments:
+                out += (np.zeros(n, np.float64), np.zeros(n, np.uint32))
+        if len(out) != (5 if moments else 3):
+            raise ValueError("out must be (sum, samples, misses), with moments (sum, samples, misses, q, batches)")
+        shapes = (((n, 3), np.float64), ((n,), np.uint32), ((n,), np.uint32), ((n,), np.float64), ((n,), np.uint32))
+        for a, (shape, dt) in zip(out, shapes):
+            if a.shape != shape or a.dtype != dt or not a.flags.c_contiguous:
+                raise ValueError("out must be C-contiguous arrays over the records (sum f64 [n, 3], samples, misses, "
+                                 "batches u32 [n], q f64 [n])")
+        s, ns, ms = out[:3]
+        q = out[3].ctypes.data_as(C.POINTER(C.c_double)) if moments else None
+        b = out[4].ctypes.data_as(C.POINTER(C.c_uint32)) if moments else None
+        count = C.c_uint64(0)
+        _check(self.lib.rt_render_list(self.handle, kind, mode, recs.ctypes.data_as(C.c_void_p), n,
+                                       idx.ctypes.data_as(C.c_void_p) if idx is not None else None,
+                                       n if idx is None else idx.size, spp, seed, sample_base, stream_base,
+                                       s.ctypes.data_as(C.POINTER(rt_color)), ns.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                       ms.ctypes.data_as(C.POINTER(C.c_uint32)), q, b, C.byref(count)))
+        return (s, ns, ms, count.value) + tuple(out[3:])
+
+    def render_list_device(self, kind: int, mode: int, d_records, n_records: int, d_index, n: int, spp: int, seed: int,
+                           sample_base: int, stream_base: int, d_sum, d_samples, d_misses, d_q=0, d_batches=0,
+                           plane: int = 0, d_rays=0, stream: int = 0) -> None:
+        """rt_render_list_device: asynchronous render of the n entries listed (uint32 entry numbers at d_index,
+        or 0: every entry, n == n_records) of the n_records records resident at d_records, into device
+        accumulators of n_records elements (d_sum planes R | G | B `plane` doubles apart, 0 = n_records; d_q,
+        d_batches both or 0; d_rays one uint64 ray counter or 0) on `stream`.  The device arrays as torch
+        tensors or as pointers (integers)."""
+        _check(self.lib.rt_render_list_device(self.handle, kind, mode, C.c_void_p(_ptr(d_records)), n_records,
+                                              C.c_void_p(0 if d_index is None else _ptr(d_index)), n, spp, seed, sample_base,
+                                              stream_base,
+                                              C.c_void_p(_ptr(d_sum)), C.c_void_p(_ptr(d_samples)),
+                                              C.c_void_p(_ptr(d_misses)), C.c_void_p(_ptr(d_q)), C.c_void_p(_ptr(d_batches)),
+                                              plane, C.c_void_p(_ptr(d_rays)), C.c_void_p(stream)))
+
+    def gather_adaptive(self, kind: int, records, rel_tol: float, min_spp: int, max_spp: int, batch_spp: int, seed: int = 0,
+                        mode: int = 0, lum_floor: float = 1e-3, shape: Optional[Tuple[int, int]] = None, stream_base: int = 0,
+                        sample_base: int = 0):
+        """render_adaptive's loop over an array of rays, beams or surfels (`kind`, `records` and `mode` as
+        render_list takes them): render until every entry's standard error is at most rel_tol of its mean
+        luminance (rtcore.h, "adaptive sampling" and "indexed radiance queries"), with the records, the
+        accumulators and the list held on this scene's device.  Each iteration: rt_adaptive_select_device
+        over the per-entry accumulators as a frame of shape = (width, height), width * height == n_records,
+        builds the list of entries that still need samples; the list's length is read (one 4-byte copy, the
+        loop's only synchronisation); rt_render_list_device adds batch_spp samples of the listed entries at
+        sample_base + iteration * batch_spp.  The default shape (n_records, 1) lists the entries in ascending
+        order; a lightmap passes its texel grid (entry y * width + x) and gets select's 8 x 8 block order,
+        neighbouring texels in one wave.  An entry's result does not depend on the order.
+        The loop stops when the list is empty.  The first select names every entry (N = 0 < min_spp), so
+        there is no special first pass.  Once an entry leaves the list its accumulators no longer change, so
+        the rule gives the same answer for ever and it never comes back; every listed entry has therefore
+        been in every earlier list and has the same N = iteration * batch_spp, which is why one sample_base
+        per iteration is right.  min_spp and max_spp are rounded up to multiples of batch_spp.
+        The estimate is that of sum / N with a miss counted as black: for a gather under a non-black ambient
+        colour it over-estimates the error of gather_mean where an entry has misses.
+        Returns render_adaptive's dict as flat device tensors of n_records: sum (3, n) f64, samples, misses,
+        batches (n,) i32 (the uint32 bits), q (n,) f64, spp (n,) i64, counts, lists, rays, params."""
+        import torch
+
+        if batch_spp <= 0 or min_spp <= 0 or max_spp < min_spp:
+            raise ValueError("need batch_spp > 0 and 0 < min_spp <= max_spp")
+        dtype = {RT_LIST_RAYS: RAY_DTYPE, RT_LIST_BEAMS: BEAM_DTYPE, RT_LIST_SURFELS: SURFEL_DTYPE}.get(kind)
+        if dtype is None:
+            raise ValueError("kind must be RT_LIST_RAYS, RT_LIST_BEAMS or RT_LIST_SURFELS")
+        recs = np.ascontiguousarray(records, dtype).reshape(-1)
+        n = recs.shape[0]
+        W, H = (n, 1) if shape is None else (int(shape[0]), int(shape[1]))
+        if n == 0 or W <= 0 or H <= 0 or W * H != n:
+            raise ValueError("shape = (width, height) must have width * height == n_records > 0")
+        up = lambda v: -(-int(v) // batch_spp) * batch_spp  # noqa: E731
+        par = rt_adaptive_params(float(rel_tol), float(lum_floor), up(min_spp), up(max_spp))
+        dev = torch.device("cuda", self.device)
+        with torch.cuda.device(dev):
+            d_recs = torch.from_numpy(recs.view(np.uint8).copy()).to(dev)
+            acc = {"sum": torch.zeros((3, n), dtype=torch.float64, device=dev),
+                   "samples": torch.zeros(n, dtype=torch.int32, device=dev),
+                   "misses": torch.zeros(n, dtype=torch.int32, device=dev),
+                   "q": torch.zeros(n, dtype=torch.float64, device=dev),
+                   "batches": torch.zeros(n, dtype=torch.int32, device=dev)}
+            d_count = torch.zeros(1, dtype=torch.int32, device=dev)
+            d_rays = torch.zeros(1, dtype=torch.int64, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            counts, lists = [], []
+            while True:
+                lst = torch.empty(n if not counts else counts[-1], dtype=torch.int32, device=dev)
+                adaptive_select_device(par, acc["sum"].data_ptr(), acc["samples"].data_ptr(), acc["misses"].data_ptr(),
+                                       acc["q"].data_ptr(), acc["batches"].data_ptr(), W, H, lst.data_ptr(), lst.numel(),
+                                       d_count.data_ptr(), stream=stream)
+                m = int(d_count.item()) & 0xFFFFFFFF
+                if m == 0:
+                    break
+                if m > lst.numel():
+                    raise RtError("gather_adaptive: the list of active entries grew")
+                lst = lst[:m]
+                self.render_list_device(kind, mode, d_recs, n, lst, m, batch_spp, seed,
+                                        int(sample_base) + len(counts) * batch_spp, stream_base, acc["sum"], acc["samples"],
+                                        acc["misses"], acc["q"], acc["batches"], 0, d_rays, stream)
+                counts.append(m)
+                lists.append(lst)
+            torch.cuda.synchronize(dev)
+        acc["spp"] = acc["samples"].to(torch.int64) + acc["misses"].to(torch.int64)
+        acc.update(counts=counts, lists=lists, rays=int(d_rays.item()), params=par)
+        return acc
+
     def _pixel_list(self, pixels) -> np.ndarray:
         p = np.asarray(pixels)
         if p.ndim == 2 and p.shape[1] == 2:  # (x, y) pairs
@@ -1581,7 +1716,9 @@ def pixels_plan(kernel: int, n: int, spp: int) -> dict:
 def pixel_standard_error(sum_rgb: np.ndarray, samples: np.ndarray, misses: np.ndarray, q: np.ndarray,
                          batches: np.ndarray) -> np.ndarray:
     """The standard error of each pixel's mean luminance from accumulators with moments (rtcore.h's
-    estimate); sum_rgb has the colour as its last axis.  inf where fewer than two batches were taken."""
+    estimate); sum_rgb has the colour as its last axis.  inf where fewer than two batches were taken.
+    It serves render_list's per-entry accumulators as they are (sum [n, 3]; gather_adaptive's planar sum
+    as sum.T): an entry is a pixel of a frame of n_records."""
     n = samples.astype(np.float64) + misses.astype(np.float64)
     y = 0.299 * sum_rgb[..., 0] + 0.587 * sum_rgb[..., 1] + 0.114 * sum_rgb[..., 2]
     with np.errstate(divide="ignore", invalid="ignore"):

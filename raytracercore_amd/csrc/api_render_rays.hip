@@ -16,11 +16,40 @@ constexpr int64_t kRaysChunk = 1 << 19;      // rays of one chunk of rt_render_r
 constexpr uint64_t kChunkItems = 1ull << 26; // most work items of one chunk: 1 GiB of 16-B partials
 constexpr RenderList kRays = {ITEMS_RAYS, sizeof(rt_ray), kRaysChunk, "rays"};
 
+// Argument and state checks shared by both entry points; RT_OK with *empty set for n == 0.
+int check_render_rays(rt_scene* s, const void* rays, int64_t n, int32_t spp, const void* sum, const void* samples,
+                      const void* misses, const char* name, bool* empty)
+{
+    *empty = false;
+    const char* bad = !s ? "null scene" : n < 0 ? "n < 0" : spp <= 0 ? "spp <= 0" : nullptr;
+    if (!bad && n == 0) { // (as rt_query_rays: an empty list may come with null arrays)
+        *empty = true;
+        return RT_OK;
+    }
+    if (!bad && (!rays || !sum || !samples || !misses)) bad = "null pointer";
+    if (bad) {
+        set_error(std::string(name) + ": bad argument (" + bad + ")");
+        return RT_ERR_ARG;
+    }
+    if (s->resolved == RT_TRAVERSAL_BVH2) {
+        set_error(std::string(name) + ": runs in the traversal modes BRUTE, GROUPED and BVH; this scene is in BVH2 mode "
+                                      "(rt_scene_set_traversal), use RT_TRAVERSAL_BVH");
+        return RT_ERR_STATE;
+    }
+    return RT_OK;
+}
+
+} // namespace
+
+namespace rtc {
+
 // The path kernel of the scene's variant, the list's instance (RAYS, BEAMS or SURFELS), over the p.n_rays
 // records at d_list, and nothing after it: the caller folds p's partials.  run_path without what
 // rt_render_rays leaves alone: no timing slot, no counters, no ray log, never the scene-specialised kernel.
+// d_index (rt_render_list; null for the three entry points here): the launch's index list over n_records
+// records, gathered as PathParams::list_gathered says.
 int run_rays(rt_scene* s, const RenderList& kind, PathParams& p, const void* d_list, unsigned long long* d_count,
-             hipStream_t stream)
+             hipStream_t stream, const uint32_t* d_index, unsigned n_records, bool gathered)
 {
     const size_t need = (size_t)p.n_chunks * (size_t)p.n_pad;
     uint64_t tickets = 0;
@@ -36,6 +65,9 @@ int run_rays(rt_scene* s, const RenderList& kind, PathParams& p, const void* d_l
     p.rays = d_count;
     p.ray_list = reinterpret_cast<const double2*>(d_list); // (beam_list is the same storage)
     p.gather_mode = kind.gather_mode;                      // (start_rows' word: 0 but for the surfels)
+    p.index_list = d_index;                                // (the cull's word: a list launch has none)
+    p.n_records = d_index ? n_records : 0u;
+    p.list_gathered = d_index && gathered ? 1 : 0;
     if (s->any_op && stream != s->last_stream) HIP_TRY(hipStreamWaitEvent(stream, s->done_ev, 0));
     HIP_TRY(hipMemsetAsync(p.counter, 0, sizeof(unsigned int) * kSplitStride * p.n_split, stream));
     const size_t dyn = path_dyn_lds(s->dev, s->variant);
@@ -64,33 +96,6 @@ int run_rays(rt_scene* s, const RenderList& kind, PathParams& p, const void* d_l
     return RT_OK;
 }
 
-// Argument and state checks shared by both entry points; RT_OK with *empty set for n == 0.
-int check_render_rays(rt_scene* s, const void* rays, int64_t n, int32_t spp, const void* sum, const void* samples,
-                      const void* misses, const char* name, bool* empty)
-{
-    *empty = false;
-    const char* bad = !s ? "null scene" : n < 0 ? "n < 0" : spp <= 0 ? "spp <= 0" : nullptr;
-    if (!bad && n == 0) { // (as rt_query_rays: an empty list may come with null arrays)
-        *empty = true;
-        return RT_OK;
-    }
-    if (!bad && (!rays || !sum || !samples || !misses)) bad = "null pointer";
-    if (bad) {
-        set_error(std::string(name) + ": bad argument (" + bad + ")");
-        return RT_ERR_ARG;
-    }
-    if (s->resolved == RT_TRAVERSAL_BVH2) {
-        set_error(std::string(name) + ": runs in the traversal modes BRUTE, GROUPED and BVH; this scene is in BVH2 mode "
-                                      "(rt_scene_set_traversal), use RT_TRAVERSAL_BVH");
-        return RT_ERR_STATE;
-    }
-    return RT_OK;
-}
-
-} // namespace
-
-namespace rtc {
-
 int render_list_device(rt_scene* s, const RenderList& kind, const char* name, const void* d_list, int64_t n, int32_t spp,
                        uint64_t seed, uint64_t sample_base, uint64_t stream_base, double* d_sum, uint32_t* d_samples,
                        uint32_t* d_misses, unsigned long long* d_count, void* stream)
@@ -107,7 +112,8 @@ int render_list_device(rt_scene* s, const RenderList& kind, const char* name, co
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     PathParams p = make_params_rays(kernel, n, spp, seed, sample_base, stream_base);
-    rc = run_rays(s, kind, p, d_list, d_count ? d_count : s->rays.p, st); // (no count wanted: the scene's scratch word)
+    // (no count wanted: the scene's scratch word)
+    rc = run_rays(s, kind, p, d_list, d_count ? d_count : s->rays.p, st, nullptr, 0, false);
     if (rc != RT_OK) return rc;
     HIP_TRY(launch_accumulate_rays(p, d_sum, d_samples, d_misses, nullptr, st));
     return end_op(s, st);
@@ -188,7 +194,7 @@ int render_list_host(rt_scene* s, const RenderList& kind, const char* name, cons
         const size_t m = count(k), slot = (size_t)(k & 1) * C;
         HIP_TRY(hipStreamWaitEvent(st, s->query_up_ev[k & 1], 0));
         PathParams p = make_params_rays(kernel, (int64_t)m, spp, seed, sample_base, stream_base + (uint64_t)(k * chunk));
-        rc = run_rays(s, kind, p, s->query_rays.p + slot * R, s->rays.p, st);
+        rc = run_rays(s, kind, p, s->query_rays.p + slot * R, s->rays.p, st, nullptr, 0, false);
         if (rc != RT_OK) return rc;
         HIP_TRY(launch_accumulate_rays(p, nullptr, nullptr, nullptr, s->render_rays_recs.p + slot, st));
         HIP_TRY(hipEventRecord(s->band_ev[k & 1], st));

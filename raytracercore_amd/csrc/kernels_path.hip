@@ -1368,6 +1368,23 @@ __device__ __forceinline__ unsigned item_ray(unsigned item, const ParT& p)
     return ((item >> (6 + p.log2_chunks)) << 6) | (item & 63u);
 }
 
+// rt_render_list (the RAYS, BEAMS and SURFELS instances of a launch with p.index_list): list position j
+// = item_ray(item) -> the record the lane loads (rec) and the number its stream is keyed by (key), both
+// j without a list.  With one the key is the entry e = index_list[j] and the record e's, or j's where the
+// host entry gathered the listed records into the chunk (p.list_gathered); false for an entry at or
+// past p.n_records, which opens no item.  The pointer test is wave-uniform.
+template <class ParT>
+__device__ __forceinline__ bool list_entry(const ParT& p, unsigned j, unsigned& rec, unsigned& key)
+{
+    rec = key = j;
+    if (p.index_list) {
+        key = p.index_list[j];
+        if (key >= p.n_records) return false;
+        if (!p.list_gathered) rec = key;
+    }
+    return true;
+}
+
 // rt_render_pixels (the PIXELS instances): a list entry pix = fy * width + fx -> (fx, fy), by the
 // fp32-reciprocal divmod the item decode uses.  Exact: the estimate (float)pix * inv_frame_w carries
 // three roundings of 2^-24 relative each, less than 2^-22 fy in all, so for fy < 2^20 rows
@@ -1408,6 +1425,11 @@ __device__ __forceinline__ int item_sample(const Lane& L, const ParT& p)
 // direction about the surfel's normal from the two GetCameraRay draws, by the functions of shade()'s
 // diffuse bounce (surfel_sample, rt_surfel.h: the copy rt_debug_surfel_rays_device's kernel compiles
 // too); p.gather_mode, a launch constant, picks the distribution.  An invalid surfel closes as a bad ray.
+// The three with an index list (rt_render_list; p.index_list, null on the three entry points' own launches):
+// the item names list position j = item_ray(item), and list_entry gives the record it loads and the
+// number its stream is keyed by, the entry index_list[j]; an entry at or past p.n_records opens no item.
+// The pointer test is wave-uniform, and without a list both are j: the code path of the entry points is
+// the one it was (profiles/render_list: the same registers and scratch in all 36 instances).
 // ITEMS_PIXELS (rt_render_pixels' instances): an item names entry item_ray(item) of p.pixel_list, a
 // frame pixel index fy * width + fx, and from there on the lane does what a tile launch does for that
 // frame pixel: its key from the table or the hash, the rng of sample_base + sample, start_sample with
@@ -1569,13 +1591,14 @@ __device__ __forceinline__ void refill(Lane& L, Sample& S, const ParT& p, const 
             } else if constexpr (SRC == ITEMS_RAYS || SRC == ITEMS_BEAMS || SRC == ITEMS_SURFELS) {
                 const unsigned ri = item_ray(L.item, p);
                 const int s0 = (int)((L.item >> 6) & (unsigned)(p.n_chunks - 1)) * p.chunk;
-                if (ri < p.n_rays && s0 < p.spp) {
+                unsigned rec, key;
+                if (ri < p.n_rays && s0 < p.spp && list_entry(p, ri, rec, key)) {
                     L.item_open = true;
                     if (!NT) L.s_next = s0;
                     L.cnt = (unsigned)(min(p.spp, s0 + p.chunk) - s0) << 16; // chunk <= 64
                     if (!NT) {
-                        L.fx = (int)ri;
-                        L.pkey = rt_rng_pixel_key(p.seed_key, p.stream_base + (unsigned long long)ri);
+                        L.fx = (int)rec;
+                        L.pkey = rt_rng_pixel_key(p.seed_key, p.stream_base + (unsigned long long)key);
                     }
                 }
             } else {
@@ -1625,8 +1648,12 @@ __device__ __forceinline__ void refill(Lane& L, Sample& S, const ParT& p, const 
     }
     if constexpr (SRC == ITEMS_RAYS) {
         if (L.active && L.item_open && !L.live && L.cnt >= 65536u) {
-            const unsigned ri = NT ? item_ray(L.item, p) : (unsigned)L.fx;
-            if (NT) L.pkey = rt_rng_pixel_key(p.seed_key, p.stream_base + (unsigned long long)ri);
+            unsigned ri = (unsigned)L.fx;
+            if (NT) { // the record and the key again (an open item's entry is inside the records: list_entry)
+                unsigned key;
+                (void)list_entry(p, item_ray(L.item, p), ri, key);
+                L.pkey = rt_rng_pixel_key(p.seed_key, p.stream_base + (unsigned long long)key);
+            }
             const QueryRay q = load_query_ray(p.ray_list, ri);
             if (q.valid) {
                 S.rng = rt_rng_from_pixel_key(L.pkey, p.sample_base + (unsigned long long)item_sample<NT>(L, p));
@@ -1648,8 +1675,12 @@ __device__ __forceinline__ void refill(Lane& L, Sample& S, const ParT& p, const 
     }
     if constexpr (SRC == ITEMS_BEAMS) {
         if (L.active && L.item_open && !L.live && L.cnt >= 65536u) {
-            const unsigned bi = NT ? item_ray(L.item, p) : (unsigned)L.fx;
-            if (NT) L.pkey = rt_rng_pixel_key(p.seed_key, p.stream_base + (unsigned long long)bi);
+            unsigned bi = (unsigned)L.fx;
+            if (NT) { // the record and the key again (an open item's entry is inside the records: list_entry)
+                unsigned key;
+                (void)list_entry(p, item_ray(L.item, p), bi, key);
+                L.pkey = rt_rng_pixel_key(p.seed_key, p.stream_base + (unsigned long long)key);
+            }
             S.rng = rt_rng_from_pixel_key(L.pkey, p.sample_base + (unsigned long long)item_sample<NT>(L, p));
             // GetCameraRay's subX and subY (Raytracer.cs:264-265): the sample's point in the footprint
             const float u = (float)rt_rng_next24(&S.rng) * 0x1p-24f;
@@ -1674,8 +1705,12 @@ __device__ __forceinline__ void refill(Lane& L, Sample& S, const ParT& p, const 
     }
     if constexpr (SRC == ITEMS_SURFELS) {
         if (L.active && L.item_open && !L.live && L.cnt >= 65536u) {
-            const unsigned si = NT ? item_ray(L.item, p) : (unsigned)L.fx;
-            if (NT) L.pkey = rt_rng_pixel_key(p.seed_key, p.stream_base + (unsigned long long)si);
+            unsigned si = (unsigned)L.fx;
+            if (NT) { // the record and the key again (an open item's entry is inside the records: list_entry)
+                unsigned key;
+                (void)list_entry(p, item_ray(L.item, p), si, key);
+                L.pkey = rt_rng_pixel_key(p.seed_key, p.stream_base + (unsigned long long)key);
+            }
             S.rng = rt_rng_from_pixel_key(L.pkey, p.sample_base + (unsigned long long)item_sample<NT>(L, p));
             // GetCameraRay's subX and subY (Raytracer.cs:264-265): the direction's cosine and turn
             const float u1 = (float)rt_rng_next24(&S.rng) * 0x1p-24f;
@@ -2787,13 +2822,11 @@ __global__ void accumulate_rays_kernel(PathParams p, double* sum, uint32_t* samp
 // Y_j = 0.299 r + 0.587 g + 0.114 b of the chunk's fp32 sums (DoubleColor.GetLuminance, left to
 // right, every operation rounded on its own), q += Y_j Y_j / t_j and batches += 1.  recs: the same
 // from zero as one PixelRec per entry (the host entry's download), zero for a skipped entry.
-__global__ void accumulate_pixels_kernel(PathParams p, double* sum, uint32_t* samples, uint32_t* misses, double* q,
-                                         uint32_t* batches, size_t plane, PixelRec* recs)
+// (fold_entry: entry i's partials into the accumulators at a; rt_render_list's fold below is the same.)
+__device__ __forceinline__ void fold_entry(const PathParams& p, size_t i, size_t a, bool inside, double* sum,
+                                           uint32_t* samples, uint32_t* misses, double* q, uint32_t* batches, size_t plane,
+                                           PixelRec* recs)
 {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)p.n_rays) return;
-    const size_t a = p.pixel_list[i];
-    const bool inside = a < (size_t)p.n_frame_px;
     if (!inside && !recs) return;
     double r = 0.0, g = 0.0, bl = 0.0, qs = 0.0;
     if (!recs) {
@@ -2841,6 +2874,28 @@ __global__ void accumulate_pixels_kernel(PathParams p, double* sum, uint32_t* sa
             batches[a] += nb;
         }
     }
+}
+
+__global__ void accumulate_pixels_kernel(PathParams p, double* sum, uint32_t* samples, uint32_t* misses, double* q,
+                                         uint32_t* batches, size_t plane, PixelRec* recs)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)p.n_rays) return;
+    const size_t a = p.pixel_list[i];
+    fold_entry(p, i, a, a < (size_t)p.n_frame_px, sum, samples, misses, q, batches, plane, recs);
+}
+
+// rt_render_list: accumulate_pixels_kernel for a RAYS, BEAMS or SURFELS launch.  List position i's partials
+// go into the per-entry accumulators at e = index[i] (i itself without a list, where the sums are
+// accumulate_rays_kernel's: r = sum[e], then r += v.x per chunk), an entry at or past n_records is
+// skipped; recs: one PixelRec per list position, from zero.
+__global__ void accumulate_list_kernel(PathParams p, const uint32_t* index, size_t n_records, double* sum, uint32_t* samples,
+                                       uint32_t* misses, double* q, uint32_t* batches, size_t plane, PixelRec* recs)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)p.n_rays) return;
+    const size_t e = index ? (size_t)index[i] : i;
+    fold_entry(p, i, e, e < n_records, sum, samples, misses, q, batches, plane, recs);
 }
 
 // SampleSet.GetOutput / GetColorCode (SampleSet.cs:50-113) per pixel of planar accumulators.
@@ -3220,6 +3275,17 @@ hipError_t launch_accumulate_pixels(const PathParams& p, double* d_sum, uint32_t
     if (plane == 0) plane = (size_t)p.n_frame_px;
     hipLaunchKernelGGL(accumulate_pixels_kernel, dim3((p.n_rays + 255u) / 256u), dim3(256), 0, stream, p, d_sum, d_samples,
                        d_misses, d_q, d_batches, plane, (PixelRec*)nullptr);
+    return hipGetLastError();
+}
+
+hipError_t launch_accumulate_list(const PathParams& p, const uint32_t* d_index, size_t n_records, double* d_sum,
+                                  uint32_t* d_samples, uint32_t* d_misses, double* d_q, uint32_t* d_batches, size_t plane,
+                                  PixelRec* d_recs, hipStream_t stream)
+{
+    if (p.n_rays == 0) return hipSuccess;
+    if (plane == 0) plane = n_records;
+    hipLaunchKernelGGL(accumulate_list_kernel, dim3((p.n_rays + 255u) / 256u), dim3(256), 0, stream, p, d_index, n_records,
+                       d_sum, d_samples, d_misses, d_q, d_batches, plane, d_recs);
     return hipGetLastError();
 }
 

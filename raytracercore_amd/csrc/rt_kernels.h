@@ -16,8 +16,20 @@ enum ItemSource : int { ITEMS_TILE = 0, ITEMS_RAYS = 1, ITEMS_PIXELS = 2, ITEMS_
 // Work decomposition of one path-tracing launch over a w x h tile.
 struct PathParams {
     int x0, y0, w, h;           // tile within the frame
-    int band, band_stride, band_offset; // band > 0: tile row r is frame row
-                                        // y0 + ((r / band) * band_stride + band_offset) * band + r % band
+    int band;                   // band > 0: tile row r is frame row
+                                // y0 + ((r / band) * band_stride + band_offset) * band + r % band
+    // rt_render_list, the RAYS, BEAMS and SURFELS instances with an index list (index_list below; a list
+    // launch has no band, band = 0, so its two words carry the list's): the records the entries name, and
+    // whether entry j's record lies at list position j (1: the host entry's gathered chunk) or at its
+    // entry number index_list[j] (0: the device entry's resident array)
+    union {
+        int band_stride;
+        unsigned int n_records;
+    };
+    union {
+        int band_offset;
+        int list_gathered;
+    };
     int band_log2;              // log2(band) for a power-of-two band, else -1 (divide by inv_band)
     float inv_band;             // fp32 1 / band
     int spp;                    // samples per pixel in this launch
@@ -145,7 +157,14 @@ struct PathParams {
     //   kCullTable + i             live block i -> bx | by << 16
     //   kCullTable + n_live + b    window block b = by * blocks_x + bx -> its live number, or -1
     // One field (last, so that no other moves): the BVH kernels take this record by value.
-    const unsigned int* cull;
+    // rt_render_list, the RAYS, BEAMS and SURFELS instances (a list launch has no cull): null, or the index
+    // list.  Item j = (block << 6) | pixel then names entry e = index_list[j]: its stream key is that
+    // of stream_base + e, its record is e's (or j's, list_gathered), and an entry at or past n_records
+    // opens no item.  Null on rt_render_rays', rt_render_beams' and rt_render_surfels' own launches.
+    union {
+        const unsigned int* cull;
+        const unsigned int* index_list;
+    };
 };
 static_assert(__builtin_offsetof(PathParams, start_rows) == __builtin_offsetof(PathParams, n_rays) + 4 &&
                   __builtin_offsetof(PathParams, scene_bound) == __builtin_offsetof(PathParams, n_rays) + 16,
@@ -372,6 +391,13 @@ struct PixelRec {
 };
 // The same fold from zero, one PixelRec per entry (q and batches always)
 hipError_t launch_accumulate_pixels_recs(const PathParams& p, PixelRec* d_recs, hipStream_t stream);
+// rt_render_list: a RAYS, BEAMS or SURFELS launch's partials folded per list position i, in chunk order,
+// into per-entry accumulators at e = d_index[i] (null: i), planes `plane` apart (0 = n_records), with
+// launch_accumulate_pixels' moments; an entry at or past n_records is skipped.  d_recs: instead written
+// from zero as one PixelRec per list position.
+hipError_t launch_accumulate_list(const PathParams& p, const uint32_t* d_index, size_t n_records, double* d_sum,
+                                  uint32_t* d_samples, uint32_t* d_misses, double* d_q, uint32_t* d_batches, size_t plane,
+                                  PixelRec* d_recs, hipStream_t stream);
 // planar row-major accumulators (w*h) -> TileRec[w*h] in x*h + y order
 hipError_t launch_tile_host_layout(int w, int h, const double* d_sum, const uint32_t* d_samples,
                                   const uint32_t* d_misses, TileRec* d_out, hipStream_t stream);

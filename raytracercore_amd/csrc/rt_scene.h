@@ -343,6 +343,11 @@ struct RenderList {
     const char* what;
     int gather_mode = 0;
 };
+// The path launch of a list (no fold): kind's instance over the p.n_rays records at d_list; with d_index
+// (rt_render_list, api_render_list.hip) item j is entry d_index[j] of n_records records, whose record lies
+// at list position j (gathered) or at its entry number.
+int run_rays(rt_scene* s, const RenderList& kind, PathParams& p, const void* d_list, unsigned long long* d_count,
+             hipStream_t stream, const uint32_t* d_index, unsigned n_records, bool gathered);
 int render_list_device(rt_scene* s, const RenderList& kind, const char* name, const void* d_list, int64_t n, int32_t spp,
                        uint64_t seed, uint64_t sample_base, uint64_t stream_base, double* d_sum, uint32_t* d_samples,
                        uint32_t* d_misses, unsigned long long* d_count, void* stream);
