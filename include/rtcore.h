@@ -54,7 +54,8 @@ extern "C" {
                                    rt_render_beams_device, rt_debug_beam_rays and rt_camera_beams, and
                                    rt_surfel, rt_gather_mode, rt_render_surfels, rt_render_surfels_device and
                                    rt_debug_surfel_rays_device, and rt_list_kind, rt_render_list and
-                                   rt_render_list_device */
+                                   rt_render_list_device, and rt_occluded_surfels and
+                                   rt_occluded_surfels_device */
 
 typedef enum rt_status {
     RT_OK = 0,
@@ -537,6 +538,59 @@ int rt_occluded_rays(rt_scene* scene, int32_t mode, const rt_ray* rays, const do
                      uint8_t* occluded_out);
 int rt_occluded_rays_device(rt_scene* scene, int32_t mode, const rt_ray* d_rays, const double* d_t_max, int64_t n,
                             uint8_t* d_occluded, void* stream);
+
+/*
+ * rt_occluded_surfels / rt_occluded_surfels_device: how many of a surface point's sample segments are
+ * occluded.  rt_occluded_rays wants one rt_ray and one t_max per SAMPLE; here the caller brings one
+ * rt_surfel (below, "radiance queries") and one t_max per POINT and the device draws the directions: ambient
+ * occlusion, sky visibility, a probe's openness, from 64 B (+ 8 B of t_max) up and 4 B down per point for
+ * any number of samples.
+ * The sample (normative).  Sample k of entry e is the ray rt_render_surfels defines for sample k of record
+ *   e: rt_rng_init(seed, stream_base + e, sample_base + k), U1 and U2 from its first two draws, the formulas
+ *   of rt_surfel in gather_mode; the ray rt_debug_surfel_rays_device reports.  No further draw is used.  The
+ *   stream is keyed by the entry number, not by the list position.
+ * The segment starts at that ray's origin and ends at t_max[e], indexed by entry; NULL means +inf for every
+ *   entry.  rt_occluded_rays' rules hold word for word: t_max[e] is rounded to fp32 to nearest; NaN, <= 0 or
+ *   rounding to 0 is an empty segment (no sample occluded); +inf is valid.  There is no skip primitive and
+ *   no t_min: the caller offsets the position.
+ * Promise 1 (bit for bit): sample k of entry e counts as occluded exactly when
+ *   rt_occluded_rays_device(RT_QUERY_FAST) answers 1 for that reported ray with t_max[e], on the same scene
+ *   in the same traversal mode (BRUTE, GROUPED, or BVH with either builder): always the generic kernels,
+ *   with the order of the records outside the main loop and RTCORE_OCCLUDED_EARLY as that entry reads them.
+ * Accumulation: occluded[e] += the count and samples[e] += spp, both added to; samples may be NULL.  An
+ *   invalid surfel (rt_render_surfels' definition) counts as spp unoccluded samples, rt_occluded_rays' rule
+ *   that a bad ray gives 0.  Every listed entry below n_records therefore gets exactly samples += spp.
+ * Promise 2: an entry's counts depend only on (seed, stream_base + e, the sample indices, the record,
+ *   t_max[e], the traversal mode); not on n, on n_records, on the entry's place in the list, on the host
+ *   entry's chunking or on the stream.  The counts are integers, so this holds however the kernels split the
+ *   samples; two calls over sample ranges that join give the counts of one call over the joined range.
+ * The list (device entry): d_index[j], j < n, names the entries; NULL is the identity and n must equal
+ *   n_records.  An entry >= n_records is skipped and nothing is written for it; an entry named twice is
+ *   undefined.  d_surfels, d_t_max, d_occluded and d_samples have n_records elements.  The host entry has no
+ *   list: n surfels, surfel i keyed stream_base + i.
+ * Errors, before anything is launched: RT_ERR_ARG for an unknown gather_mode (checked first), a null scene,
+ *   n < 0, spp <= 0; then, for n > 0, a null surfels or occluded pointer, n_records <= 0 or >= 2^32, a null
+ *   index with n != n_records.  RT_ERR_STATE on a BVH2 scene, with rt_query_rays' message.  n == 0 returns
+ *   RT_OK and touches nothing.  No camera is needed.  The counters of rt_scene_get_stats, an armed
+ *   rt_debug_ray_log, the rt_kernel_times ring and the scene-specialised kernels are left as they were.
+ * rt_occluded_surfels_device is asynchronous on `stream`, ordered like the device-resident renders (the
+ *   per-scene scratch rule of the preamble); it splits into as many launches as 2^30 (entry, sample) pairs
+ *   per launch need.
+ * rt_occluded_surfels takes host buffers and is synchronous, on the scene's own stream, for any n: in
+ *   rt_occluded_rays' chunks (2^19 surfels, RTCORE_QUERY_CHUNK, two resident, the copies beside the kernels)
+ *   and buffers.
+ * Not part of it: RT_QUERY_EXACT (the answer is defined through the fp32 ray; the exact any-hit kernel stays
+ *   a per-ray entry), a falloff weight, and a loop that adapts spp to the counts (the standard error of an
+ *   occluded share p over N samples is sqrt(p (1 - p) / N): no moments are needed).
+ */
+struct rt_surfel; /* (defined under "radiance queries") */
+int rt_occluded_surfels_device(rt_scene* scene, int32_t gather_mode, const struct rt_surfel* d_surfels, int64_t n_records,
+                               const uint32_t* d_index, int64_t n, const double* d_t_max, int32_t spp, uint64_t seed,
+                               uint64_t sample_base, uint64_t stream_base, uint32_t* d_occluded, uint32_t* d_samples,
+                               void* stream);
+int rt_occluded_surfels(rt_scene* scene, int32_t gather_mode, const struct rt_surfel* surfels, int64_t n,
+                        const double* t_max, int32_t spp, uint64_t seed, uint64_t sample_base, uint64_t stream_base,
+                        uint32_t* occluded, uint32_t* samples);
 
 /* ------------------------------------------------------------ selection pass --- */
 /* DebugRaycaster's Selection mode (DebugRaycaster.cs:174-192): the overlay that shows only what

@@ -252,7 +252,8 @@ _OPTIONAL = ("rt_query_rays", "rt_query_rays_device", "rt_camera_rays", "rt_sele
              "rt_occluded_rays", "rt_occluded_rays_device", "rt_render_pixels", "rt_render_pixels_device",
              "rt_adaptive_select_device", "rt_primary_hits_device", "rt_denoise_device", "rt_reproject_device",
              "rt_render_beams", "rt_render_beams_device", "rt_camera_beams",
-             "rt_render_surfels", "rt_render_surfels_device", "rt_render_list", "rt_render_list_device")
+             "rt_render_surfels", "rt_render_surfels_device", "rt_render_list", "rt_render_list_device",
+             "rt_occluded_surfels", "rt_occluded_surfels_device")
 
 _lib: Optional[C.CDLL] = None
 
@@ -384,7 +385,12 @@ def load_library(path: str = "") -> C.CDLL:
         "rt_occluded_rays": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
         "rt_occluded_rays_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                               C.c_void_p]),
-        "rt_render_pixels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64,
+        "rt_occluded_surfels": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_uint64,
+                                          C.c_uint64, C.c_uint64, P(C.c_uint32), P(C.c_uint32)]),
+        "rt_occluded_surfels_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                 C.c_void_p, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]),
+        "rt_render_pixels":(C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64,
                                        P(rt_color), P(C.c_uint32), P(C.c_uint32), P(C.c_double), P(C.c_uint32),
                                        P(C.c_uint64)]),
         "rt_render_pixels_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64] +
@@ -739,6 +745,25 @@ def gather_mean(sum_rgb, samples, misses, ambient) -> np.ndarray:
     ns, ms = np.asarray(samples, np.float64), np.asarray(misses, np.float64)
     with np.errstate(invalid="ignore", divide="ignore"):
         return (s + ms[..., None] * amb) / (ns + ms)[..., None]
+
+
+def ambient_occlusion(occluded, samples) -> np.ndarray:
+    """1 - occluded / samples of occluded_surfels' counts: the share of a point's sample segments that
+    reach their end unhindered (in RT_GATHER_COSINE mode the ambient occlusion term).  NaN where a point has
+    no sample.  Its standard error is sqrt(p (1 - p) / samples)."""
+    occ, ns = np.asarray(occluded, np.float64), np.asarray(samples, np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(ns > 0, 1.0 - occ / ns, np.nan)
+
+
+def _surfel_t_max(t_max, n: int) -> Optional[np.ndarray]:
+    """occluded_surfels' t_max (None, a scalar or an array of n) as n contiguous doubles, or None."""
+    if t_max is None:
+        return None
+    t = np.asarray(t_max, np.float64)
+    if t.ndim > 1 or (t.ndim == 1 and t.shape[0] != n):
+        raise ValueError("t_max must be None, a scalar or an array with one value per surfel")
+    return np.ascontiguousarray(np.broadcast_to(t, (n,)))
 
 
 def prim_surfels(prim: rt_prim, width: int, height: int, offset: float, flip: bool = False) -> Tuple[np.ndarray, np.ndarray]:
@@ -1160,6 +1185,45 @@ class GpuRaytracer:
             if rays.nbytes:
                 rays.view(np.uint8).reshape(-1)[:] = d_out.cpu().numpy()[:rays.nbytes]
         return rays
+
+    def occluded_surfels(self, positions, normals, spp: int, seed: int, mode: int = RT_GATHER_COSINE, t_max=None,
+                         sample_base: int = 0, stream_base: int = 0, out=None):
+        """rt_occluded_surfels: how many of spp sample segments of each surface point are occluded.  The
+        directions are render_surfels' (sample k of surfel i from the stream (seed, stream_base + i,
+        sample_base + k), the rays surfel_rays reports), each segment starts at the position and ends at t_max:
+        None (+inf), a scalar, or one value per surfel.  A sample counts exactly when occluded_rays answers
+        True for its ray and t_max.  positions and normals as render_surfels takes them; a caller that leaves
+        a surface offsets the positions itself.  Returns (occluded u32[n], samples u32[n]): new zeroed arrays,
+        or the caller's `out` = (occluded, samples), which the call adds into; ambient_occlusion turns them
+        into 1 - occluded / samples."""
+        surfels = _pack_surfels(positions, normals)
+        n = surfels.shape[0]
+        tm = _surfel_t_max(t_max, n)
+        if out is None:
+            out = (np.zeros(n, np.uint32), np.zeros(n, np.uint32))
+        if len(out) != 2:
+            raise ValueError("out must be (occluded, samples)")
+        for a in out:
+            if a.shape != (n,) or a.dtype != np.uint32 or not a.flags.c_contiguous:
+                raise ValueError("out must be C-contiguous (occluded u32 [n], samples u32 [n])")
+        occ, ns = out
+        _check(self.lib.rt_occluded_surfels(self.handle, mode, surfels.ctypes.data_as(C.c_void_p), n,
+                                            tm.ctypes.data_as(C.c_void_p) if tm is not None else None, spp, seed,
+                                            sample_base, stream_base, occ.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                            ns.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return occ, ns
+
+    def occluded_surfels_device(self, mode: int, d_surfels, n_records: int, d_index, n: int, d_t_max, spp: int, seed: int,
+                                sample_base: int, stream_base: int, d_occluded, d_samples=0, stream: int = 0) -> None:
+        """rt_occluded_surfels_device: asynchronous counts for the n entries listed (uint32 entry numbers at
+        d_index, or None: every entry, n == n_records) of the n_records rt_surfel resident at d_surfels, bounded
+        by the n_records doubles at d_t_max (None or 0: unbounded), added into n_records uint32 at d_occluded and
+        (unless 0) d_samples on `stream`.  The device arrays as torch tensors or as pointers (integers)."""
+        _check(self.lib.rt_occluded_surfels_device(self.handle, mode, C.c_void_p(_ptr(d_surfels)), n_records,
+                                                   C.c_void_p(0 if d_index is None else _ptr(d_index)), n,
+                                                   C.c_void_p(0 if d_t_max is None else _ptr(d_t_max)), spp, seed, sample_base,
+                                                   stream_base, C.c_void_p(_ptr(d_occluded)), C.c_void_p(_ptr(d_samples)),
+                                                   C.c_void_p(stream)))
 
     def render_list(self, kind: int, records, index=None, spp: int = 1, seed: int = 0, mode: int = 0, sample_base: int = 0,
                     stream_base: int = 0, out=None, moments: bool = False):

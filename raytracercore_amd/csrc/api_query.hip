@@ -7,16 +7,10 @@
 
 #include "rt_scene.h"
 
-namespace {
+namespace rtc { // (declared in rt_scene.h: api_occluded_surfels.hip launches over the same record)
 
-constexpr int64_t kQueryChunk = 1 << 19;    // rays of one chunk of rt_query_rays; two chunks are resident
-constexpr int64_t kQueryLaunchMax = 1 << 30; // rays of one launch (32-bit ray indices and dispenser)
-
-// The generic kernel of the scene's traversal mode (path_variant's numbering).
 int query_kernel(const rt_scene* s) { return s->resolved == RT_TRAVERSAL_BVH ? 3 : s->resolved == RT_TRAVERSAL_GROUPED ? 1 : 0; }
 
-// The RT_QUERY_FAST launch record of n rays for that kernel (unstaged records) and its grid; the BVH
-// kernel's ray dispenser is zeroed on `st` and its overflow area reserved.
 int fill_query(rt_scene* s, int kernel, int blocks_per_cu, const rt_ray* d_rays, unsigned n, hipStream_t st, QueryParams& p,
                int& grid)
 {
@@ -49,6 +43,10 @@ int fill_query(rt_scene* s, int kernel, int blocks_per_cu, const rt_ray* d_rays,
     }
     return RT_OK;
 }
+
+} // namespace rtc
+
+namespace {
 
 // One launch over n <= kQueryLaunchMax rays on `st`, after the stream ordering is settled.
 int launch_rays(rt_scene* s, int32_t mode, const rt_ray* d_rays, unsigned n, rt_hit* d_hits, hipStream_t st)

@@ -2736,6 +2736,183 @@ __global__ void __launch_bounds__(256, RT_BVH_WAVES) occluded_bvh_kernel(Occlude
     }
 }
 
+// ---- rt_occluded_surfels: the occluded samples of a surfel, counted ------------------------------------
+// The segments of rt_occluded_rays with the ray drawn here: sample k of entry e is surfel_sample's ray
+// for the draws of rt_rng_init(seed, stream_base + e, sample_base + k), the ray
+// rt_debug_surfel_rays_device reports, and it is held to load_query_ray's rule as that ray would be
+// when it came back through rt_occluded_rays.  The counts are integers: how the samples are split among
+// lanes, waves and launches changes nothing.
+
+// The entry of list position j; false past the list or for an entry past the records (nothing written).
+__device__ __forceinline__ bool surfel_entry(const OccludedSurfelsParams& P, unsigned j, unsigned& e)
+{
+    if (j >= P.q.n) return false;
+    e = P.index ? P.index[j] : j;
+    return e < P.n_records;
+}
+
+// Sample k's ray of the surfel at rows; false: no query (an invalid surfel, or a ray rt_occluded_rays refuses).
+__device__ __forceinline__ bool surfel_segment(const OccludedSurfelsParams& P, const double2* __restrict__ rows, rt_key2 pkey,
+                                               unsigned k, V3& o, V3& d)
+{
+    rt_rng rng = rt_rng_from_pixel_key(pkey, P.sample_base + (unsigned long long)k);
+    const float u1 = (float)rt_rng_next24(&rng) * 0x1p-24f;
+    const float u2 = (float)rt_rng_next24(&rng) * 0x1p-24f;
+    if (!surfel_sample(rows, P.gather_mode, u1, u2, o, d)) return false;
+    const float inf = __builtin_huge_valf(); // (the origin is finite: surfel_sample)
+    return (fabsf(d.x) < inf) & (fabsf(d.y) < inf) & (fabsf(d.z) < inf) & ((d.x != 0.0f) | (d.y != 0.0f) | (d.z != 0.0f));
+}
+
+// Brute force (CULL: the grouped order).  A unit is (64 >> P.log2_lanes) consecutive list positions x
+// P.block consecutive samples, one wave per unit in a grid-stride loop.  The 1 << P.log2_lanes lanes that
+// share a position keep its surfel and walk the unit's samples side by side, sample k0 + lane % lanes first,
+// through occluded_brute_kernel's body: a wave then holds the samples of few neighbouring surfels, as
+// a wave of rt_occluded_rays over surfel-major rays does, which is what the grouped order's wave-wide box
+// culling lives on.  The sample loop is wave-uniform, so the votes of the any-hit form see the whole wave;
+// a lane without an entry, past the block's end, with an invalid surfel or an empty segment is masked.
+template <bool CULL>
+__global__ void __launch_bounds__(256, CULL ? RT_GROUPED_WAVES : RT_PATH_WAVES) occluded_surfels_brute_kernel(OccludedSurfelsParams P)
+{
+    const QueryParams& p = P.q;
+    const auto tests = (const RT_AS_CONST TestRec*)p.tests;
+    const auto rects = (const RT_AS_CONST RectRec*)p.rects;
+    const auto frames = (const RT_AS_CONST FrameRec*)p.frames;
+    const auto boxes = (const RT_AS_CONST BoxRec*)p.frames;
+    const auto groups = (const RT_AS_CONST GroupRec*)p.groups;
+    const auto xf = (const RT_AS_CONST XformF*)p.xf;
+    const unsigned lane = threadIdx.x & 63u;
+    const unsigned wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
+    const unsigned lanes = 1u << P.log2_lanes, per_wave = 64u >> P.log2_lanes; // lanes per position, positions per wave
+    const unsigned mine = lane & (lanes - 1u);
+    const unsigned n_units = ((p.n + per_wave - 1u) >> (6 - P.log2_lanes)) * P.blocks; // (the host keeps it in 32 bits)
+    for (unsigned u = wave; u < n_units; u += gridDim.x * 4u) {
+        const unsigned g = u / P.blocks, sb = u - g * P.blocks;
+        const unsigned k0 = sb * P.block, k1 = min(P.spp, k0 + P.block);
+        unsigned e = 0;
+        const bool listed = surfel_entry(P, g * per_wave + (lane >> P.log2_lanes), e);
+        if (!listed) e = 0; // (masked by the empty segment; its loads stay inside the records)
+        const double2* const rows = p.rays + 4 * (size_t)e;
+        const float tm = listed ? load_t_max(P.t_max, e) : 0.0f;
+        const rt_key2 pkey = rt_rng_pixel_key(P.seed_key, P.stream_base + (unsigned long long)e);
+        unsigned count = 0;
+        for (unsigned k = k0; k < k1; k += lanes) {
+            V3 o, d;
+            Best b{tm, -1};
+            if ((tm > 0.0f) && (k + mine < k1) && surfel_segment(P, rows, pkey, k + mine, o, d)) {
+                unsigned n_flat = 0, n_sph = 0, n_node = 0;
+                if (P.early) test_planes(p.scene, tests, o, d, -1, b);
+                if (__any(b.sg < 0)) {
+                    trace_brute<CULL, false, true>(p.scene, groups, tests, rects, frames, boxes, xf, o, d, -1, b, n_flat, n_sph,
+                                                   n_node);
+                    if (!P.early) test_planes(p.scene, tests, o, d, -1, b);
+                }
+            }
+            count += b.sg >= 0 ? 1u : 0u;
+        }
+        for (unsigned off = 1; off < lanes; off <<= 1) count += (unsigned)__shfl_xor((int)count, (int)off); // the position's lanes
+        if (!listed || mine != 0) continue;
+        if (P.blocks == 1) { // the position's lanes own its entry for the whole launch
+            P.occluded[e] += count;
+        } else if (count) {
+            atomicAdd(P.occluded + e, count);
+        }
+        if (P.samples && sb == 0) P.samples[e] += P.spp; // (one unit per entry has the first block)
+    }
+}
+
+// The wide BVH: occluded_bvh_kernel's loop with the pool dealing (list position, sample) units, unit =
+// position * spp + sample, so a wave's consecutive units are consecutive samples of one surfel and then
+// the next surfel's: its origins stay together.  A lane that takes a unit builds the ray and walks as
+// that kernel does.  The lanes whose queries ended occluded in one iteration add to the counts once per
+// entry among them (a ballot of the lanes with the leader's entry, and its population count).
+template <int STACK>
+__global__ void __launch_bounds__(256, RT_BVH_WAVES) occluded_surfels_bvh_kernel(OccludedSurfelsParams P)
+{
+    __shared__ int stack_mem[STACK * 256];
+    const QueryParams& p = P.q;
+    const TravStack stk = make_stack(stack_mem, p.stack_ovf);
+    const int lane = threadIdx.x & 63;
+    const RT_AS_CONST TestRec* tests = (const RT_AS_CONST TestRec*)p.tests;
+    const RT_AS_CONST float4* rows = (const RT_AS_CONST float4*)p.rows;
+    const RT_AS_CONST Node4Q* nodes4 = (const RT_AS_CONST Node4Q*)p.nodes4;
+    const RT_AS_CONST XformF* xf = (const RT_AS_CONST XformF*)p.xf;
+    const auto fetch = [&](int ref) { return Node4Q(nodes4[ref]); };
+    const unsigned n_units = p.n * P.spp; // (the host keeps it at or below 2^30)
+    bool trav = false, exhausted = false;
+    Walk w{false, 0, 0, -1};
+    unsigned n_tri = 0, n_sph = 0;
+    unsigned ent = 0;
+    RayPool pool{0, 0};
+    V3 o{0, 0, 0}, d{0, 0, 0}, id{0, 0, 0}, oi{0, 0, 0};
+    Best b{__builtin_huge_valf(), -1};
+    auto outside = [&]() { // the records outside the tree
+        if (p.scene.n_groups > 0)
+            test_outer<false>((const RT_AS_CONST GroupRec*)p.groups, (const RT_AS_CONST RectRec*)p.rects,
+                              (const RT_AS_CONST BoxRec*)p.frames, o, d, -1, b, n_tri);
+        test_planes(p.scene, tests, o, d, -1, b);
+    };
+    auto add_counts = [&](bool hit) { // every lane of the wave arrives
+        unsigned long long left = __ballot(hit);
+        while (left) {
+            const int leader = __builtin_ctzll(left);
+            const unsigned e0 = (unsigned)__builtin_amdgcn_readlane((int)ent, leader);
+            const unsigned long long same = __ballot(hit && ent == e0);
+            if (lane == leader) atomicAdd(P.occluded + e0, (unsigned)__popcll(same));
+            left &= ~same;
+        }
+    };
+    while (true) {
+        const bool need = !trav && !exhausted;
+        const unsigned long long m = __ballot(need);
+        // lanes without a query take the next units, once there are P.refill of them (or no lane walks): a
+        // unit's ray is drawn here, and that arithmetic is worth a fuller wave than a ray's four loads are
+        if (m && ((unsigned)__popcll(m) >= P.refill || !__any(trav))) {
+            const unsigned take = pool_take(pool, need, m, lane, p.counter);
+            bool hit = false;
+            if (need) {
+                if (take >= n_units) {
+                    exhausted = true;
+                } else {
+                    const unsigned j = take / P.spp, k = take - j * P.spp;
+                    unsigned e = 0;
+                    if (surfel_entry(P, j, e)) {
+                        ent = e;
+                        if (P.samples && k == 0) P.samples[e] += P.spp; // (one unit per entry has the first sample)
+                        const float tm = load_t_max(P.t_max, e);
+                        b = Best{tm, -1};
+                        bool open = (tm > 0.0f) && surfel_segment(P, p.rays + 4 * (size_t)e,
+                                                                  rt_rng_pixel_key(P.seed_key, P.stream_base + (unsigned long long)e), k, o, d);
+                        if (open && P.early) {
+                            outside();
+                            open = b.sg < 0;
+                        }
+                        if (!open) { // answered; the lane takes another unit at the next refill
+                            hit = b.sg >= 0;
+                        } else {
+                            id = v3(slab_rcp(d.x), slab_rcp(d.y), slab_rcp(d.z));
+                            oi = o * id;
+                            walk_start(w, p.root4, p.n_nodes4 > 0);
+                            trav = true;
+                        }
+                    }
+                }
+            }
+            add_counts(hit);
+        }
+        if (!__any(trav)) {
+            if (__any(!exhausted)) continue; // only answered units this round: refill again
+            break;
+        }
+        bool hit = false;
+        if (walk_step<STACK, true>(w, trav, p.spec, fetch, id, oi, stk, tests, rows, xf, o, d, -1, b, n_tri, n_sph).ended) {
+            trav = false;
+            if (!P.early && b.sg < 0) outside();
+            hit = b.sg >= 0;
+        }
+        add_counts(hit);
+    }
+}
+
 // plane: element stride between the R, G and B planes of sum (>= w*h; a gather slot may be taller
 // than the band set written into it)
 __global__ void accumulate_kernel(PathParams p, double* sum, uint32_t* samples, uint32_t* misses, size_t plane)
@@ -3370,6 +3547,21 @@ int occluded_blocks_per_cu(int kernel) { return blocks_per_cu(pick_occluded(kern
 hipError_t launch_occluded(const OccludedParams& p, int kernel, int grid_blocks, hipStream_t stream)
 {
     hipLaunchKernelGGL(pick_occluded(kernel), dim3(grid_blocks), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+using OccludedSurfelsKernel = void (*)(OccludedSurfelsParams);
+OccludedSurfelsKernel pick_occluded_surfels(int kernel)
+{
+    if (kernel == 3) return occluded_surfels_bvh_kernel<RT_WIDE_STACK>;
+    return kernel == 1 ? occluded_surfels_brute_kernel<true> : occluded_surfels_brute_kernel<false>;
+}
+
+int occluded_surfels_blocks_per_cu(int kernel) { return blocks_per_cu(pick_occluded_surfels(kernel)); }
+
+hipError_t launch_occluded_surfels(const OccludedSurfelsParams& p, int kernel, int grid_blocks, hipStream_t stream)
+{
+    hipLaunchKernelGGL(pick_occluded_surfels(kernel), dim3(grid_blocks), dim3(256), 0, stream, p);
     return hipGetLastError();
 }
 

@@ -306,6 +306,30 @@ struct OccludedParams {
 // RT_QUERY_FAST: kernel numbering, grids and blocks per CU as launch_query / query_blocks_per_cu.
 int occluded_blocks_per_cu(int kernel);
 hipError_t launch_occluded(const OccludedParams& p, int kernel, int grid_blocks, hipStream_t stream);
+// rt_occluded_surfels: the scene as rt_occluded_rays' kernels take it, q.rays the surfel records (an
+// rt_surfel has an rt_ray's rows) and q.n the list positions of the launch (q.hits unused).  Entry e of
+// position j is index[j], or j without a list; the records, t_max and the counts are indexed by entry.
+struct OccludedSurfelsParams {
+    QueryParams q;
+    const unsigned int* index;  // list positions -> entries, or null: the identity
+    unsigned int n_records;     // entries at or past it are skipped
+    const double* t_max;        // per entry, or null: +inf for every entry
+    unsigned int* occluded;     // per entry, added to
+    unsigned int* samples;      // per entry, added to, or null
+    int early;                  // as OccludedParams.early
+    int gather_mode;            // rt_gather_mode
+    unsigned int spp;           // samples of the launch per entry
+    unsigned int log2_lanes;    // brute force: lanes that share a list position, 1 << log2_lanes <= 64
+    unsigned int block;         // brute force: samples of one work unit ((64 >> log2_lanes) positions x block samples)
+    unsigned int blocks;        // brute force: units per position, ceil(spp / block); 1: its lanes own its entry
+    unsigned int refill;        // BVH: lanes without a query that trigger a refill (1 ... 64)
+    rt_key2 seed_key;
+    unsigned long long sample_base, stream_base;
+};
+// Kernel numbering as launch_occluded.  The brute-force kernels take any grid (grid-stride loop over the
+// units, one wave per unit), the BVH kernel deals q.n * spp (position, sample) units to whatever grid it gets.
+int occluded_surfels_blocks_per_cu(int kernel);
+hipError_t launch_occluded_surfels(const OccludedSurfelsParams& p, int kernel, int grid_blocks, hipStream_t stream);
 // RT_QUERY_EXACT (kernels_exact.hip): ref_raytrace_hit's distance against t_max in fp64, one ray per lane.
 hipError_t launch_occluded_exact(const DevScene& s, const rt_ray* d_rays, const double* d_t_max, unsigned n,
                                  unsigned char* d_out, hipStream_t stream);

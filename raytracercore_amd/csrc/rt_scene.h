@@ -192,6 +192,8 @@ struct rt_scene {
     // rt_occluded_rays: two chunks of segment ends and of answer bytes (its rays share query_rays and query_up_ev)
     DevBuf<double> occluded_t_max;
     DevBuf<unsigned char> occluded_out;
+    // rt_occluded_surfels: two chunks of counts (its surfels share query_rays, its segment ends occluded_t_max)
+    DevBuf<uint32_t> occluded_counts;
     // rt_render_rays: two chunks of per-ray records (its rays share query_rays and query_up_ev), and
     // the blocks per CU of the RAYS instance of `rays_variant`
     DevBuf<TileRec> render_rays_recs;
@@ -354,6 +356,15 @@ int render_list_device(rt_scene* s, const RenderList& kind, const char* name, co
 int render_list_host(rt_scene* s, const RenderList& kind, const char* name, const void* list, int64_t n, int32_t spp,
                      uint64_t seed, uint64_t sample_base, uint64_t stream_base, rt_color* sum_rgb, uint32_t* samples,
                      uint32_t* misses, uint64_t* rays_out);
+// api_query.hip: what rt_query_rays, rt_occluded_rays and rt_occluded_surfels (api_occluded_surfels.hip) share.
+constexpr int64_t kQueryChunk = 1 << 19;     // rays of one chunk of rt_query_rays; two chunks are resident
+constexpr int64_t kQueryLaunchMax = 1 << 30; // rays of one launch (32-bit ray indices and dispenser)
+// The generic kernel of the scene's traversal mode (path_variant's numbering).
+int query_kernel(const rt_scene* s);
+// The RT_QUERY_FAST launch record of n rays for that kernel (unstaged records) and its grid; the BVH
+// kernel's ray dispenser is zeroed on `st` and its overflow area reserved.
+int fill_query(rt_scene* s, int kernel, int blocks_per_cu, const rt_ray* d_rays, unsigned n, hipStream_t st, QueryParams& p,
+               int& grid);
 // api_render_pixels.hip: rt_render_pixels' list check (every entry below npix, none twice); null, or
 // what is wrong with entry *at
 const char* check_pixel_list(const uint32_t* pixels, int64_t n, uint64_t npix, int64_t* at);

@@ -2,7 +2,7 @@
 cosine-distributed directions about the hit's normal along which nothing lies within a radius R.
 
 usage: python tools/bake_ao.py SCENE [--width W] [--rays K] [--radius R] [--seed S]
-                               [--traversal MODE] [--out PREFIX]
+                               [--traversal MODE] [--device] [--out PREFIX]
 
 SCENE is a scene file (or the name of one shipped in tests/golden/scenes).  The steps: camera_rays (the
 rays rt_primary_ids traces), query_rays (RT_QUERY_FAST) for the hits, K directions per hit from a
@@ -11,6 +11,8 @@ position moved AO_EPSILON * max(1, |position|_inf) along the normal, off its own
 / K; a primary miss, and a hit whose normal is NaN (Triangle.GetNormal's quirk inside a vertex-normal
 triangle), get AO 1.  The image keeps the scene's aspect ratio at width W.  Writes PREFIX.npy (AO as
 float32 [H, W]) and PREFIX.ppm (binary P6, grey).
+--device: the K directions are drawn on the device instead (bake_ao_device): one surfel per hit through
+occluded_surfels (rt_occluded_surfels) in RT_GATHER_COSINE mode, 72 B up and 4 B down per hit for any K.
 """
 from __future__ import annotations
 
@@ -76,6 +78,34 @@ def bake_ao(gpu, k: int, radius: float, seed: int = 0, occluded=None) -> np.ndar
     return np.ascontiguousarray(ao.T)
 
 
+def ao_surfels(hits):
+    """The surfels of a HIT_DTYPE array (any shape): (mask, positions, normals) with mask as ao_rays gives
+    it, positions (m, 3) moved off the surface as ao_rays moves its origins, and the (m, 3) normals."""
+    h = np.asarray(hits).reshape(-1)
+    nrm = h["normal"].astype(np.float64)
+    mask = (h["prim_id"] >= 0) & np.isfinite(nrm).all(axis=1)
+    nrm = nrm[mask]
+    nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+    pos = h["position"][mask].astype(np.float64)
+    off = AO_EPSILON * np.maximum(1.0, np.max(np.abs(pos), axis=1, keepdims=True))
+    return mask.reshape(np.shape(hits)), pos + off * nrm, nrm
+
+
+def bake_ao_device(gpu, k: int, radius: float, seed: int = 0) -> np.ndarray:
+    """bake_ao with the directions drawn on the device (--device): one surfel per primary hit through
+    occluded_surfels (rt_occluded_surfels, RT_GATHER_COSINE) with t_max = radius, surfel i of the masked
+    hits on the stream (seed, i).  The same distribution as bake_ao's directions, not the same samples."""
+    import raytracercore_amd as rc
+
+    hits = gpu.query_rays(gpu.camera_rays())  # [x, y]
+    mask, pos, nrm = ao_surfels(hits)
+    ao = np.ones(hits.shape, np.float32)
+    if len(pos):
+        occ, ns = gpu.occluded_surfels(pos, nrm, k, seed, rc.RT_GATHER_COSINE, t_max=float(radius))
+        ao[mask] = rc.ambient_occlusion(occ, ns).astype(np.float32)
+    return np.ascontiguousarray(ao.T)
+
+
 def write_ppm(path: str, ao: np.ndarray) -> None:
     """AO [H, W] in [0, 1] as a grey binary PPM."""
     g = np.clip(np.rint(ao * 255.0), 0, 255).astype(np.uint8)
@@ -92,6 +122,7 @@ def main(argv=None) -> int:
     ap.add_argument("--radius", type=float, default=1.0)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--traversal", default="AUTO", choices=["AUTO", "BRUTE", "GROUPED", "BVH"])
+    ap.add_argument("--device", action="store_true", help="draw the directions on the device (rt_occluded_surfels)")
     ap.add_argument("--out", default="ao")
     a = ap.parse_args(argv)
     if a.width < 1 or a.rays < 1 or not a.radius > 0:
@@ -104,7 +135,7 @@ def main(argv=None) -> int:
     height = max(1, round(a.width * scene.params.height / max(1, scene.params.width)))
     gpu = rc.GpuRaytracer(scene, 0, size=(a.width, height), traversal=getattr(rc, "RT_TRAVERSAL_" + a.traversal))
     try:
-        ao = bake_ao(gpu, a.rays, a.radius, a.seed)
+        ao = (bake_ao_device if a.device else bake_ao)(gpu, a.rays, a.radius, a.seed)
     finally:
         gpu.close()
     np.save(a.out + ".npy", ao)
