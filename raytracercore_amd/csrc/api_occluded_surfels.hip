@@ -2,8 +2,8 @@
 // queries", rt_occluded_surfels): rt_occluded_rays with the sample's direction drawn on the device about
 // the surfel's normal (rt_surfel.h) and the answers counted per surfel.  The kernels are
 // kernels_path.hip's occluded_surfels_*; here the launch planning (how many launches the 32-bit work
-// indices need, the brute-force kernels' sample blocks) and the two entry points.  The host entry is
-// rt_occluded_rays' pipeline (api_query.hip) in its buffers: a surfel has an rt_ray's size.
+// indices need, the brute-force kernels' sample blocks) and the two entry points.  The host entry runs
+// the chunk pipeline in rt_occluded_rays' buffers: a surfel has an rt_ray's size.
 #include <cstdlib>
 #include <cstring>
 
@@ -154,16 +154,15 @@ int rt_occluded_surfels_device(rt_scene* s, int32_t gather_mode, const rt_surfel
     hipStream_t st = static_cast<hipStream_t>(stream);
     HIP_TRY(hipSetDevice(s->device));
     // the work counter and the stack overflow area are the scene's: order after its last operation
-    if (s->any_op && st != s->last_stream) HIP_TRY(hipStreamWaitEvent(st, s->done_ev, 0));
+    HIP_TRY(wait_last_op(s, st));
     const Draw dr{gather_mode, rt_rng_seed_key(seed), sample_base, stream_base};
     rc = launch_all(s, dr, d_surfels, n_records, d_index, n, d_t_max, spp, d_occluded, d_samples, st);
     if (rc != RT_OK) return rc;
     return end_op(s, st);
 }
 
-// rt_occluded_rays' pipeline (api_query.hip) with 72 B up (64 B without t_max) and 4 B down per surfel,
-// for any spp: the pinned staging holds the two slots of counts (at the offsets queue_copy gives them),
-// then the two surfel slots and the two slots of segment ends.  A chunk's counts are zeroed on the
+// The chunk pipeline (run_chunks) with 72 B up (64 B without t_max) and 4 B down per surfel, for any spp:
+// the surfels' two staging slots, then the two slots of segment ends.  A chunk's counts are zeroed on the
 // scene's stream before its kernel adds to them (after the download that last read the slot: the
 // kernel's wait for its upload orders that), and the host adds them, and spp, into the caller's arrays.
 int rt_occluded_surfels(rt_scene* s, int32_t gather_mode, const rt_surfel* surfels, int64_t n, const double* t_max, int32_t spp,
@@ -172,33 +171,23 @@ int rt_occluded_surfels(rt_scene* s, int32_t gather_mode, const rt_surfel* surfe
     bool empty;
     int rc = check_surfels(s, gather_mode, surfels, 1, true, n, spp, occluded, "rt_occluded_surfels", &empty); // (no list, any n)
     if (rc != RT_OK || empty) return rc;
-    int64_t chunk = kQueryChunk;
-    if (const char* e = getenv("RTCORE_QUERY_CHUNK")) chunk = std::max<int64_t>(1, std::min<int64_t>(kQueryChunk, atoll(e)));
-    chunk = std::min(chunk, n);
-    HIP_TRY(hipSetDevice(s->device));
-    if (!s->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
-    HIP_TRY(hipStreamSynchronize(s->copy_stream)); // (copies a failed call left behind: see rt_render_tile)
-    const size_t C = (size_t)chunk;
-    HIP_TRY(s->query_rays.reserve(2 * C));
-    HIP_TRY(s->occluded_counts.reserve(2 * C));
-    if (t_max) HIP_TRY(s->occluded_t_max.reserve(2 * C));
-    const size_t surfels_at = (2 * C * sizeof(uint32_t) + 63) & ~(size_t)63;
-    HIP_TRY(s->stage.reserve(surfels_at + 2 * C * (sizeof(rt_surfel) + sizeof(double))));
-    rt_surfel* stage_surfels = reinterpret_cast<rt_surfel*>(s->stage.p + surfels_at);
-    double* stage_t = reinterpret_cast<double*>(stage_surfels + 2 * C);
-    for (int j = 0; j < 2; j++) {
-        if (!s->query_up_ev[j]) HIP_TRY(hipEventCreateWithFlags(&s->query_up_ev[j], hipEventDisableTiming));
-        if (!s->band_ev[j]) HIP_TRY(hipEventCreateWithFlags(&s->band_ev[j], hipEventDisableTiming));
-    }
-    hipStream_t st = s->stream;
-    if (s->any_op && st != s->last_stream) HIP_TRY(hipStreamWaitEvent(st, s->done_ev, 0));
     const Draw dr{gather_mode, rt_rng_seed_key(seed), sample_base, stream_base};
-    const int64_t K = (n + chunk - 1) / chunk;
-    auto count = [&](int64_t k) { return (size_t)std::min(chunk, n - k * chunk); };
-    auto upload = [&](int64_t k) -> int {
-        const size_t m = count(k), slot = (size_t)(k & 1) * C;
-        const rt_surfel* src = surfels + k * chunk;
-        const double* src_t = t_max ? t_max + k * chunk : nullptr;
+    rt_surfel* stage_surfels = nullptr;
+    double* stage_t = nullptr;
+    ChunkJob job{n, kQueryChunk, 0, sizeof(uint32_t), sizeof(rt_surfel) + sizeof(double), /*one_piece*/ true,
+                 /*count_rays*/ false};
+    job.reserve = [&](size_t C, unsigned char* up, const void*& d_down) -> int {
+        HIP_TRY(s->query_rays.reserve(2 * C));
+        HIP_TRY(s->occluded_counts.reserve(2 * C));
+        if (t_max) HIP_TRY(s->occluded_t_max.reserve(2 * C));
+        stage_surfels = reinterpret_cast<rt_surfel*>(up);
+        stage_t = reinterpret_cast<double*>(stage_surfels + 2 * C);
+        d_down = s->occluded_counts.p;
+        return RT_OK;
+    };
+    job.upload = [&](int64_t, size_t first, size_t m, size_t slot) -> int {
+        const rt_surfel* src = surfels + first;
+        const double* src_t = t_max ? t_max + first : nullptr;
         parallel_ranges(m, 65536, [&](size_t a, size_t b) {
             std::memcpy(stage_surfels + slot + a, src + a, (b - a) * sizeof(rt_surfel));
             if (src_t) std::memcpy(stage_t + slot + a, src_t + a, (b - a) * sizeof(double));
@@ -208,50 +197,23 @@ int rt_occluded_surfels(rt_scene* s, int32_t gather_mode, const rt_surfel* surfe
         if (src_t)
             HIP_TRY(hipMemcpyAsync(s->occluded_t_max.p + slot, stage_t + slot, m * sizeof(double), hipMemcpyHostToDevice,
                                    s->copy_stream));
-        HIP_TRY(hipEventRecord(s->query_up_ev[k & 1], s->copy_stream));
         return RT_OK;
     };
-    CopyPlan plans[2];
-    auto consume = [&](int64_t k) -> int {
-        const size_t slot = (size_t)(k & 1) * C;
-        uint32_t* dst = occluded + k * chunk;
-        uint32_t* dst_n = samples ? samples + k * chunk : nullptr;
-        return consume_copies(s, plans[k & 1], [&](const unsigned char* stage, size_t a, size_t b) {
-            const uint32_t* c = reinterpret_cast<const uint32_t*>(stage);
-            for (size_t i = a; i < b; i++) {
-                dst[i - slot] += c[i];
-                if (dst_n) dst_n[i - slot] += (uint32_t)spp;
-            }
-        });
-    };
-    rc = upload(0);
-    if (rc != RT_OK) return rc;
-    for (int64_t k = 0; k < K; k++) {
-        const size_t m = count(k), slot = (size_t)(k & 1) * C;
-        HIP_TRY(hipStreamWaitEvent(st, s->query_up_ev[k & 1], 0));
+    job.launch = [&](int64_t, size_t first, size_t m, size_t slot, hipStream_t st) -> int {
         HIP_TRY(hipMemsetAsync(s->occluded_counts.p + slot, 0, m * sizeof(uint32_t), st));
         Draw d = dr;
-        d.stream_base += (uint64_t)(k * chunk);
-        rc = launch_all(s, d, reinterpret_cast<const rt_surfel*>(s->query_rays.p + slot), (int64_t)m, nullptr, (int64_t)m,
-                        t_max ? s->occluded_t_max.p + slot : nullptr, spp, s->occluded_counts.p + slot, nullptr, st);
-        if (rc != RT_OK) return rc;
-        HIP_TRY(hipEventRecord(s->band_ev[k & 1], st));
-        if (k >= 1) {
-            rc = consume(k - 1);
-            if (rc != RT_OK) return rc;
+        d.stream_base += (uint64_t)first;
+        return launch_all(s, d, reinterpret_cast<const rt_surfel*>(s->query_rays.p + slot), (int64_t)m, nullptr, (int64_t)m,
+                          t_max ? s->occluded_t_max.p + slot : nullptr, spp, s->occluded_counts.p + slot, nullptr, st);
+    };
+    job.consume = [&](const unsigned char* stage, size_t a, size_t b, size_t first, size_t slot) {
+        const uint32_t* c = reinterpret_cast<const uint32_t*>(stage);
+        for (size_t i = a; i < b; i++) {
+            occluded[first + (i - slot)] += c[i];
+            if (samples) samples[first + (i - slot)] += (uint32_t)spp;
         }
-        if (k + 1 < K) {
-            rc = upload(k + 1);
-            if (rc != RT_OK) return rc;
-        }
-        HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->band_ev[k & 1], 0));
-        plans[k & 1] = CopyPlan{};
-        rc = queue_copy(s, plans[k & 1], s->occluded_counts.p, slot, slot + m, sizeof(uint32_t), 1, s->copy_stream);
-        if (rc != RT_OK) return rc;
-    }
-    rc = end_op(s, st);
-    if (rc != RT_OK) return rc;
-    return consume(K - 1);
+    };
+    return run_chunks(s, job);
 }
 
 } // extern "C"

@@ -120,7 +120,7 @@ int query_device(rt_scene* s, int32_t mode, const rt_ray* d_rays, int64_t n, rt_
     }
     HIP_TRY(hipSetDevice(s->device));
     // the work counter and the stack overflow area are the scene's: order after its last operation
-    if (s->any_op && st != s->last_stream) HIP_TRY(hipStreamWaitEvent(st, s->done_ev, 0));
+    HIP_TRY(wait_last_op(s, st));
     for (int64_t a = 0; a < n; a += kQueryLaunchMax) {
         const int rc = launch_rays(s, mode, d_rays + a, (unsigned)std::min(kQueryLaunchMax, n - a), d_hits + a, st);
         if (rc != RT_OK) return rc;
@@ -160,7 +160,7 @@ int rt_primary_hits_device(rt_scene* s, int32_t x0, int32_t y0, int32_t w, int32
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(s->primary_rays.reserve((size_t)rows * (size_t)w));
     // the rays, the work counter and the stack overflow area are the scene's: order after its last operation
-    if (s->any_op && st != s->last_stream) HIP_TRY(hipStreamWaitEvent(st, s->done_ev, 0));
+    HIP_TRY(wait_last_op(s, st));
     for (int r = 0; r < h; r += rows) {
         const unsigned n = (unsigned)std::min(rows, h - r) * (unsigned)w;
         hipLaunchKernelGGL(camera_rays_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, s->camd, x0, y0 + r, w, n,
@@ -180,90 +180,45 @@ int rt_query_rays_device(rt_scene* s, int32_t mode, const rt_ray* d_rays, int64_
     return query_device(s, mode, d_rays, n, d_hits, static_cast<hipStream_t>(stream));
 }
 
-// Chunk k's rays go through pinned staging to device slot k & 1 on copy_stream, its kernel runs on the
-// scene's stream once they have landed, and its hits come back on copy_stream (queue_copy) into the
-// staging slot the host pool then copies out of (consume_copies).  The copy stream's order is
-// upload k + 1, download k: so chunk k's kernel runs beside download k - 1 and upload k + 1, and a
-// slot (device or pinned) is rewritten only after what last read it: upload k + 1 follows download
-// k - 1, which followed kernel k - 1, and the host refills a pinned ray slot after it has consumed the
-// download queued behind that slot's previous upload.
+// The chunk pipeline (run_chunks) with 64 B up and one rt_hit down per ray.
 int rt_query_rays(rt_scene* s, int32_t mode, const rt_ray* rays, int64_t n, rt_hit* hits_out)
 {
     bool empty;
     int rc = check_query(s, mode, rays, n, hits_out, "rt_query_rays", &empty);
     if (rc != RT_OK || empty) return rc;
-    int64_t chunk = kQueryChunk;
-    if (const char* e = getenv("RTCORE_QUERY_CHUNK")) chunk = std::max<int64_t>(1, std::min<int64_t>(kQueryChunk, atoll(e)));
-    chunk = std::min(chunk, n);
     if (mode == RT_QUERY_EXACT) {
         rc = ensure_ref_bvh(s);
         if (rc != RT_OK) return rc;
     }
-    HIP_TRY(hipSetDevice(s->device));
-    if (!s->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
-    HIP_TRY(hipStreamSynchronize(s->copy_stream)); // (copies a failed call left behind: see rt_render_tile)
-    const size_t C = (size_t)chunk;
-    HIP_TRY(s->query_rays.reserve(2 * C));
-    HIP_TRY(s->query_hits.reserve(2 * C));
-    // pinned staging: the two hit slots (at the offsets queue_copy gives them), then the two ray slots
-    HIP_TRY(s->stage.reserve(2 * C * (sizeof(rt_hit) + sizeof(rt_ray))));
-    rt_ray* stage_rays = reinterpret_cast<rt_ray*>(s->stage.p + 2 * C * sizeof(rt_hit));
-    for (int j = 0; j < 2; j++) {
-        if (!s->query_up_ev[j]) HIP_TRY(hipEventCreateWithFlags(&s->query_up_ev[j], hipEventDisableTiming));
-        if (!s->band_ev[j]) HIP_TRY(hipEventCreateWithFlags(&s->band_ev[j], hipEventDisableTiming));
-    }
-    hipStream_t st = s->stream;
-    if (s->any_op && st != s->last_stream) HIP_TRY(hipStreamWaitEvent(st, s->done_ev, 0));
-    const int64_t K = (n + chunk - 1) / chunk;
-    auto count = [&](int64_t k) { return (size_t)std::min(chunk, n - k * chunk); };
-    auto upload = [&](int64_t k) -> int {
-        const size_t m = count(k), slot = (size_t)(k & 1) * C;
-        const rt_ray* src = rays + k * chunk;
-        parallel_ranges(m, 65536, [&](size_t a, size_t b) { std::memcpy(stage_rays + slot + a, src + a, (b - a) * sizeof(rt_ray)); });
-        HIP_TRY(hipMemcpyAsync(s->query_rays.p + slot, stage_rays + slot, m * sizeof(rt_ray), hipMemcpyHostToDevice,
-                               s->copy_stream));
-        HIP_TRY(hipEventRecord(s->query_up_ev[k & 1], s->copy_stream));
+    rt_ray* stage_rays = nullptr;
+    std::atomic<bool> overflow{false};
+    ChunkJob job{n, kQueryChunk, 0, sizeof(rt_hit), sizeof(rt_ray), /*one_piece*/ false, /*count_rays*/ false};
+    job.reserve = [&](size_t C, unsigned char* up, const void*& d_down) -> int {
+        HIP_TRY(s->query_rays.reserve(2 * C));
+        HIP_TRY(s->query_hits.reserve(2 * C));
+        stage_rays = reinterpret_cast<rt_ray*>(up);
+        d_down = s->query_hits.p;
         return RT_OK;
     };
-    std::atomic<bool> overflow{false};
-    CopyPlan plans[2];
-    auto consume = [&](int64_t k) -> int {
-        const size_t slot = (size_t)(k & 1) * C;
-        rt_hit* dst = hits_out + k * chunk;
-        return consume_copies(s, plans[k & 1], [&](const unsigned char* stage, size_t a, size_t b) {
-            const rt_hit* h = reinterpret_cast<const rt_hit*>(stage);
-            std::memcpy(dst + (a - slot), h + a, (b - a) * sizeof(rt_hit));
-            if (mode == RT_QUERY_EXACT)
-                for (size_t i = a; i < b; i++)
-                    if (h[i].prim_id == -2) overflow = true;
-        });
+    job.upload = [&](int64_t, size_t first, size_t m, size_t slot) -> int {
+        const rt_ray* src = rays + first;
+        parallel_ranges(m, 65536,
+                        [&](size_t a, size_t b) { std::memcpy(stage_rays + slot + a, src + a, (b - a) * sizeof(rt_ray)); });
+        HIP_TRY(hipMemcpyAsync(s->query_rays.p + slot, stage_rays + slot, m * sizeof(rt_ray), hipMemcpyHostToDevice,
+                               s->copy_stream));
+        return RT_OK;
     };
-    rc = upload(0);
-    if (rc != RT_OK) return rc;
-    for (int64_t k = 0; k < K; k++) {
-        const size_t m = count(k), slot = (size_t)(k & 1) * C;
-        HIP_TRY(hipStreamWaitEvent(st, s->query_up_ev[k & 1], 0));
-        rc = launch_rays(s, mode, s->query_rays.p + slot, (unsigned)m, s->query_hits.p + slot, st);
-        if (rc != RT_OK) return rc;
-        HIP_TRY(hipEventRecord(s->band_ev[k & 1], st));
-        if (k >= 1) {
-            rc = consume(k - 1);
-            if (rc != RT_OK) return rc;
-        }
-        if (k + 1 < K) {
-            rc = upload(k + 1);
-            if (rc != RT_OK) return rc;
-        }
-        HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->band_ev[k & 1], 0));
-        plans[k & 1] = CopyPlan{};
-        rc = queue_copy(s, plans[k & 1], s->query_hits.p, slot, slot + m, sizeof(rt_hit),
-                        (int)std::max<size_t>(1, std::min<size_t>(rt_scene::kCopyChunks, (m * sizeof(rt_hit)) >> 20)),
-                        s->copy_stream);
-        if (rc != RT_OK) return rc;
-    }
-    rc = end_op(s, st);
-    if (rc != RT_OK) return rc;
-    rc = consume(K - 1);
+    job.launch = [&](int64_t, size_t, size_t m, size_t slot, hipStream_t st) {
+        return launch_rays(s, mode, s->query_rays.p + slot, (unsigned)m, s->query_hits.p + slot, st);
+    };
+    job.consume = [&](const unsigned char* stage, size_t a, size_t b, size_t first, size_t slot) {
+        const rt_hit* h = reinterpret_cast<const rt_hit*>(stage);
+        std::memcpy(hits_out + first + (a - slot), h + a, (b - a) * sizeof(rt_hit));
+        if (mode == RT_QUERY_EXACT)
+            for (size_t i = a; i < b; i++)
+                if (h[i].prim_id == -2) overflow = true;
+    };
+    rc = run_chunks(s, job);
     if (rc != RT_OK) return rc;
     if (overflow) {
         set_error("rt_query_rays: the reference BVH is deeper than the exact kernel's traversal stack");
@@ -284,7 +239,7 @@ int rt_occluded_rays_device(rt_scene* s, int32_t mode, const rt_ray* d_rays, con
         if (rc != RT_OK) return rc;
     }
     HIP_TRY(hipSetDevice(s->device));
-    if (s->any_op && st != s->last_stream) HIP_TRY(hipStreamWaitEvent(st, s->done_ev, 0));
+    HIP_TRY(wait_last_op(s, st));
     for (int64_t a = 0; a < n; a += kQueryLaunchMax) {
         rc = launch_segments(s, mode, d_rays + a, d_t_max ? d_t_max + a : nullptr, (unsigned)std::min(kQueryLaunchMax, n - a),
                              d_occluded + a, st);
@@ -293,44 +248,33 @@ int rt_occluded_rays_device(rt_scene* s, int32_t mode, const rt_ray* d_rays, con
     return end_op(s, st);
 }
 
-// rt_query_rays' pipeline (above) with 72 B up (64 B without t_max) and 1 B down per ray: the pinned
-// staging holds the two answer slots (at the offsets queue_copy gives them), then the two ray slots
-// and the two slots of segment ends.
+// The chunk pipeline (run_chunks) with 72 B up (64 B without t_max) and 1 B down per ray: the rays' two
+// staging slots, then the two slots of segment ends.
 int rt_occluded_rays(rt_scene* s, int32_t mode, const rt_ray* rays, const double* t_max, int64_t n, uint8_t* occluded_out)
 {
     bool empty;
     int rc = check_query(s, mode, rays, n, occluded_out, "rt_occluded_rays", &empty);
     if (rc != RT_OK || empty) return rc;
-    int64_t chunk = kQueryChunk;
-    if (const char* e = getenv("RTCORE_QUERY_CHUNK")) chunk = std::max<int64_t>(1, std::min<int64_t>(kQueryChunk, atoll(e)));
-    chunk = std::min(chunk, n);
     if (mode == RT_QUERY_EXACT) {
         rc = ensure_ref_bvh(s);
         if (rc != RT_OK) return rc;
     }
-    HIP_TRY(hipSetDevice(s->device));
-    if (!s->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
-    HIP_TRY(hipStreamSynchronize(s->copy_stream)); // (copies a failed call left behind: see rt_render_tile)
-    const size_t C = (size_t)chunk;
-    HIP_TRY(s->query_rays.reserve(2 * C));
-    HIP_TRY(s->occluded_out.reserve(2 * C));
-    if (t_max) HIP_TRY(s->occluded_t_max.reserve(2 * C));
-    const size_t rays_at = (2 * C + 63) & ~(size_t)63;
-    HIP_TRY(s->stage.reserve(rays_at + 2 * C * (sizeof(rt_ray) + sizeof(double))));
-    rt_ray* stage_rays = reinterpret_cast<rt_ray*>(s->stage.p + rays_at);
-    double* stage_t = reinterpret_cast<double*>(stage_rays + 2 * C);
-    for (int j = 0; j < 2; j++) {
-        if (!s->query_up_ev[j]) HIP_TRY(hipEventCreateWithFlags(&s->query_up_ev[j], hipEventDisableTiming));
-        if (!s->band_ev[j]) HIP_TRY(hipEventCreateWithFlags(&s->band_ev[j], hipEventDisableTiming));
-    }
-    hipStream_t st = s->stream;
-    if (s->any_op && st != s->last_stream) HIP_TRY(hipStreamWaitEvent(st, s->done_ev, 0));
-    const int64_t K = (n + chunk - 1) / chunk;
-    auto count = [&](int64_t k) { return (size_t)std::min(chunk, n - k * chunk); };
-    auto upload = [&](int64_t k) -> int {
-        const size_t m = count(k), slot = (size_t)(k & 1) * C;
-        const rt_ray* src = rays + k * chunk;
-        const double* src_t = t_max ? t_max + k * chunk : nullptr;
+    rt_ray* stage_rays = nullptr;
+    double* stage_t = nullptr;
+    std::atomic<bool> overflow{false};
+    ChunkJob job{n, kQueryChunk, 0, 1, sizeof(rt_ray) + sizeof(double), /*one_piece*/ true, /*count_rays*/ false};
+    job.reserve = [&](size_t C, unsigned char* up, const void*& d_down) -> int {
+        HIP_TRY(s->query_rays.reserve(2 * C));
+        HIP_TRY(s->occluded_out.reserve(2 * C));
+        if (t_max) HIP_TRY(s->occluded_t_max.reserve(2 * C));
+        stage_rays = reinterpret_cast<rt_ray*>(up);
+        stage_t = reinterpret_cast<double*>(stage_rays + 2 * C);
+        d_down = s->occluded_out.p;
+        return RT_OK;
+    };
+    job.upload = [&](int64_t, size_t first, size_t m, size_t slot) -> int {
+        const rt_ray* src = rays + first;
+        const double* src_t = t_max ? t_max + first : nullptr;
         parallel_ranges(m, 65536, [&](size_t a, size_t b) {
             std::memcpy(stage_rays + slot + a, src + a, (b - a) * sizeof(rt_ray));
             if (src_t) std::memcpy(stage_t + slot + a, src_t + a, (b - a) * sizeof(double));
@@ -340,44 +284,17 @@ int rt_occluded_rays(rt_scene* s, int32_t mode, const rt_ray* rays, const double
         if (src_t)
             HIP_TRY(hipMemcpyAsync(s->occluded_t_max.p + slot, stage_t + slot, m * sizeof(double), hipMemcpyHostToDevice,
                                    s->copy_stream));
-        HIP_TRY(hipEventRecord(s->query_up_ev[k & 1], s->copy_stream));
         return RT_OK;
     };
-    std::atomic<bool> overflow{false};
-    CopyPlan plans[2];
-    auto consume = [&](int64_t k) -> int {
-        const size_t slot = (size_t)(k & 1) * C;
-        uint8_t* dst = occluded_out + k * chunk;
-        return consume_copies(s, plans[k & 1], [&](const unsigned char* stage, size_t a, size_t b) {
-            std::memcpy(dst + (a - slot), stage + a, b - a);
-            if (mode == RT_QUERY_EXACT && std::memchr(stage + a, 255, b - a)) overflow = true;
-        });
+    job.launch = [&](int64_t, size_t, size_t m, size_t slot, hipStream_t st) {
+        return launch_segments(s, mode, s->query_rays.p + slot, t_max ? s->occluded_t_max.p + slot : nullptr, (unsigned)m,
+                               s->occluded_out.p + slot, st);
     };
-    rc = upload(0);
-    if (rc != RT_OK) return rc;
-    for (int64_t k = 0; k < K; k++) {
-        const size_t m = count(k), slot = (size_t)(k & 1) * C;
-        HIP_TRY(hipStreamWaitEvent(st, s->query_up_ev[k & 1], 0));
-        rc = launch_segments(s, mode, s->query_rays.p + slot, t_max ? s->occluded_t_max.p + slot : nullptr, (unsigned)m,
-                             s->occluded_out.p + slot, st);
-        if (rc != RT_OK) return rc;
-        HIP_TRY(hipEventRecord(s->band_ev[k & 1], st));
-        if (k >= 1) {
-            rc = consume(k - 1);
-            if (rc != RT_OK) return rc;
-        }
-        if (k + 1 < K) {
-            rc = upload(k + 1);
-            if (rc != RT_OK) return rc;
-        }
-        HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->band_ev[k & 1], 0));
-        plans[k & 1] = CopyPlan{};
-        rc = queue_copy(s, plans[k & 1], s->occluded_out.p, slot, slot + m, 1, 1, s->copy_stream);
-        if (rc != RT_OK) return rc;
-    }
-    rc = end_op(s, st);
-    if (rc != RT_OK) return rc;
-    rc = consume(K - 1);
+    job.consume = [&](const unsigned char* stage, size_t a, size_t b, size_t first, size_t slot) {
+        std::memcpy(occluded_out + first + (a - slot), stage + a, b - a);
+        if (mode == RT_QUERY_EXACT && std::memchr(stage + a, 255, b - a)) overflow = true;
+    };
+    rc = run_chunks(s, job);
     if (rc != RT_OK) return rc;
     if (overflow) {
         set_error("rt_occluded_rays: the reference BVH is deeper than the exact kernel's traversal stack");

@@ -3,7 +3,6 @@
 // array of records, added into per-entry accumulators with rt_render_pixels' moments.  The launch is
 // the three entry points' own (run_rays, api_render_rays.hip) with an index list in the launch record
 // (PathParams::index_list, refill's list_entry); the fold is rt_render_pixels' (accumulate_list_kernel).
-#include <cstdlib>
 #include <cstring>
 
 #include "rt_scene.h"
@@ -11,8 +10,6 @@
 static_assert(sizeof(rt_surfel) == sizeof(rt_ray) && sizeof(rt_beam) == 3 * sizeof(rt_ray), "records in rt_ray units");
 
 namespace {
-
-constexpr uint64_t kChunkItems = 1ull << 26; // most work items of one chunk: 1 GiB of 16-B partials (rt_render_rays')
 
 // The three kinds as the existing entry points describe them (record size, host chunk, name).
 bool list_kind(int32_t kind, int32_t gather_mode, RenderList* out)
@@ -93,14 +90,14 @@ int rt_render_list_device(rt_scene* s, int32_t kind, int32_t gather_mode, const 
     return end_op(s, st);
 }
 
-// rt_render_rays' pipeline (render_list_host) with the listed records gathered on the host: chunk k is
-// the list positions [k chunk, ..); their records go into the chunk's staging slot in list order and
-// their entry numbers beside them, both up to device slot k & 1 on copy_stream; the launch reads the
-// record at the list position and keys the stream by the entry (PathParams::list_gathered), so an
-// entry's samples do not depend on the chunking; one PixelRec per list position comes back and the host
-// pool adds it at the entry (no entry is named twice, so the pool's ranges write disjoint elements).
+// The chunk pipeline (run_chunks) with the listed records gathered on the host: chunk k is the list
+// positions [k C, ..); their records go into the chunk's staging slot in list order and their entry
+// numbers beside them, both up to device slot k & 1; the launch reads the record at the list position
+// and keys the stream by the entry (PathParams::list_gathered), so an entry's samples do not depend on
+// the chunking; one PixelRec per list position comes back and the host pool adds it at the entry (no
+// entry is named twice, so the pool's ranges write disjoint elements).
 // Without an index list the chunk is a run of consecutive entries and needs no list on the device: the
-// launch is rt_render_rays' own, keyed from stream_base + k chunk.
+// launch is rt_render_rays' own, keyed from stream_base + k C.
 int rt_render_list(rt_scene* s, int32_t kind, int32_t gather_mode, const void* records, int64_t n_records,
                    const uint32_t* index, int64_t n, int32_t spp, uint64_t seed, uint64_t sample_base, uint64_t stream_base,
                    rt_color* sum_rgb, uint32_t* samples, uint32_t* misses, double* q, uint32_t* batches, uint64_t* rays_out)
@@ -121,40 +118,24 @@ int rt_render_list(rt_scene* s, int32_t kind, int32_t gather_mode, const void* r
     const int kernel = s->variant >> 1;
     const size_t R = what.rec_bytes / sizeof(rt_ray);
     const rt_ray* recs_in = static_cast<const rt_ray*>(records);
-    int64_t chunk = what.chunk;
-    if (const char* e = getenv("RTCORE_QUERY_CHUNK")) chunk = std::max<int64_t>(1, std::min<int64_t>(what.chunk, atoll(e)));
-    // a chunk's partials stay below kChunkItems items (whole blocks of 64 entries), whatever spp is
-    const PathParams probe = make_params_rays(kernel, 64, spp, seed, sample_base, stream_base);
-    const int64_t fit = (int64_t)(kChunkItems / ((uint64_t)probe.n_chunks * 64u)) * 64;
+    const int64_t fit = chunk_fit(make_params_rays(kernel, 64, spp, seed, sample_base, stream_base));
     if (fit < 64) {
         set_error("rt_render_list: spp too large for one launch; render it in several calls (sample_base)");
         return RT_ERR_ARG;
     }
-    chunk = std::min(std::min(chunk, fit), n);
-    HIP_TRY(hipSetDevice(s->device));
-    if (!s->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
-    HIP_TRY(hipStreamSynchronize(s->copy_stream)); // (copies a failed call left behind: see rt_render_tile)
-    const size_t C = (size_t)chunk;
-    HIP_TRY(s->query_rays.reserve(2 * C * R));
-    HIP_TRY(s->pixel_list.reserve(2 * C));
-    HIP_TRY(s->pixel_recs.reserve(2 * C));
-    // pinned staging: the two record slots (at the offsets queue_copy gives them), the two slots of the
-    // caller's records, the two list slots
-    HIP_TRY(s->stage.reserve(2 * C * (sizeof(PixelRec) + what.rec_bytes + sizeof(uint32_t))));
-    HIP_TRY(s->rays_h.reserve(1));
-    rt_ray* stage_recs = reinterpret_cast<rt_ray*>(s->stage.p + 2 * C * sizeof(PixelRec));
-    uint32_t* stage_list = reinterpret_cast<uint32_t*>(s->stage.p + 2 * C * (sizeof(PixelRec) + what.rec_bytes));
-    for (int j = 0; j < 2; j++) {
-        if (!s->query_up_ev[j]) HIP_TRY(hipEventCreateWithFlags(&s->query_up_ev[j], hipEventDisableTiming));
-        if (!s->band_ev[j]) HIP_TRY(hipEventCreateWithFlags(&s->band_ev[j], hipEventDisableTiming));
-    }
-    hipStream_t st = s->stream;
-    if (s->any_op && st != s->last_stream) HIP_TRY(hipStreamWaitEvent(st, s->done_ev, 0));
-    HIP_TRY(hipMemsetAsync(s->rays.p, 0, sizeof(unsigned long long), st));
-    const int64_t K = (n + chunk - 1) / chunk;
-    auto count = [&](int64_t k) { return (size_t)std::min(chunk, n - k * chunk); };
-    auto upload = [&](int64_t k) -> int {
-        const size_t m = count(k), slot = (size_t)(k & 1) * C, first = (size_t)(k * chunk);
+    rt_ray* stage_recs = nullptr;
+    uint32_t* stage_list = nullptr;
+    ChunkJob job{n, what.chunk, fit, sizeof(PixelRec), what.rec_bytes + sizeof(uint32_t), /*one_piece*/ false, /*count_rays*/ true};
+    job.reserve = [&](size_t C, unsigned char* up, const void*& d_down) -> int {
+        HIP_TRY(s->query_rays.reserve(2 * C * R));
+        HIP_TRY(s->pixel_list.reserve(2 * C));
+        HIP_TRY(s->pixel_recs.reserve(2 * C));
+        stage_recs = reinterpret_cast<rt_ray*>(up); // the two slots of the caller's records, then the two list slots
+        stage_list = reinterpret_cast<uint32_t*>(stage_recs + 2 * C * R);
+        d_down = s->pixel_recs.p;
+        return RT_OK;
+    };
+    job.upload = [&](int64_t, size_t first, size_t m, size_t slot) -> int {
         rt_ray* dst = stage_recs + slot * R;
         if (index) {
             parallel_ranges(m, 16384, [&](size_t a, size_t b) {
@@ -169,64 +150,34 @@ int rt_render_list(rt_scene* s, int32_t kind, int32_t gather_mode, const void* r
             parallel_ranges(m * R, 65536, [&](size_t a, size_t b) { std::memcpy(dst + a, src + a, (b - a) * sizeof(rt_ray)); });
         }
         HIP_TRY(hipMemcpyAsync(s->query_rays.p + slot * R, dst, m * R * sizeof(rt_ray), hipMemcpyHostToDevice, s->copy_stream));
-        HIP_TRY(hipEventRecord(s->query_up_ev[k & 1], s->copy_stream));
         return RT_OK;
     };
-    CopyPlan plans[2];
-    auto consume = [&](int64_t k) -> int {
-        const size_t slot = (size_t)(k & 1) * C, first = (size_t)(k * chunk);
-        return consume_copies(s, plans[k & 1], [&](const unsigned char* stage, size_t a, size_t b) {
-            const PixelRec* r = reinterpret_cast<const PixelRec*>(stage);
-            for (size_t i = a; i < b; i++) {
-                const size_t pos = first + (i - slot), o = index ? (size_t)index[pos] : pos;
-                sum_rgb[o].r += r[i].r;
-                sum_rgb[o].g += r[i].g;
-                sum_rgb[o].b += r[i].b;
-                samples[o] += r[i].samples;
-                misses[o] += r[i].misses;
-                if (q) {
-                    q[o] += r[i].q;
-                    batches[o] += r[i].batches;
-                }
-            }
-        });
-    };
-    rc = upload(0);
-    if (rc != RT_OK) return rc;
-    for (int64_t k = 0; k < K; k++) {
-        const size_t m = count(k), slot = (size_t)(k & 1) * C;
-        HIP_TRY(hipStreamWaitEvent(st, s->query_up_ev[k & 1], 0));
+    job.launch = [&](int64_t, size_t first, size_t m, size_t slot, hipStream_t st) -> int {
         PathParams p = make_params_rays(kernel, (int64_t)m, spp, seed, sample_base,
-                                        index ? stream_base : stream_base + (uint64_t)(k * chunk));
+                                        index ? stream_base : stream_base + (uint64_t)first);
         const uint32_t* d_index = index ? s->pixel_list.p + slot : nullptr;
-        rc = run_rays(s, what, p, s->query_rays.p + slot * R, s->rays.p, st, d_index, (unsigned)n_records, true);
-        if (rc != RT_OK) return rc;
+        const int lrc = run_rays(s, what, p, s->query_rays.p + slot * R, s->rays.p, st, d_index, (unsigned)n_records, true);
+        if (lrc != RT_OK) return lrc;
         // (from zero, per list position: the fold takes no entry numbers, every entry is inside)
         HIP_TRY(launch_accumulate_list(p, nullptr, m, nullptr, nullptr, nullptr, nullptr, nullptr, 0, s->pixel_recs.p + slot, st));
-        HIP_TRY(hipEventRecord(s->band_ev[k & 1], st));
-        if (k >= 1) {
-            rc = consume(k - 1);
-            if (rc != RT_OK) return rc;
+        return RT_OK;
+    };
+    job.consume = [&](const unsigned char* stage, size_t a, size_t b, size_t first, size_t slot) {
+        const PixelRec* r = reinterpret_cast<const PixelRec*>(stage);
+        for (size_t i = a; i < b; i++) {
+            const size_t pos = first + (i - slot), o = index ? (size_t)index[pos] : pos;
+            sum_rgb[o].r += r[i].r;
+            sum_rgb[o].g += r[i].g;
+            sum_rgb[o].b += r[i].b;
+            samples[o] += r[i].samples;
+            misses[o] += r[i].misses;
+            if (q) {
+                q[o] += r[i].q;
+                batches[o] += r[i].batches;
+            }
         }
-        if (k + 1 < K) {
-            rc = upload(k + 1);
-            if (rc != RT_OK) return rc;
-        }
-        HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->band_ev[k & 1], 0));
-        if (k + 1 == K) // (before the last records, so it has landed when they have)
-            HIP_TRY(hipMemcpyAsync(s->rays_h.p, s->rays.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, s->copy_stream));
-        plans[k & 1] = CopyPlan{};
-        rc = queue_copy(s, plans[k & 1], s->pixel_recs.p, slot, slot + m, sizeof(PixelRec),
-                        (int)std::max<size_t>(1, std::min<size_t>(rt_scene::kCopyChunks, (m * sizeof(PixelRec)) >> 20)),
-                        s->copy_stream);
-        if (rc != RT_OK) return rc;
-    }
-    rc = end_op(s, st);
-    if (rc != RT_OK) return rc;
-    rc = consume(K - 1);
-    if (rc != RT_OK) return rc;
-    if (rays_out) *rays_out += s->rays_h.p[0];
-    return RT_OK;
+    };
+    return run_chunks(s, job, rays_out);
 }
 
 } // extern "C"

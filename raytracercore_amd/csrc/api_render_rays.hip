@@ -12,8 +12,7 @@
 
 namespace {
 
-constexpr int64_t kRaysChunk = 1 << 19;      // rays of one chunk of rt_render_rays (rt_query_rays' size and variable)
-constexpr uint64_t kChunkItems = 1ull << 26; // most work items of one chunk: 1 GiB of 16-B partials
+constexpr int64_t kRaysChunk = 1 << 19; // rays of one chunk of rt_render_rays (rt_query_rays' size and variable)
 constexpr RenderList kRays = {ITEMS_RAYS, sizeof(rt_ray), kRaysChunk, "rays"};
 
 // Argument and state checks shared by both entry points; RT_OK with *empty set for n == 0.
@@ -43,19 +42,16 @@ int check_render_rays(rt_scene* s, const void* rays, int64_t n, int32_t spp, con
 
 namespace rtc {
 
-// The path kernel of the scene's variant, the list's instance (RAYS, BEAMS or SURFELS), over the p.n_rays
-// records at d_list, and nothing after it: the caller folds p's partials.  run_path without what
-// rt_render_rays leaves alone: no timing slot, no counters, no ray log, never the scene-specialised kernel.
-// d_index (rt_render_list; null for the three entry points here): the launch's index list over n_records
-// records, gathered as PathParams::list_gathered says.
-int run_rays(rt_scene* s, const RenderList& kind, PathParams& p, const void* d_list, unsigned long long* d_count,
-             hipStream_t stream, const uint32_t* d_index, unsigned n_records, bool gathered)
+// The path kernel of the scene's variant, src's instance, and nothing after it: the caller folds p's
+// partials.  run_path without what the list renders leave alone: no timing slot, no counters, no ray log,
+// never the scene-specialised kernel, no block cull.
+int run_items(rt_scene* s, ItemSource src, const char* what, PathParams& p, unsigned long long* d_count, hipStream_t stream)
 {
     const size_t need = (size_t)p.n_chunks * (size_t)p.n_pad;
     uint64_t tickets = 0;
     for (int g = 0; g < p.n_split; g++) tickets += p.split_tickets[g];
     if (need > 0xF0000000ull || tickets > need / 64) { // (run_path's bound; the entry points check n first)
-        set_error(std::string("rt_render_") + kind.what + ": n x spp too large for one launch");
+        set_error(std::string("rt_render_") + what + ": n x spp too large for one launch");
         return RT_ERR_ARG;
     }
     HIP_TRY(s->partial.reserve(need));
@@ -63,27 +59,32 @@ int run_rays(rt_scene* s, const RenderList& kind, PathParams& p, const void* d_l
     p.partial = s->partial.p;
     p.counter = s->counter.p;
     p.rays = d_count;
-    p.ray_list = reinterpret_cast<const double2*>(d_list); // (beam_list is the same storage)
-    p.gather_mode = kind.gather_mode;                      // (start_rows' word: 0 but for the surfels)
-    p.index_list = d_index;                                // (the cull's word: a list launch has none)
-    p.n_records = d_index ? n_records : 0u;
-    p.list_gathered = d_index && gathered ? 1 : 0;
-    if (s->any_op && stream != s->last_stream) HIP_TRY(hipStreamWaitEvent(stream, s->done_ev, 0));
+    HIP_TRY(wait_last_op(s, stream));
     HIP_TRY(hipMemsetAsync(p.counter, 0, sizeof(unsigned int) * kSplitStride * p.n_split, stream));
     const size_t dyn = path_dyn_lds(s->dev, s->variant);
-    const bool beams = kind.src == ITEMS_BEAMS, surfels = kind.src == ITEMS_SURFELS;
-    int& cached_variant = beams ? s->beams_variant : surfels ? s->surfels_variant : s->rays_variant;
-    int& blocks_per_cu = beams ? s->beams_blocks_per_cu : surfels ? s->surfels_blocks_per_cu : s->rays_blocks_per_cu;
-    if (cached_variant != s->variant) {
-        blocks_per_cu = path_blocks_per_cu(s->variant, dyn, false, s->dev.n_vn > 0, kind.src);
-        cached_variant = s->variant;
+    int& blocks_per_cu = s->items_blocks_per_cu[src];
+    if (s->items_variant[src] != s->variant) {
+        blocks_per_cu = path_blocks_per_cu(s->variant, dyn, false, s->dev.n_vn > 0, src);
+        s->items_variant[src] = s->variant;
     }
     int grid = s->n_cu * blocks_per_cu;
+    if (src == ITEMS_PIXELS) p.pkeys = nullptr;
     if ((s->variant >> 1) < 2) { // a small brute-force launch runs fewer blocks per CU (see run_path)
         const double samples = (double)p.n_rays * (double)p.spp;
         int cap = (int)std::ceil(samples / ((double)s->n_cu * 256.0 * 6.0));
         if (const char* e = getenv("RTCORE_GRID_BPC")) cap = atoi(e);
         grid = s->n_cu * std::min(blocks_per_cu, std::max(1, cap));
+        // the scene's pixel-key table, as a tile launch reads it (run_path builds it the same way)
+        static const bool pkeys_on = !(getenv("RTCORE_PIXEL_KEYS") && getenv("RTCORE_PIXEL_KEYS")[0] == '0');
+        if (src == ITEMS_PIXELS && pkeys_on) {
+            if (!s->pkeys_valid || s->pkeys_seed != p.seed) {
+                HIP_TRY(s->pkeys.reserve((size_t)s->params.width * (size_t)s->params.height));
+                HIP_TRY(launch_pixel_keys(p.seed_key, s->params.width, s->params.height, s->pkeys.p, stream));
+                s->pkeys_valid = true;
+                s->pkeys_seed = p.seed;
+            }
+            p.pkeys = s->pkeys.p;
+        }
     } else {
         HIP_TRY(s->stack_ovf.reserve((size_t)grid * 256 * kStackOverflow));
         p.stack_ovf = s->stack_ovf.p;
@@ -92,8 +93,21 @@ int run_rays(rt_scene* s, const RenderList& kind, PathParams& p, const void* d_l
     const PathParams* pa = nullptr;
     const int rc = upload_params(s, p, stream, &pa);
     if (rc != RT_OK) return rc;
-    HIP_TRY(launch_path(s->dev, s->camf_d.p, pa, s->variant, grid, stream, false, kind.src));
+    HIP_TRY(launch_path(s->dev, s->camf_d.p, pa, s->variant, grid, stream, false, src));
     return RT_OK;
+}
+
+// d_index (rt_render_list; null for the three entry points here): the launch's index list over n_records
+// records, gathered as PathParams::list_gathered says.
+int run_rays(rt_scene* s, const RenderList& kind, PathParams& p, const void* d_list, unsigned long long* d_count,
+             hipStream_t stream, const uint32_t* d_index, unsigned n_records, bool gathered)
+{
+    p.ray_list = reinterpret_cast<const double2*>(d_list); // (beam_list is the same storage)
+    p.gather_mode = kind.gather_mode;                      // (start_rows' word: 0 but for the surfels)
+    p.index_list = d_index;                                // (the cull's word: a list launch has none)
+    p.n_records = d_index ? n_records : 0u;
+    p.list_gathered = d_index && gathered ? 1 : 0;
+    return run_items(s, kind.src, kind.what, p, d_count, stream);
 }
 
 int render_list_device(rt_scene* s, const RenderList& kind, const char* name, const void* d_list, int64_t n, int32_t spp,
@@ -119,11 +133,9 @@ int render_list_device(rt_scene* s, const RenderList& kind, const char* name, co
     return end_op(s, st);
 }
 
-// rt_query_rays' pipeline with a path launch and its fold in the kernel's place: chunk k's rays go
-// through pinned staging to device slot k & 1 on copy_stream, its launch runs on the scene's stream once
-// they have landed, and its records (one TileRec per ray, folded from zero) come back on copy_stream
-// into the staging slot the host pool then adds into the caller's arrays.  The partials are one
-// buffer: launch k + 1 follows fold k on the scene's stream.  A record of the list takes R =
+// The chunk pipeline (run_chunks) with a path launch and its fold as the chunk's kernels: one TileRec per
+// record comes down, folded from zero, and the host pool adds it into the caller's arrays.  The partials
+// are one buffer: launch k + 1 follows fold k on the scene's stream.  A record of the list takes R =
 // rec_bytes / sizeof(rt_ray) entries of query_rays and of the staging's ray slots (a beam: 3).
 int render_list_host(rt_scene* s, const RenderList& kind, const char* name, const void* list, int64_t n, int32_t spp,
                      uint64_t seed, uint64_t sample_base, uint64_t stream_base, rt_color* sum_rgb, uint32_t* samples,
@@ -135,92 +147,48 @@ int render_list_host(rt_scene* s, const RenderList& kind, const char* name, cons
     const int kernel = s->variant >> 1;
     const size_t R = kind.rec_bytes / sizeof(rt_ray);
     const rt_ray* rays = static_cast<const rt_ray*>(list);
-    int64_t chunk = kind.chunk;
-    if (const char* e = getenv("RTCORE_QUERY_CHUNK")) chunk = std::max<int64_t>(1, std::min<int64_t>(kind.chunk, atoll(e)));
-    // a chunk's partials stay below kChunkItems items (whole blocks of 64 rays), whatever spp is
-    const PathParams probe = make_params_rays(kernel, 64, spp, seed, sample_base, stream_base);
-    const int64_t fit = (int64_t)(kChunkItems / ((uint64_t)probe.n_chunks * 64u)) * 64;
+    const int64_t fit = chunk_fit(make_params_rays(kernel, 64, spp, seed, sample_base, stream_base));
     if (fit < 64) {
         set_error(std::string(name) + ": spp too large for one launch; render it in several calls (sample_base)");
         return RT_ERR_ARG;
     }
-    chunk = std::min(std::min(chunk, fit), n);
-    HIP_TRY(hipSetDevice(s->device));
-    if (!s->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
-    HIP_TRY(hipStreamSynchronize(s->copy_stream)); // (copies a failed call left behind: see rt_render_tile)
-    const size_t C = (size_t)chunk;
-    HIP_TRY(s->query_rays.reserve(2 * C * R));
-    HIP_TRY(s->render_rays_recs.reserve(2 * C));
-    // pinned staging: the two record slots (at the offsets queue_copy gives them), then the two ray slots
-    HIP_TRY(s->stage.reserve(2 * C * (sizeof(TileRec) + kind.rec_bytes)));
-    HIP_TRY(s->rays_h.reserve(1));
-    rt_ray* stage_rays = reinterpret_cast<rt_ray*>(s->stage.p + 2 * C * sizeof(TileRec));
-    for (int j = 0; j < 2; j++) {
-        if (!s->query_up_ev[j]) HIP_TRY(hipEventCreateWithFlags(&s->query_up_ev[j], hipEventDisableTiming));
-        if (!s->band_ev[j]) HIP_TRY(hipEventCreateWithFlags(&s->band_ev[j], hipEventDisableTiming));
-    }
-    hipStream_t st = s->stream;
-    if (s->any_op && st != s->last_stream) HIP_TRY(hipStreamWaitEvent(st, s->done_ev, 0));
-    HIP_TRY(hipMemsetAsync(s->rays.p, 0, sizeof(unsigned long long), st));
-    const int64_t K = (n + chunk - 1) / chunk;
-    auto count = [&](int64_t k) { return (size_t)std::min(chunk, n - k * chunk); };
-    auto upload = [&](int64_t k) -> int {
-        const size_t m = count(k) * R, slot = (size_t)(k & 1) * C * R; // in rt_ray entries
-        const rt_ray* src = rays + (size_t)(k * chunk) * R;
-        parallel_ranges(m, 65536, [&](size_t a, size_t b) { std::memcpy(stage_rays + slot + a, src + a, (b - a) * sizeof(rt_ray)); });
-        HIP_TRY(hipMemcpyAsync(s->query_rays.p + slot, stage_rays + slot, m * sizeof(rt_ray), hipMemcpyHostToDevice,
-                               s->copy_stream));
-        HIP_TRY(hipEventRecord(s->query_up_ev[k & 1], s->copy_stream));
+    rt_ray* stage_rays = nullptr;
+    ChunkJob job{n, kind.chunk, fit, sizeof(TileRec), kind.rec_bytes, /*one_piece*/ false, /*count_rays*/ true};
+    job.reserve = [&](size_t C, unsigned char* up, const void*& d_down) -> int {
+        HIP_TRY(s->query_rays.reserve(2 * C * R));
+        HIP_TRY(s->render_rays_recs.reserve(2 * C));
+        stage_rays = reinterpret_cast<rt_ray*>(up);
+        d_down = s->render_rays_recs.p;
         return RT_OK;
     };
-    CopyPlan plans[2];
-    auto consume = [&](int64_t k) -> int {
-        const size_t slot = (size_t)(k & 1) * C, first = (size_t)(k * chunk);
-        return consume_copies(s, plans[k & 1], [&](const unsigned char* stage, size_t a, size_t b) {
-            const TileRec* r = reinterpret_cast<const TileRec*>(stage);
-            for (size_t i = a; i < b; i++) {
-                const size_t o = first + (i - slot);
-                sum_rgb[o].r += r[i].r;
-                sum_rgb[o].g += r[i].g;
-                sum_rgb[o].b += r[i].b;
-                samples[o] += r[i].samples;
-                misses[o] += r[i].misses;
-            }
-        });
+    job.upload = [&](int64_t, size_t first, size_t m, size_t slot) -> int { // (m and slot in rt_ray entries from here)
+        m *= R, slot *= R;
+        const rt_ray* src = rays + first * R;
+        parallel_ranges(m, 65536,
+                        [&](size_t a, size_t b) { std::memcpy(stage_rays + slot + a, src + a, (b - a) * sizeof(rt_ray)); });
+        HIP_TRY(hipMemcpyAsync(s->query_rays.p + slot, stage_rays + slot, m * sizeof(rt_ray), hipMemcpyHostToDevice,
+                               s->copy_stream));
+        return RT_OK;
     };
-    rc = upload(0);
-    if (rc != RT_OK) return rc;
-    for (int64_t k = 0; k < K; k++) {
-        const size_t m = count(k), slot = (size_t)(k & 1) * C;
-        HIP_TRY(hipStreamWaitEvent(st, s->query_up_ev[k & 1], 0));
-        PathParams p = make_params_rays(kernel, (int64_t)m, spp, seed, sample_base, stream_base + (uint64_t)(k * chunk));
-        rc = run_rays(s, kind, p, s->query_rays.p + slot * R, s->rays.p, st, nullptr, 0, false);
-        if (rc != RT_OK) return rc;
+    job.launch = [&](int64_t, size_t first, size_t m, size_t slot, hipStream_t st) -> int {
+        PathParams p = make_params_rays(kernel, (int64_t)m, spp, seed, sample_base, stream_base + (uint64_t)first);
+        const int lrc = run_rays(s, kind, p, s->query_rays.p + slot * R, s->rays.p, st, nullptr, 0, false);
+        if (lrc != RT_OK) return lrc;
         HIP_TRY(launch_accumulate_rays(p, nullptr, nullptr, nullptr, s->render_rays_recs.p + slot, st));
-        HIP_TRY(hipEventRecord(s->band_ev[k & 1], st));
-        if (k >= 1) {
-            rc = consume(k - 1);
-            if (rc != RT_OK) return rc;
+        return RT_OK;
+    };
+    job.consume = [&](const unsigned char* stage, size_t a, size_t b, size_t first, size_t slot) {
+        const TileRec* r = reinterpret_cast<const TileRec*>(stage);
+        for (size_t i = a; i < b; i++) {
+            const size_t o = first + (i - slot);
+            sum_rgb[o].r += r[i].r;
+            sum_rgb[o].g += r[i].g;
+            sum_rgb[o].b += r[i].b;
+            samples[o] += r[i].samples;
+            misses[o] += r[i].misses;
         }
-        if (k + 1 < K) {
-            rc = upload(k + 1);
-            if (rc != RT_OK) return rc;
-        }
-        HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->band_ev[k & 1], 0));
-        if (k + 1 == K) // (before the last records, so it has landed when they have)
-            HIP_TRY(hipMemcpyAsync(s->rays_h.p, s->rays.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, s->copy_stream));
-        plans[k & 1] = CopyPlan{};
-        rc = queue_copy(s, plans[k & 1], s->render_rays_recs.p, slot, slot + m, sizeof(TileRec),
-                        (int)std::max<size_t>(1, std::min<size_t>(rt_scene::kCopyChunks, (m * sizeof(TileRec)) >> 20)),
-                        s->copy_stream);
-        if (rc != RT_OK) return rc;
-    }
-    rc = end_op(s, st);
-    if (rc != RT_OK) return rc;
-    rc = consume(K - 1);
-    if (rc != RT_OK) return rc;
-    if (rays_out) *rays_out += s->rays_h.p[0];
-    return RT_OK;
+    };
+    return run_chunks(s, job, rays_out);
 }
 
 } // namespace rtc

@@ -1,6 +1,6 @@
 // rt_scene.h -- the scene object behind the C ABI and what the API's translation units share
 // (rtcore_api.hip, scene_upload.hip, api_frame.hip, api_debug.hip, api_query.hip, api_select.hip, api_render_rays.hip,
-// api_render_pixels.hip, api_adaptive.hip, api_denoise.hip, api_reproject.hip).
+// api_render_pixels.hip, chunk_pipeline.hip, api_adaptive.hip, api_denoise.hip, api_reproject.hip).
 #pragma once
 #include <algorithm>
 #include <array>
@@ -182,33 +182,22 @@ struct rt_scene {
     std::array<hipEvent_t, kCopyChunks> band_ev{};
     DevBuf<uint32_t> samples, misses;
     DevBuf<int32_t> ids;
-    // rt_query_rays: two chunks of rays and of hits, and the events of the chunks' uploads
+    // the chunked host entries' device slots (run_chunks, below, says which entry uses which) and the
+    // events of the chunks' uploads
     DevBuf<rt_ray> query_rays;
     DevBuf<rt_hit> query_hits;
+    DevBuf<double> occluded_t_max;
+    DevBuf<unsigned char> occluded_out;
+    DevBuf<uint32_t> occluded_counts;
+    DevBuf<TileRec> render_rays_recs;
+    DevBuf<uint32_t> pixel_list;
+    DevBuf<PixelRec> pixel_recs;
     std::array<hipEvent_t, 2> query_up_ev{};
     // rt_primary_hits_device: one chunk of camera rays, made and read on the caller's stream (its own
     // buffer: rt_query_rays fills query_rays from its copy stream)
     DevBuf<rt_ray> primary_rays;
-    // rt_occluded_rays: two chunks of segment ends and of answer bytes (its rays share query_rays and query_up_ev)
-    DevBuf<double> occluded_t_max;
-    DevBuf<unsigned char> occluded_out;
-    // rt_occluded_surfels: two chunks of counts (its surfels share query_rays, its segment ends occluded_t_max)
-    DevBuf<uint32_t> occluded_counts;
-    // rt_render_rays: two chunks of per-ray records (its rays share query_rays and query_up_ev), and
-    // the blocks per CU of the RAYS instance of `rays_variant`
-    DevBuf<TileRec> render_rays_recs;
-    int rays_variant = -1, rays_blocks_per_cu = 1;
-    // rt_render_beams: its beams share query_rays (three rt_ray per beam) and its records
-    // render_rays_recs; the blocks per CU of the BEAMS instance of `beams_variant`
-    int beams_variant = -1, beams_blocks_per_cu = 1;
-    // rt_render_surfels: a surfel has an rt_ray's size and takes its place in query_rays and the staging;
-    // the blocks per CU of the SURFELS instance of `surfels_variant`
-    int surfels_variant = -1, surfels_blocks_per_cu = 1;
-    // rt_render_pixels: two chunks of list entries and of per-entry records, and the blocks per CU of
-    // the PIXELS instance of `pixels_variant`
-    DevBuf<uint32_t> pixel_list;
-    DevBuf<PixelRec> pixel_recs;
-    int pixels_variant = -1, pixels_blocks_per_cu = 1;
+    // run_items: the blocks per CU of each ItemSource's instance of `items_variant`
+    int items_variant[ITEMS_SURFELS + 1] = {-1, -1, -1, -1, -1}, items_blocks_per_cu[ITEMS_SURFELS + 1] = {1, 1, 1, 1, 1};
     // the selection pass (api_select.hip): the caller's item list on the device, and the host-buffer
     // entry points' rays (one chunk) and results
     DevBuf<rt_select_item> select_items;
@@ -333,6 +322,43 @@ int end_op(rt_scene* s, hipStream_t stream);
 int queue_copy(rt_scene* s, CopyPlan& plan, const void* d_src, size_t a, size_t b, size_t rec_bytes, int k,
                hipStream_t stream);
 int consume_copies(rt_scene* s, const CopyPlan& plan, const std::function<void(const unsigned char*, size_t, size_t)>& consume);
+// The scene's scratch (partials, work counter, stack overflow area) is shared: work on another stream than
+// the last operation's waits for its end.
+inline hipError_t wait_last_op(rt_scene* s, hipStream_t st)
+{
+    return s->any_op && st != s->last_stream ? hipStreamWaitEvent(st, s->done_ev, 0) : hipSuccess;
+}
+// chunk_pipeline.hip: the loop of every host entry that takes n of the caller's items (rt_query_rays,
+// rt_occluded_rays, rt_occluded_surfels, rt_render_rays / _beams / _surfels, rt_render_list,
+// rt_render_pixels), in chunks of C = min(largest, RTCORE_QUERY_CHUNK, cap, n) items, two of them resident;
+// the order of its steps is argued at its definition.  An entry says what varies:
+//   reserve(C, up, d_down)             its device buffers for two chunks of C items; it names the one the answers
+//                                      come from, two slots of C x down_bytes, and keeps `up`, its part of the
+//                                      pinned staging (2 C x up_bytes, 64-byte aligned, behind the two answer slots)
+//   upload(k, first, m, slot)          chunk k, items [first, first + m) of the caller's: staged into slot's part of
+//                                      `up` and queued from there to the device, all on copy_stream
+//   launch(k, first, m, slot, st)      everything chunk k needs on the scene's stream, answers into slot
+//   consume(stage, a, b, first, slot)  on the host pool: answer i in [a, b) of the staging is item first + (i - slot)
+// slot = (k & 1) C is the chunk's offset, in items, in every two-chunk buffer.  The buffers are the scene's and
+// shared by size, not by name: every entry's records travel in query_rays (a surfel is an rt_ray, a beam three)
+// and its entry numbers in pixel_list; the segment ends of both occlusion entries in occluded_t_max; the answers
+// in query_hits, occluded_out, occluded_counts, render_rays_recs (rays, beams, surfels) or pixel_recs (pixels,
+// lists).  An entry has consumed its last chunk when it returns, so the next call finds them free.
+struct ChunkJob {
+    int64_t n, largest, cap; // cap 0: none
+    size_t down_bytes, up_bytes;
+    bool one_piece;   // a chunk's answers come down as one copy (else in up to kCopyChunks pieces of at least 1 MB)
+    bool count_rays;  // the render entries: s->rays zeroed before the first chunk and returned after the last
+    std::function<int(size_t, unsigned char*, const void*&)> reserve;
+    std::function<int(int64_t, size_t, size_t, size_t)> upload;
+    std::function<int(int64_t, size_t, size_t, size_t, hipStream_t)> launch;
+    std::function<void(const unsigned char*, size_t, size_t, size_t, size_t)> consume;
+};
+int run_chunks(rt_scene* s, const ChunkJob& job, uint64_t* rays_out = nullptr);
+// The render entries' cap: a chunk's partials stay below 2^26 work items (1 GiB of 16-B partials), in whole
+// blocks of 64 entries, whatever spp is; probe: the entry's launch record for 64 entries.  Below 64: spp is
+// too large for one launch.
+int64_t chunk_fit(const PathParams& probe);
 // api_render_rays.hip: what rt_render_rays, rt_render_beams and rt_render_surfels share, a radiance query
 // over a list of caller's records (rt_ray, rt_beam or rt_surfel) by the src instances of the path
 // kernels.  rec_bytes: one record, a multiple of sizeof(rt_ray); chunk: most records of one chunk of the
@@ -345,7 +371,11 @@ struct RenderList {
     const char* what;
     int gather_mode = 0;
 };
-// The path launch of a list (no fold): kind's instance over the p.n_rays records at d_list; with d_index
+// The launch of an item-list instance of the path kernels (src: RAYS, BEAMS, SURFELS or PIXELS) and nothing
+// after it: the caller has set the instance's own words of p (run_rays; pixel_list and a null cull) and
+// folds p's partials.  what: the entry's items in messages ("rt_render_<what>: ...").
+int run_items(rt_scene* s, ItemSource src, const char* what, PathParams& p, unsigned long long* d_count, hipStream_t stream);
+// run_items for a list of records: kind's instance over the p.n_rays records at d_list; with d_index
 // (rt_render_list, api_render_list.hip) item j is entry d_index[j] of n_records records, whose record lies
 // at list position j (gathered) or at its entry number.
 int run_rays(rt_scene* s, const RenderList& kind, PathParams& p, const void* d_list, unsigned long long* d_count,
@@ -357,7 +387,7 @@ int render_list_host(rt_scene* s, const RenderList& kind, const char* name, cons
                      uint64_t seed, uint64_t sample_base, uint64_t stream_base, rt_color* sum_rgb, uint32_t* samples,
                      uint32_t* misses, uint64_t* rays_out);
 // api_query.hip: what rt_query_rays, rt_occluded_rays and rt_occluded_surfels (api_occluded_surfels.hip) share.
-constexpr int64_t kQueryChunk = 1 << 19;     // rays of one chunk of rt_query_rays; two chunks are resident
+constexpr int64_t kQueryChunk = 1 << 19;     // most items of one chunk of a host entry (run_chunks; beams: 2^18)
 constexpr int64_t kQueryLaunchMax = 1 << 30; // rays of one launch (32-bit ray indices and dispenser)
 // The generic kernel of the scene's traversal mode (path_variant's numbering).
 int query_kernel(const rt_scene* s);
