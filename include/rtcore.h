@@ -55,7 +55,8 @@ extern "C" {
                                    rt_surfel, rt_gather_mode, rt_render_surfels, rt_render_surfels_device and
                                    rt_debug_surfel_rays_device, and rt_list_kind, rt_render_list and
                                    rt_render_list_device, and rt_occluded_surfels and
-                                   rt_occluded_surfels_device */
+                                   rt_occluded_surfels_device, and rt_probe_sh, rt_render_probes,
+                                   rt_render_probes_device, rt_debug_sh_basis and rt_debug_probe_fold */
 
 typedef enum rt_status {
     RT_OK = 0,
@@ -858,6 +859,74 @@ int rt_render_surfels_device(rt_scene* scene, int32_t mode, const rt_surfel* d_s
    n > 0, n < 0, spp <= 0) / RT_ERR_HIP. */
 int rt_debug_surfel_rays_device(int32_t mode, const rt_surfel* d_surfels, int64_t n, int32_t spp, uint64_t seed,
                                 uint64_t sample_base, uint64_t stream_base, rt_ray* d_rays_out, void* stream);
+
+/*
+ * Light probes: what arrives at a point, kept as a function of direction.  An RT_GATHER_SPHERE gather
+ * returns one colour per point, the mean over the sphere; rt_render_probes returns, per point, the sums of
+ * its SPHERE gather samples weighted by the nine L2 real spherical-harmonic basis functions of each
+ * sample's direction, and the same projection of the directions that met nothing (which never leave the
+ * device otherwise).  From them a diffuse receiver's irradiance for any normal is a nine-term dot product.
+ *
+ * The record.  A probe is an rt_surfel: position is the point, normal only fixes the frame in which the
+ * sphere's directions are drawn (RT_GATHER_SPHERE's rule; the mode is fixed).  It is invalid exactly when
+ * rt_render_surfels calls it invalid.
+ * Sampling (normative).  Sample k of probe i is sample k of surfel i of rt_render_surfels in
+ * RT_GATHER_SPHERE: its ray is the one rt_debug_surfel_rays_device reports, and its fp32 colour col and
+ * whether it is a primary miss are what rt_render_rays gives for that ray at spp = 1, sample_base + k and
+ * stream_base + i.
+ * Basis (normative).  (x, y, z) = the reported fp32 direction widened to fp64; fp64 throughout, every
+ * operation rounded on its own, no fused multiply-add; the constants are these decimal literals:
+ *   K0 = 0.28209479177387814   K1 = 0.48860251190291992   K2 = 1.0925484305920792
+ *   K3 = 0.31539156525252005   K4 = 0.54627421529603959
+ *   Y0 = K0        Y1 = K1*y      Y2 = K1*z                  Y3 = K1*x       Y4 = (K2*x)*y
+ *   Y5 = (K2*y)*z  Y6 = K3*((3*z)*z - 1)                     Y7 = (K2*x)*z   Y8 = K4*(x*x - y*y)
+ * Accumulation (normative).  Everything is added to what the arrays hold; per probe in sample order
+ * k = 0 .. spp - 1:
+ *   a hit:          c[l][j] = c[l][j] + ((double)col_j * Y_l) for j = 0, 1, 2 (r, g, b), the product rounded,
+ *                   then the sum; samples += 1
+ *   a primary miss: c[l][3] = c[l][3] + Y_l; misses += 1
+ *   an invalid probe: misses += spp and nothing else (its rays are all zeros).
+ * So c[.][3] is the projection of the probe's view of the sky, and the probe's radiance coefficients are
+ *   L[l][ch] = 4 pi / N * (c[l][ch] + c[l][3] * ambient_ch),   N = samples + misses.
+ * The ray count follows rt_render_rays.
+ * What is promised (normative):
+ *   1. The result equals rt_debug_probe_fold over the reported rays and the per-sample rt_render_rays
+ *      results, and a replay of the formulas above, bit for bit.
+ *   2. A probe's result depends on (seed, stream_base + i, the sample indices, the record, the traversal
+ *      mode) only: not on n, on list position, on the host entry's chunking or on the stream.
+ *   3. One call of a + b samples equals a call of a samples followed by a call of b samples at
+ *      sample_base + a into the same arrays, bit for bit (every work item is one sample at any spp; the
+ *      scalar gathers, whose samples per item depend on spp, cannot promise this).
+ * Everything else is rt_render_surfels' contract: always the generic kernels; RT_ERR_STATE on a BVH2 scene;
+ * the argument errors, and n == 0 returning RT_OK and touching nothing; the counters of rt_scene_get_stats,
+ * an armed rt_debug_ray_log, rt_kernel_times and the scene-specialised kernels left as they were; no
+ * camera needed; rt_render_probes_device asynchronous on `stream`, ordered like the device-resident renders.
+ * Bounds.  One launch holds at most 2^26 work items, one per sample slot: rt_render_probes_device returns
+ * RT_ERR_ARG when 64 * ceil(n / 64) * P > 2^26, P = spp rounded up to a power of two; split by n, or by
+ * sample_base (promise 3 makes that free).  rt_render_probes takes any n in chunks (2^19 probes,
+ * RTCORE_QUERY_CHUNK, fewer where spp asks for it), two of them resident: per probe 360 B up (the record and
+ * what the caller's arrays hold, which the sums continue from) and 296 B down; it returns RT_ERR_ARG only
+ * when not even 64 probes fit (spp > 2^20).
+ */
+/* 288 B per probe: nine rows l = 0..8 of four doubles (r, g, b sums and the misses' projection) */
+typedef struct rt_probe_sh {
+    double c[9][4];
+} rt_probe_sh;
+int rt_render_probes_device(rt_scene* scene, const rt_surfel* d_probes, int64_t n, int32_t spp, uint64_t seed,
+                            uint64_t sample_base, uint64_t stream_base, rt_probe_sh* d_sh, uint32_t* d_samples,
+                            uint32_t* d_misses, unsigned long long* d_rays_count, void* stream);
+int rt_render_probes(rt_scene* scene, const rt_surfel* probes, int64_t n, int32_t spp, uint64_t seed,
+                     uint64_t sample_base, uint64_t stream_base, rt_probe_sh* sh, uint32_t* samples, uint32_t* misses,
+                     uint64_t* rays_out);
+/* Host only, no device: y9_out[9 i + l] = Y_l of the direction dirs_xyz[3 i ..], the kernel's function
+   compiled for the CPU.  RT_ERR_ARG for n < 0 or a null pointer with n > 0. */
+int rt_debug_sh_basis(const double* dirs_xyz, int64_t n, double* y9_out);
+/* Host only, no device: the accumulation above for n probes of spp samples each, sample k of probe i at
+   i * spp + k: its ray (a direction of all zeros: a sample of an invalid probe), its fp32 colour rgb[3 (i spp
+   + k) ..] and miss[i spp + k] != 0 for a primary miss; added into sh, samples and misses (n each).
+   RT_ERR_ARG for n < 0, spp <= 0 or a null pointer with n > 0. */
+int rt_debug_probe_fold(const rt_ray* rays, const float* rgb, const uint8_t* miss, int64_t n, int32_t spp,
+                        rt_probe_sh* sh, uint32_t* samples, uint32_t* misses);
 
 /* ---------------------------------------------------- indexed radiance queries --- */
 /*

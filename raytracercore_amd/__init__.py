@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import ctypes as C
 import enum
+import math
 import os
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
@@ -153,6 +154,11 @@ class rt_surfel(C.Structure):
     _fields_ = [("position", rt_vec4d), ("normal", rt_vec4d)]
 
 
+class rt_probe_sh(C.Structure):
+    """288 B: nine rows l = 0 .. 8 of four doubles (the r, g, b sums and the misses' projection)."""
+    _fields_ = [("c", (C.c_double * 4) * 9)]
+
+
 class rt_hit(C.Structure):
     """One answer of rt_query_rays (Hit.cs): 48 B, offsets in include/rtcore.h."""
     _fields_ = [
@@ -253,7 +259,7 @@ _OPTIONAL = ("rt_query_rays", "rt_query_rays_device", "rt_camera_rays", "rt_sele
              "rt_adaptive_select_device", "rt_primary_hits_device", "rt_denoise_device", "rt_reproject_device",
              "rt_render_beams", "rt_render_beams_device", "rt_camera_beams",
              "rt_render_surfels", "rt_render_surfels_device", "rt_render_list", "rt_render_list_device",
-             "rt_occluded_surfels", "rt_occluded_surfels_device")
+             "rt_occluded_surfels", "rt_occluded_surfels_device", "rt_render_probes", "rt_render_probes_device")
 
 _lib: Optional[C.CDLL] = None
 
@@ -376,6 +382,13 @@ def load_library(path: str = "") -> C.CDLL:
                                                C.c_uint64, C.c_uint64] + [C.c_void_p] * 4 + [C.c_void_p]),
         "rt_debug_surfel_rays_device": (C.c_int, [C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64,
                                                   C.c_uint64, C.c_void_p, C.c_void_p]),
+        "rt_render_probes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64,
+                                       P(rt_probe_sh), P(C.c_uint32), P(C.c_uint32), P(C.c_uint64)]),
+        "rt_render_probes_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64,
+                                              C.c_uint64] + [C.c_void_p] * 4 + [C.c_void_p]),
+        "rt_debug_sh_basis": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+        "rt_debug_probe_fold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, P(rt_probe_sh),
+                                          P(C.c_uint32), P(C.c_uint32)]),
         "rt_render_list": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                      C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, P(rt_color), P(C.c_uint32),
                                      P(C.c_uint32), P(C.c_double), P(C.c_uint32), P(C.c_uint64)]),
@@ -745,6 +758,85 @@ def gather_mean(sum_rgb, samples, misses, ambient) -> np.ndarray:
     ns, ms = np.asarray(samples, np.float64), np.asarray(misses, np.float64)
     with np.errstate(invalid="ignore", divide="ignore"):
         return (s + ms[..., None] * amb) / (ns + ms)[..., None]
+
+
+def _probe_out(n: int, out):
+    """render_probes' and probe_fold_host's `out` = (sh f64 [n, 9, 4], samples u32 [n], misses u32 [n]), new
+    zeroed arrays for None; checked."""
+    if out is None:
+        out = (np.zeros((n, 9, 4), np.float64), np.zeros(n, np.uint32), np.zeros(n, np.uint32))
+    if len(out) != 3:
+        raise ValueError("out must be (sh, samples, misses)")
+    for a, shape, dt in zip(out, ((n, 9, 4), (n,), (n,)), (np.float64, np.uint32, np.uint32)):
+        if a.shape != shape or a.dtype != dt or not a.flags.c_contiguous:
+            raise ValueError("out must be C-contiguous (sh f64 [n, 9, 4], samples u32 [n], misses u32 [n])")
+    return out
+
+
+def sh_basis(dirs) -> np.ndarray:
+    """rt_debug_sh_basis (host code, no GPU): the nine L2 real spherical-harmonic basis functions of each
+    direction of dirs (..., 3), taken as given, as (..., 9): the probes' fold kernel's function compiled for
+    the CPU (order Y00, Y1-1, Y10, Y11, Y2-2, Y2-1, Y20, Y21, Y22)."""
+    lib = load_library()
+    if not hasattr(lib, "rt_debug_sh_basis"):
+        raise RtError("this build of the library has no rt_debug_sh_basis")
+    d = np.ascontiguousarray(dirs, np.float64)
+    if d.ndim < 1 or d.shape[-1] != 3:
+        raise ValueError("dirs must be a (..., 3) array")
+    y = np.zeros(d.shape[:-1] + (9,), np.float64)
+    _check(lib.rt_debug_sh_basis(d.ctypes.data_as(C.c_void_p), d.size // 3, y.ctypes.data_as(C.c_void_p)))
+    return y
+
+
+def probe_fold_host(rays, rgb, miss, out=None):
+    """rt_debug_probe_fold (host code, no GPU): render_probes' accumulation over per-sample results.  rays
+    (n, spp) of RAY_DTYPE as surfel_rays reports them in RT_GATHER_SPHERE (a direction of all zeros: a sample
+    of an invalid probe), rgb (n, spp, 3) the samples' fp32 colours and miss (n, spp) true for a primary miss:
+    what render_rays gives for rays[:, k] at spp 1.  Returns (sh, samples, misses), new or the caller's `out`,
+    which the call adds into."""
+    lib = load_library()
+    if not hasattr(lib, "rt_debug_probe_fold"):
+        raise RtError("this build of the library has no rt_debug_probe_fold")
+    r = np.ascontiguousarray(rays, RAY_DTYPE)
+    if r.ndim != 2:
+        raise ValueError("rays must be an (n, spp) RAY_DTYPE array")
+    n, spp = r.shape
+    col = np.ascontiguousarray(rgb, np.float32)
+    ms = np.ascontiguousarray(np.asarray(miss) != 0, np.uint8)
+    if col.shape != (n, spp, 3) or ms.shape != (n, spp):
+        raise ValueError("rgb must be (n, spp, 3) and miss (n, spp)")
+    sh, ns, nm = _probe_out(n, out)
+    _check(lib.rt_debug_probe_fold(r.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p),
+                                   ms.ctypes.data_as(C.c_void_p), n, spp, sh.ctypes.data_as(C.POINTER(rt_probe_sh)),
+                                   ns.ctypes.data_as(C.POINTER(C.c_uint32)), nm.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return sh, ns, nm
+
+
+def probe_radiance_sh(sh, samples, misses, ambient) -> np.ndarray:
+    """The radiance coefficients of render_probes' accumulators, L[..., l, ch] = 4 pi / N * (c[l][ch] + c[l][3] *
+    ambient[ch]) with N = samples + misses: a sample that met nothing saw the untinted ambient colour (three
+    floats or an rt_color) in its direction.  sh (..., 9, 4) -> (..., 9, 3); NaN where a probe has no sample."""
+    amb = np.array([ambient.r, ambient.g, ambient.b] if isinstance(ambient, rt_color) else ambient, np.float64).reshape(3)
+    c = np.asarray(sh, np.float64)
+    total = np.asarray(samples, np.float64) + np.asarray(misses, np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return (4.0 * math.pi / total)[..., None, None] * (c[..., :3] + c[..., 3:4] * amb)
+
+
+SH_COSINE_LOBE = np.array([math.pi] + [2.0 * math.pi / 3.0] * 3 + [math.pi / 4.0] * 5)  # A_l of bands 0, 1, 2
+
+
+def sh_radiance(L, dirs) -> np.ndarray:
+    """The radiance the coefficients L (..., 9, 3) reconstruct in the unit directions dirs (..., 3):
+    sum over l of L[l] Y_l(dir), (..., 3); the leading shapes broadcast."""
+    return np.einsum("...lc,...l->...c", np.asarray(L, np.float64), sh_basis(dirs))
+
+
+def sh_irradiance(L, normals) -> np.ndarray:
+    """The irradiance of a diffuse receiver with the unit normals (..., 3) under the radiance L (..., 9, 3):
+    sum over l of A_l L[l] Y_l(n), A = pi, 2 pi / 3 (l = 1 .. 3) and pi / 4 (l = 4 .. 8), the cosine lobe's
+    zonal coefficients (Ramamoorthi and Hanrahan 2001); (..., 3).  Exact for radiance of bands 0 .. 2."""
+    return np.einsum("...lc,...l->...c", np.asarray(L, np.float64), sh_basis(normals) * SH_COSINE_LOBE)
 
 
 def ambient_occlusion(occluded, samples) -> np.ndarray:
@@ -1164,6 +1256,41 @@ class GpuRaytracer:
                                                  sample_base, stream_base, C.c_void_p(_ptr(d_sum)),
                                                  C.c_void_p(_ptr(d_samples)), C.c_void_p(_ptr(d_misses)),
                                                  C.c_void_p(_ptr(d_rays)), C.c_void_p(stream)))
+
+    def render_probes(self, positions, spp: int, seed: int, normals=None, sample_base: int = 0, stream_base: int = 0,
+                      out=None):
+        """rt_render_probes: light probes.  spp RT_GATHER_SPHERE gather samples per point, sample k of probe i
+        render_surfels' (the ray surfel_rays reports), summed under the nine L2 spherical-harmonic basis
+        functions of its direction: sh[i, l, 0:3] += colour * Y_l for a hit, sh[i, l, 3] += Y_l for a sample
+        that met nothing.  positions (n, 3) or (n, 4); normals only fix the frame the directions are drawn in,
+        default (0, 0, 1); or one SURFEL_DTYPE array as positions.  Returns (sh f64 [n, 9, 4], samples u32 [n],
+        misses u32 [n], rays): new zeroed arrays, or the caller's `out` = (sh, samples, misses), which the call
+        continues from (a + b samples are a samples, then b at sample_base + a, bit for bit).
+        probe_radiance_sh turns them into radiance coefficients."""
+        if normals is None and not (isinstance(positions, np.ndarray) and positions.dtype == SURFEL_DTYPE):
+            pos = np.asarray(positions, np.float64)
+            normals = np.zeros_like(pos)
+            if pos.ndim == 2 and pos.shape[1] >= 3:
+                normals[:, 2] = 1.0
+        probes = _pack_surfels(positions, normals)
+        n = probes.shape[0]
+        sh, ns, ms = _probe_out(n, out)
+        count = C.c_uint64(0)
+        _check(self.lib.rt_render_probes(self.handle, probes.ctypes.data_as(C.c_void_p), n, spp, seed, sample_base,
+                                         stream_base, sh.ctypes.data_as(C.POINTER(rt_probe_sh)),
+                                         ns.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                         ms.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(count)))
+        return sh, ns, ms, count.value
+
+    def render_probes_device(self, d_probes, n: int, spp: int, seed: int, sample_base: int, stream_base: int, d_sh,
+                             d_samples, d_misses, d_rays=0, stream: int = 0) -> None:
+        """rt_render_probes_device: asynchronous probes for n rt_surfel (64 B each) at d_probes, added into n
+        rt_probe_sh (288 B each: [n, 9, 4] doubles) at d_sh and n uint32 each at d_samples and d_misses (d_rays:
+        one uint64 ray counter or 0) on `stream`; 64 * ceil(n / 64) * (spp rounded up to a power of two) must
+        not pass 2^26.  The device arrays as torch tensors or as pointers (integers)."""
+        _check(self.lib.rt_render_probes_device(self.handle, C.c_void_p(_ptr(d_probes)), n, spp, seed, sample_base,
+                                                stream_base, C.c_void_p(_ptr(d_sh)), C.c_void_p(_ptr(d_samples)),
+                                                C.c_void_p(_ptr(d_misses)), C.c_void_p(_ptr(d_rays)), C.c_void_p(stream)))
 
     def surfel_rays(self, positions, normals, spp: int, seed: int, mode: int = RT_GATHER_DIFFUSE, sample_base: int = 0,
                     stream_base: int = 0) -> np.ndarray:

@@ -15,6 +15,10 @@ namespace {
 constexpr int64_t kRaysChunk = 1 << 19; // rays of one chunk of rt_render_rays (rt_query_rays' size and variable)
 constexpr RenderList kRays = {ITEMS_RAYS, sizeof(rt_ray), kRaysChunk, "rays"};
 
+} // namespace
+
+namespace rtc {
+
 // Argument and state checks shared by both entry points; RT_OK with *empty set for n == 0.
 int check_render_rays(rt_scene* s, const void* rays, int64_t n, int32_t spp, const void* sum, const void* samples,
                       const void* misses, const char* name, bool* empty)
@@ -37,10 +41,6 @@ int check_render_rays(rt_scene* s, const void* rays, int64_t n, int32_t spp, con
     }
     return RT_OK;
 }
-
-} // namespace
-
-namespace rtc {
 
 // The path kernel of the scene's variant, src's instance, and nothing after it: the caller folds p's
 // partials.  run_path without what the list renders leave alone: no timing slot, no counters, no ray log,

@@ -43,6 +43,9 @@ __device__ __forceinline__ bool known_zero(float c)
 } // namespace rtc
 #define RT_HAVE_KNOWN_ZERO
 #include "rt_surfel.h"
+#ifndef __HIPCC_RTC__ // (the probes' fold is no part of a scene-specialised build)
+#include "rt_sh.h"
+#endif
 #ifdef RT_SCENE_CONST
 // rt_jit.cpp generates this header per scene (and camera, for the grouped order): the launch's
 // PathScene and its brute-force records as 32-bit words (kSceneW, kGroupsW, kRectsW, kFramesW,
@@ -3075,6 +3078,70 @@ __global__ void accumulate_list_kernel(PathParams p, const uint32_t* index, size
     fold_entry(p, i, e, e < n_records, sum, samples, misses, q, batches, plane, recs);
 }
 
+// rt_render_probes: the fold of a SURFELS launch in RT_GATHER_SPHERE with one sample per work item
+// (make_params_probes), one thread per probe as accumulate_rays_kernel, so that a wave's loads of chunk k
+// are 64 consecutive float4.  Row k of probe i is sample k's fp32 colour and its hit or miss; the sample's
+// direction is drawn again as the launch drew it (refill: the stream's first two draws through
+// surfel_sample) and weighs the colour, or for a primary miss the count, by the nine basis functions of
+// rt_sh.h: fp64, product and sum each rounded on its own, in sample order from what the accumulators hold.
+// recs null: sh, samples and misses of the probe; else recs[i], which came up with the caller's sums and
+// zero counts and goes down to the host entry.  The 36 sums stay in registers; no LDS, no atomics.
+__global__ void __launch_bounds__(256) accumulate_probes_kernel(PathParams p, rt_probe_sh* sh, uint32_t* samples,
+                                                                uint32_t* misses, ProbeRec* recs)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)p.n_rays) return;
+    double* const acc = recs ? &recs[i].sh.c[0][0] : &sh[i].c[0][0];
+    double c[kShCoeffs][4];
+#pragma unroll
+    for (int l = 0; l < kShCoeffs; l++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) c[l][j] = acc[4 * l + j];
+    uint32_t ns = 0, nm = 0;
+    const double2* const rows = p.ray_list + 4 * i;
+    const rt_key2 pkey = rt_rng_pixel_key(p.seed_key, p.stream_base + (unsigned long long)i);
+    const float4* const row = p.partial + ((((i >> 6) << p.log2_chunks) << 6) + (i & 63));
+    for (int k = 0; k < p.spp; k++) { // (chunk == 1: chunk k is sample k)
+        const float4 v = row[(size_t)k << 6];
+        const uint32_t w = __float_as_uint(v.w);
+        rt_rng rng = rt_rng_from_pixel_key(pkey, p.sample_base + (unsigned long long)k);
+        const float u1 = (float)rt_rng_next24(&rng) * 0x1p-24f;
+        const float u2 = (float)rt_rng_next24(&rng) * 0x1p-24f;
+        V3 o, d;
+        if (!surfel_sample(rows, RT_GATHER_SPHERE, u1, u2, o, d)) { // an invalid probe: a miss in no direction
+            nm++;
+            continue;
+        }
+        double Y[kShCoeffs];
+        sh_basis((double)d.x, (double)d.y, (double)d.z, Y);
+        if (w >> 16) {
+            nm++;
+#pragma unroll
+            for (int l = 0; l < kShCoeffs; l++) c[l][3] = __dadd_rn(c[l][3], Y[l]);
+        } else if (w & 0xFFFFu) {
+            ns++;
+            const double r = (double)v.x, g = (double)v.y, b = (double)v.z;
+#pragma unroll
+            for (int l = 0; l < kShCoeffs; l++) {
+                c[l][0] = __dadd_rn(c[l][0], __dmul_rn(r, Y[l]));
+                c[l][1] = __dadd_rn(c[l][1], __dmul_rn(g, Y[l]));
+                c[l][2] = __dadd_rn(c[l][2], __dmul_rn(b, Y[l]));
+            }
+        }
+    }
+#pragma unroll
+    for (int l = 0; l < kShCoeffs; l++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) acc[4 * l + j] = c[l][j];
+    if (recs) {
+        recs[i].samples += ns;
+        recs[i].misses += nm;
+    } else {
+        samples[i] += ns;
+        misses[i] += nm;
+    }
+}
+
 // SampleSet.GetOutput / GetColorCode (SampleSet.cs:50-113) per pixel of planar accumulators.
 __device__ __forceinline__ uint32_t color_code(double r, double g, double b, double a)
 {
@@ -3463,6 +3530,15 @@ hipError_t launch_accumulate_list(const PathParams& p, const uint32_t* d_index, 
     if (plane == 0) plane = n_records;
     hipLaunchKernelGGL(accumulate_list_kernel, dim3((p.n_rays + 255u) / 256u), dim3(256), 0, stream, p, d_index, n_records,
                        d_sum, d_samples, d_misses, d_q, d_batches, plane, d_recs);
+    return hipGetLastError();
+}
+
+hipError_t launch_accumulate_probes(const PathParams& p, rt_probe_sh* d_sh, uint32_t* d_samples, uint32_t* d_misses,
+                                    ProbeRec* d_recs, hipStream_t stream)
+{
+    if (p.n_rays == 0) return hipSuccess;
+    hipLaunchKernelGGL(accumulate_probes_kernel, dim3((p.n_rays + 255u) / 256u), dim3(256), 0, stream, p, d_sh, d_samples,
+                       d_misses, d_recs);
     return hipGetLastError();
 }
 

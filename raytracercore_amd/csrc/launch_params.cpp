@@ -238,6 +238,26 @@ int64_t render_rays_max_n(int kernel, int spp)
     return std::min<int64_t>(blocks * 64, (int64_t)1 << 30);
 }
 
+// rt_render_probes: make_params_rays with chunks_over = spp, which gives chunk = ceil(spp / spp) = 1 and
+// `used` = spp real chunks of n_chunks = the next power of two; set_item_order deals no slot past them and,
+// with no short chunk, every ticket is full-length but a block's last.  The tuned chunk counts and
+// RTCORE_PATH_CHUNKS do not apply: what a probe's sample is must not depend on them.
+PathParams make_params_probes(int kernel, int64_t n, int spp, uint64_t seed, uint64_t base, uint64_t stream_base)
+{
+    PathParams p = make_params_for(kernel, spp, 0, 0, 0, 8, (int)((n + 7) / 8), spp, seed, base, 2073600.0);
+    p.n_rays = (unsigned)n;
+    p.stream_base = stream_base;
+    return p;
+}
+
+int64_t probes_max_n(int spp)
+{
+    const uint64_t items = 1ull << 26; // chunk_pipeline's figure (kChunkItems)
+    uint64_t slots = 1;
+    while (slots < (uint64_t)spp) slots *= 2; // (spp < 2^31: no overflow)
+    return slots > items / 64 ? 0 : (int64_t)(items / slots); // a power of two >= 64: whole blocks
+}
+
 // Start rows: a wave that opens items builds every camera ray of those items with all its lanes and
 // keeps them in a row buffer of its own; the sample start, which the lanes reach one by one, loads
 // the lane's row instead of building the ray (refill).  For the brute-force tile launches that are

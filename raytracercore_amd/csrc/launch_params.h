@@ -18,6 +18,13 @@ int64_t render_rays_max_n(int kernel, int spp);
 // rt_render_pixels: the launch record of a list of n frame pixels of a width x height frame, planned as
 // make_params_rays plans n rays (p.pixel_list is set by the caller); render_rays_max_n bounds n.
 PathParams make_params_pixels(int kernel, int64_t n, int spp, uint64_t seed, uint64_t base, int width, int height);
+// rt_render_probes: the launch record of n probes, planned as make_params_rays plans n rays but with spp
+// chunks per probe: one sample per work item whatever spp is (chunk = 1, n_chunks = spp rounded up to a
+// power of two), so that the partial row of item (probe i, chunk k) is sample k's colour and count.
+// probes_max_n bounds n: the most probes, in whole blocks of 64, whose n_chunks slots stay within 2^26 work
+// items (1 GiB of partials); 0 when not even 64 fit (spp > 2^20).  Call it first: it takes any spp > 0.
+PathParams make_params_probes(int kernel, int64_t n, int spp, uint64_t seed, uint64_t base, uint64_t stream_base);
+int64_t probes_max_n(int spp);
 // The order in which the dispensers deal p's work items, from p's chunks, pool and ranges.
 void set_item_order(PathParams& p);
 // Plans p's item ranges and tickets (set_item_order) over n_blocks blocks; p.n_pad = 64 n_blocks.

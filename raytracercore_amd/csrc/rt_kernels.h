@@ -422,6 +422,18 @@ hipError_t launch_accumulate_pixels_recs(const PathParams& p, PixelRec* d_recs, 
 hipError_t launch_accumulate_list(const PathParams& p, const uint32_t* d_index, size_t n_records, double* d_sum,
                                   uint32_t* d_samples, uint32_t* d_misses, double* d_q, uint32_t* d_batches, size_t plane,
                                   PixelRec* d_recs, hipStream_t stream);
+// One probe of rt_render_probes' host entry: the accumulators as they travel, up with what the caller's
+// arrays hold in sh and zero counts, down with the call's samples folded in.
+struct ProbeRec {
+    rt_probe_sh sh;
+    uint32_t samples, misses;
+};
+// rt_render_probes: the partials of a SURFELS launch in RT_GATHER_SPHERE planned by make_params_probes (one
+// sample per work item) folded per probe in sample order, each sample weighted by the L2 basis (rt_sh.h) of
+// its direction, which the fold draws again as the launch did (p.ray_list, the seed and the bases of p).
+// d_recs null: added to d_sh, d_samples, d_misses (p.n_rays each); else to d_recs[p.n_rays] in place.
+hipError_t launch_accumulate_probes(const PathParams& p, rt_probe_sh* d_sh, uint32_t* d_samples, uint32_t* d_misses,
+                                    ProbeRec* d_recs, hipStream_t stream);
 // planar row-major accumulators (w*h) -> TileRec[w*h] in x*h + y order
 hipError_t launch_tile_host_layout(int w, int h, const double* d_sum, const uint32_t* d_samples,
                                   const uint32_t* d_misses, TileRec* d_out, hipStream_t stream);

@@ -1,6 +1,6 @@
 // rt_scene.h -- the scene object behind the C ABI and what the API's translation units share
 // (rtcore_api.hip, scene_upload.hip, api_frame.hip, api_debug.hip, api_query.hip, api_select.hip, api_render_rays.hip,
-// api_render_pixels.hip, chunk_pipeline.hip, api_adaptive.hip, api_denoise.hip, api_reproject.hip).
+// api_render_pixels.hip, api_render_probes.hip, chunk_pipeline.hip, api_adaptive.hip, api_denoise.hip, api_reproject.hip).
 #pragma once
 #include <algorithm>
 #include <array>
@@ -192,6 +192,7 @@ struct rt_scene {
     DevBuf<TileRec> render_rays_recs;
     DevBuf<uint32_t> pixel_list;
     DevBuf<PixelRec> pixel_recs;
+    DevBuf<ProbeRec> probe_recs; // rt_render_probes: two chunks' accumulators, uploaded, folded into and downloaded
     std::array<hipEvent_t, 2> query_up_ev{};
     // rt_primary_hits_device: one chunk of camera rays, made and read on the caller's stream (its own
     // buffer: rt_query_rays fills query_rays from its copy stream)
@@ -329,7 +330,7 @@ inline hipError_t wait_last_op(rt_scene* s, hipStream_t st)
     return s->any_op && st != s->last_stream ? hipStreamWaitEvent(st, s->done_ev, 0) : hipSuccess;
 }
 // chunk_pipeline.hip: the loop of every host entry that takes n of the caller's items (rt_query_rays,
-// rt_occluded_rays, rt_occluded_surfels, rt_render_rays / _beams / _surfels, rt_render_list,
+// rt_occluded_rays, rt_occluded_surfels, rt_render_rays / _beams / _surfels, rt_render_probes, rt_render_list,
 // rt_render_pixels), in chunks of C = min(largest, RTCORE_QUERY_CHUNK, cap, n) items, two of them resident;
 // the order of its steps is argued at its definition.  An entry says what varies:
 //   reserve(C, up, d_down)             its device buffers for two chunks of C items; it names the one the answers
@@ -342,8 +343,8 @@ inline hipError_t wait_last_op(rt_scene* s, hipStream_t st)
 // slot = (k & 1) C is the chunk's offset, in items, in every two-chunk buffer.  The buffers are the scene's and
 // shared by size, not by name: every entry's records travel in query_rays (a surfel is an rt_ray, a beam three)
 // and its entry numbers in pixel_list; the segment ends of both occlusion entries in occluded_t_max; the answers
-// in query_hits, occluded_out, occluded_counts, render_rays_recs (rays, beams, surfels) or pixel_recs (pixels,
-// lists).  An entry has consumed its last chunk when it returns, so the next call finds them free.
+// in query_hits, occluded_out, occluded_counts, render_rays_recs (rays, beams, surfels), pixel_recs (pixels,
+// lists) or probe_recs (probes: these also go up, with the sums the fold continues from).  An entry has consumed its last chunk when it returns, so the next call finds them free.
 struct ChunkJob {
     int64_t n, largest, cap; // cap 0: none
     size_t down_bytes, up_bytes;
@@ -380,6 +381,10 @@ int run_items(rt_scene* s, ItemSource src, const char* what, PathParams& p, unsi
 // at list position j (gathered) or at its entry number.
 int run_rays(rt_scene* s, const RenderList& kind, PathParams& p, const void* d_list, unsigned long long* d_count,
              hipStream_t stream, const uint32_t* d_index, unsigned n_records, bool gathered);
+// The argument and state checks of every entry over such a list (rt_render_probes' too, api_render_probes.hip),
+// with the entry point's name for messages; RT_OK with *empty set for n == 0.
+int check_render_rays(rt_scene* s, const void* rays, int64_t n, int32_t spp, const void* sum, const void* samples,
+                      const void* misses, const char* name, bool* empty);
 int render_list_device(rt_scene* s, const RenderList& kind, const char* name, const void* d_list, int64_t n, int32_t spp,
                        uint64_t seed, uint64_t sample_base, uint64_t stream_base, double* d_sum, uint32_t* d_samples,
                        uint32_t* d_misses, unsigned long long* d_count, void* stream);
