@@ -56,7 +56,10 @@ extern "C" {
                                    rt_debug_surfel_rays_device, and rt_list_kind, rt_render_list and
                                    rt_render_list_device, and rt_occluded_surfels and
                                    rt_occluded_surfels_device, and rt_probe_sh, rt_render_probes,
-                                   rt_render_probes_device, rt_debug_sh_basis and rt_debug_probe_fold */
+                                   rt_render_probes_device, rt_debug_sh_basis and rt_debug_probe_fold, and
+                                   rt_probe_grid, rt_probe_radiance_device, rt_debug_probe_radiance,
+                                   rt_shade_probes, rt_shade_probes_device, rt_debug_probe_segments,
+                                   rt_debug_probe_segments_device and rt_debug_shade_probes */
 
 typedef enum rt_status {
     RT_OK = 0,
@@ -927,6 +930,100 @@ int rt_debug_sh_basis(const double* dirs_xyz, int64_t n, double* y9_out);
    RT_ERR_ARG for n < 0, spp <= 0 or a null pointer with n > 0. */
 int rt_debug_probe_fold(const rt_ray* rays, const float* rgb, const uint8_t* miss, int64_t n, int32_t spp,
                         rt_probe_sh* sh, uint32_t* samples, uint32_t* misses);
+
+/*
+ * Probe grids: the irradiance a regular grid of such probes gives at shading points, on the device.  Per
+ * point: the trilinear blend of the radiance coefficients of its cell's eight probes, without the probes the
+ * point cannot see (a probe behind a wall does not light the point in front of it), then the nine-term dot
+ * product with the cosine lobe for the point's normal.  A grid goes from rt_render_probes to shading with
+ * nothing leaving the device.
+ *
+ * The grid.  Probe (ix, iy, iz) has index (iz * ny + iy) * nx + ix, x fastest, and the position
+ * origin + (ix, iy, iz) * step.  Its radiance is L: n_probes x 9 x 3 doubles, L[p][l][ch].
+ *
+ * Everything below is normative and fp64: every operation is rounded on its own, nothing is contracted,
+ * division and square root are IEEE, no library function is called.
+ *
+ * Radiance (rt_probe_radiance_device, rt_debug_probe_radiance).  N = samples + misses in 64 bits,
+ *   k = (4.0 * 3.141592653589793) / (double)N,   L[l][ch] = k * (c[l][ch] + c[l][3] * ambient_ch),
+ * the product rounded, then the sum, then the product by k.  N == 0: all 27 coefficients are a quiet NaN;
+ * such a probe is ABSENT.
+ * Point.  An rt_surfel.  It is invalid if one of its 8 doubles is not finite, or n2 = (nx*nx + ny*ny) + nz*nz
+ * is 0 or not finite: irradiance (0, 0, 0), weight 0, all eight segments zero.  Else n^ = normal / sqrt(n2),
+ * component by component.
+ * Cell, per axis a.  dims_a == 1: i_a = 0, f_a = 0.  Else g = (p_a - origin_a) / step_a, held to
+ * [0, dims_a - 1] (g < 0 ? 0 : g > dims_a - 1 ? dims_a - 1 : g: a point outside the grid takes the boundary's
+ * value), i_a = (int)g held to dims_a - 2, f_a = g - (double)i_a.
+ * Corners c = dx + 2 dy + 4 dz, c = 0 .. 7.  w_a = d_a ? f_a : 1 - f_a, t_c = (w_x * w_y) * w_z.  A corner
+ * with t_c == 0 is NOT VISITED (so no index past dims is formed, and a point at a probe's own position reads
+ * that probe alone).  A visited corner's probe is (i_x + dx, i_y + dy, i_z + dz), at
+ * q_a = origin_a + (double)(i_a + d_a) * step_a.
+ * Segment of point i, corner c, stored at 8 i + c; it depends on the grid and the point only.  A corner that
+ * is not visited, or a grid without RT_PROBE_GRID_VISIBILITY: an all-zero rt_ray and t_max = 0, an empty
+ * segment, for which rt_occluded_rays answers 0.  Else o_a = p_a + bias * n^_a, v = q - o,
+ * d2 = (vx*vx + vy*vy) + vz*vz, dist = sqrt(d2); dist not > 0 or not finite: the empty segment again; else
+ * origin = (o, 1), direction = (v / dist, 0), t_max = dist.
+ * Visibility.  Corner c is HIDDEN exactly when rt_occluded_rays_device(RT_QUERY_FAST) answers 1 for that
+ * segment on this scene in its traversal mode; rt_occluded_rays' rules apply word for word (fp32 rounding of
+ * ray and t_max, culling of one-sided primitives, generic kernels only, RTCORE_OCCLUDED_EARLY, RT_ERR_STATE
+ * on a BVH2 scene).  Without the flag no query runs and the scene is used only for its device and scratch.
+ * Blend, corners ascending; a corner contributes if it is visited, not hidden and present (all 27 of its
+ * coefficients finite):  W = W + t_c;  B[l][ch] = B[l][ch] + t_c * L_c[l][ch], the product rounded, then the
+ * sum; both start at 0.
+ * W > 0:  Y = the basis of "light probes" at n^;  a_l = A_l * Y_l with A_0 = 3.141592653589793,
+ * A_1..3 = 2.0943951023931953, A_4..8 = 0.7853981633974483;
+ *   E_ch = (a_0 * B[0][ch] + a_1 * B[1][ch] + ... + a_8 * B[8][ch]) / W, left to right.
+ * The irradiance is E and the weight W: about 1 when every corner contributes, else the share of the
+ * trilinear weight that could see the point.  W == 0: irradiance 0 and weight 0; the caller falls back, for
+ * example to a gather at those points.
+ * What is promised:
+ *   1. The device result equals rt_debug_shade_probes fed with rt_debug_probe_segments_device's segments and
+ *      rt_occluded_rays_device's answers for them, bit for bit.
+ *   2. The device segments equal rt_debug_probe_segments, bit for bit.
+ *   3. A point's result depends on the grid, L, the record and the traversal mode only: not on n, on list
+ *      position, on chunking or on the stream.
+ * Calls.  `grid` is always a host pointer, copied by value into the launches.  The outputs are written, not
+ * added to; d_weight / weight may be NULL.  RT_ERR_ARG, before anything is launched, for a null scene or
+ * grid; a grid that breaks a rule of the struct; n < 0; then, for n > 0, a null L, points or irradiance
+ * pointer.  n == 0 returns RT_OK and touches nothing.  RT_ERR_STATE on a BVH2 scene only with the visibility
+ * flag.  No camera is needed; the counters of rt_scene_get_stats, an armed rt_debug_ray_log, rt_kernel_times
+ * and the scene-specialised kernels are left as they were.  rt_shade_probes_device is asynchronous on
+ * `stream`, ordered like the device-resident renders, and works in chunks of 2^16 points (RTCORE_QUERY_CHUNK
+ * / 8: one any-hit launch of at most 2^19 segments, 73 B of per-scene scratch each); rt_shade_probes uploads
+ * L once and takes the points in the same chunks, 64 B up and 32 B down per point.
+ * Not part of it: DDGI's backface "wrap" weight and its Chebyshev depth moments; a shortened segment end
+ * (probes belong in the air); RT_QUERY_EXACT; a grid that is not axis-aligned; adding into the outputs.
+ */
+#define RT_PROBE_GRID_VISIBILITY 1u
+typedef struct rt_probe_grid {   /* 80 B, five 16-byte rows */
+    double   origin[3];  /* position of probe (0, 0, 0); finite                                */
+    double   step[3];    /* spacing per axis; finite and > 0 (also where dims is 1)             */
+    int32_t  dims[3];    /* nx, ny, nz >= 1; nx * ny * nz < 2^31                                */
+    uint32_t flags;      /* RT_PROBE_GRID_VISIBILITY: leave out the probes the point cannot see */
+    double   bias;       /* finite, >= 0: the segments start at position + bias * unit normal   */
+    uint32_t reserved[2];/* 0 */
+} rt_probe_grid;
+/* L from rt_render_probes' accumulators, on the calling thread's current device (as rt_tonemap_device),
+   asynchronous on `stream`.  RT_ERR_ARG for n < 0, n >= 2^31 or a null pointer with n > 0. */
+int rt_probe_radiance_device(const rt_probe_sh* d_sh, const uint32_t* d_samples, const uint32_t* d_misses, int64_t n,
+                             rt_color ambient, double* d_L, void* stream);
+/* Its host twin: host only, no device. */
+int rt_debug_probe_radiance(const rt_probe_sh* sh, const uint32_t* samples, const uint32_t* misses, int64_t n,
+                            rt_color ambient, double* L);
+int rt_shade_probes_device(rt_scene* scene, const rt_probe_grid* grid, const double* d_L, const rt_surfel* d_points,
+                           int64_t n, rt_color* d_irradiance, double* d_weight, void* stream);
+int rt_shade_probes(rt_scene* scene, const rt_probe_grid* grid, const double* L, const rt_surfel* points, int64_t n,
+                    rt_color* irradiance, double* weight);
+/* The eight segments of every point (no scene: the current device, as rt_debug_surfel_rays_device), and the
+   host twin.  RT_ERR_ARG as above, and for a null output pointer with n > 0. */
+int rt_debug_probe_segments_device(const rt_probe_grid* grid, const rt_surfel* d_points, int64_t n, rt_ray* d_rays_out,
+                                   double* d_t_max_out, void* stream);
+int rt_debug_probe_segments(const rt_probe_grid* grid, const rt_surfel* points, int64_t n, rt_ray* rays_out,
+                            double* t_max_out);
+/* Host twin of the blend, no device: occluded = rt_occluded_rays' answers for those segments (n * 8 bytes),
+   NULL = all 0. */
+int rt_debug_shade_probes(const rt_probe_grid* grid, const double* L, const rt_surfel* points, int64_t n,
+                          const uint8_t* occluded, rt_color* irradiance, double* weight);
 
 /* ---------------------------------------------------- indexed radiance queries --- */
 /*

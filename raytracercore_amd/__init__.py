@@ -159,6 +159,24 @@ class rt_probe_sh(C.Structure):
     _fields_ = [("c", (C.c_double * 4) * 9)]
 
 
+RT_PROBE_GRID_VISIBILITY = 1  # rt_probe_grid.flags: leave out the probes the point cannot see
+
+
+class rt_probe_grid(C.Structure):
+    """A regular grid of light probes (rt_shade_probes): 80 B, five 16-byte rows; probe (ix, iy, iz) has index
+    (iz * ny + iy) * nx + ix and the position origin + (ix, iy, iz) * step."""
+    _fields_ = [("origin", C.c_double * 3), ("step", C.c_double * 3), ("dims", C.c_int32 * 3), ("flags", C.c_uint32),
+                ("bias", C.c_double), ("reserved", C.c_uint32 * 2)]
+
+
+def probe_grid(origin, step, dims, visibility: bool = True, bias: float = 0.0) -> rt_probe_grid:
+    """rt_probe_grid from three floats each for origin and step and three ints for dims; the library checks
+    the values."""
+    return rt_probe_grid((C.c_double * 3)(*[float(v) for v in origin]), (C.c_double * 3)(*[float(v) for v in step]),
+                         (C.c_int32 * 3)(*[int(v) for v in dims]), RT_PROBE_GRID_VISIBILITY if visibility else 0,
+                         float(bias))
+
+
 class rt_hit(C.Structure):
     """One answer of rt_query_rays (Hit.cs): 48 B, offsets in include/rtcore.h."""
     _fields_ = [
@@ -259,7 +277,8 @@ _OPTIONAL = ("rt_query_rays", "rt_query_rays_device", "rt_camera_rays", "rt_sele
              "rt_adaptive_select_device", "rt_primary_hits_device", "rt_denoise_device", "rt_reproject_device",
              "rt_render_beams", "rt_render_beams_device", "rt_camera_beams",
              "rt_render_surfels", "rt_render_surfels_device", "rt_render_list", "rt_render_list_device",
-             "rt_occluded_surfels", "rt_occluded_surfels_device", "rt_render_probes", "rt_render_probes_device")
+             "rt_occluded_surfels", "rt_occluded_surfels_device", "rt_render_probes", "rt_render_probes_device",
+             "rt_probe_radiance_device", "rt_shade_probes", "rt_shade_probes_device")
 
 _lib: Optional[C.CDLL] = None
 
@@ -389,6 +408,19 @@ def load_library(path: str = "") -> C.CDLL:
         "rt_debug_sh_basis": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
         "rt_debug_probe_fold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, P(rt_probe_sh),
                                           P(C.c_uint32), P(C.c_uint32)]),
+        "rt_probe_radiance_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, rt_color, C.c_void_p,
+                                               C.c_void_p]),
+        "rt_debug_probe_radiance": (C.c_int, [P(rt_probe_sh), P(C.c_uint32), P(C.c_uint32), C.c_int64, rt_color,
+                                              P(C.c_double)]),
+        "rt_shade_probes_device": (C.c_int, [C.c_void_p, P(rt_probe_grid), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
+        "rt_shade_probes": (C.c_int, [C.c_void_p, P(rt_probe_grid), P(C.c_double), C.c_void_p, C.c_int64, P(rt_color),
+                                      P(C.c_double)]),
+        "rt_debug_probe_segments_device": (C.c_int, [P(rt_probe_grid), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p]),
+        "rt_debug_probe_segments": (C.c_int, [P(rt_probe_grid), C.c_void_p, C.c_int64, C.c_void_p, P(C.c_double)]),
+        "rt_debug_shade_probes": (C.c_int, [P(rt_probe_grid), P(C.c_double), C.c_void_p, C.c_int64, C.c_void_p,
+                                            P(rt_color), P(C.c_double)]),
         "rt_render_list": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                      C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, P(rt_color), P(C.c_uint32),
                                      P(C.c_uint32), P(C.c_double), P(C.c_uint32), P(C.c_uint64)]),
@@ -837,6 +869,87 @@ def sh_irradiance(L, normals) -> np.ndarray:
     sum over l of A_l L[l] Y_l(n), A = pi, 2 pi / 3 (l = 1 .. 3) and pi / 4 (l = 4 .. 8), the cosine lobe's
     zonal coefficients (Ramamoorthi and Hanrahan 2001); (..., 3).  Exact for radiance of bands 0 .. 2."""
     return np.einsum("...lc,...l->...c", np.asarray(L, np.float64), sh_basis(normals) * SH_COSINE_LOBE)
+
+
+def _ambient_arg(ambient) -> rt_color:
+    return ambient if isinstance(ambient, rt_color) else rt_color(*[float(v) for v in np.asarray(ambient, np.float64).reshape(3)])
+
+
+def probe_radiance_host(sh, samples, misses, ambient) -> np.ndarray:
+    """rt_debug_probe_radiance (host code, no GPU): probe_radiance_sh by the device pass's function compiled for
+    the CPU, bit for bit the same numbers, except that a probe without a sample is all NaN by an explicit
+    store.  sh (n, 9, 4), samples and misses (n,) -> L (n, 9, 3)."""
+    lib = load_library()
+    if not hasattr(lib, "rt_debug_probe_radiance"):
+        raise RtError("this build of the library has no rt_debug_probe_radiance")
+    c = np.ascontiguousarray(sh, np.float64)
+    if c.ndim != 3 or c.shape[1:] != (9, 4):
+        raise ValueError("sh must be an (n, 9, 4) array")
+    n = c.shape[0]
+    ns, nm = np.ascontiguousarray(samples, np.uint32), np.ascontiguousarray(misses, np.uint32)
+    if ns.shape != (n,) or nm.shape != (n,):
+        raise ValueError("samples and misses must be (n,) arrays")
+    L = np.zeros((n, 9, 3), np.float64)
+    _check(lib.rt_debug_probe_radiance(c.ctypes.data_as(C.POINTER(rt_probe_sh)), ns.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                       nm.ctypes.data_as(C.POINTER(C.c_uint32)), n, _ambient_arg(ambient),
+                                       L.ctypes.data_as(C.POINTER(C.c_double))))
+    return L
+
+
+def probe_radiance_device(d_sh, d_samples, d_misses, n: int, ambient, d_L, stream: int = 0) -> None:
+    """rt_probe_radiance_device: L (n x 9 x 3 doubles at d_L) from rt_render_probes' device accumulators, on the
+    current device, asynchronous on `stream`.  The device arrays as torch tensors or as pointers (integers)."""
+    lib = load_library()
+    if not hasattr(lib, "rt_probe_radiance_device"):
+        raise RtError("this build of the library has no rt_probe_radiance_device")
+    _check(lib.rt_probe_radiance_device(C.c_void_p(_ptr(d_sh)), C.c_void_p(_ptr(d_samples)), C.c_void_p(_ptr(d_misses)), n,
+                                        _ambient_arg(ambient), C.c_void_p(_ptr(d_L)), C.c_void_p(stream)))
+
+
+def _grid_L(grid: rt_probe_grid, L) -> np.ndarray:
+    """A grid's radiance as contiguous (n_probes, 9, 3) doubles; checked against the grid's dims."""
+    a = np.ascontiguousarray(L, np.float64)
+    n = int(grid.dims[0]) * int(grid.dims[1]) * int(grid.dims[2])
+    if a.size != n * 27 or a.shape[-2:] != (9, 3):
+        raise ValueError("L must hold nx * ny * nz probes of (9, 3) coefficients")
+    return a.reshape(n, 9, 3)
+
+
+def probe_segments_host(grid: rt_probe_grid, positions, normals) -> Tuple[np.ndarray, np.ndarray]:
+    """rt_debug_probe_segments (host code, no GPU): the eight visibility segments of every point, from the
+    point (pushed grid.bias along its unit normal) to each probe of its cell, as (rays (n, 8) RAY_DTYPE,
+    t_max (n, 8) f64); all zeros for a corner of weight 0, an invalid point or a grid without visibility."""
+    lib = load_library()
+    if not hasattr(lib, "rt_debug_probe_segments"):
+        raise RtError("this build of the library has no rt_debug_probe_segments")
+    pts = _pack_surfels(positions, normals)
+    n = pts.shape[0]
+    rays, t_max = np.zeros((n, 8), RAY_DTYPE), np.zeros((n, 8), np.float64)
+    _check(lib.rt_debug_probe_segments(C.byref(grid), pts.ctypes.data_as(C.c_void_p), n, rays.ctypes.data_as(C.c_void_p),
+                                       t_max.ctypes.data_as(C.POINTER(C.c_double))))
+    return rays, t_max
+
+
+def shade_probes_host(grid: rt_probe_grid, L, positions, normals, occluded=None) -> Tuple[np.ndarray, np.ndarray]:
+    """rt_debug_shade_probes (host code, no GPU): shade_probes' blend with the visibility answers given:
+    occluded (n, 8), true where occluded_rays answers True for the segment probe_segments_host reports, or
+    None for nothing hidden.  Returns (irradiance (n, 3), weight (n,))."""
+    lib = load_library()
+    if not hasattr(lib, "rt_debug_shade_probes"):
+        raise RtError("this build of the library has no rt_debug_shade_probes")
+    pts = _pack_surfels(positions, normals)
+    n = pts.shape[0]
+    coeffs = _grid_L(grid, L)
+    occ = None
+    if occluded is not None:
+        occ = np.ascontiguousarray(np.asarray(occluded) != 0, np.uint8)
+        if occ.shape != (n, 8):
+            raise ValueError("occluded must be (n, 8)")
+    irr, w = np.zeros((n, 3), np.float64), np.zeros(n, np.float64)
+    _check(lib.rt_debug_shade_probes(C.byref(grid), coeffs.ctypes.data_as(C.POINTER(C.c_double)),
+                                     pts.ctypes.data_as(C.c_void_p), n, occ.ctypes.data_as(C.c_void_p) if occ is not None else None,
+                                     irr.ctypes.data_as(C.POINTER(rt_color)), w.ctypes.data_as(C.POINTER(C.c_double))))
+    return irr, w
 
 
 def ambient_occlusion(occluded, samples) -> np.ndarray:
@@ -1291,6 +1404,56 @@ class GpuRaytracer:
         _check(self.lib.rt_render_probes_device(self.handle, C.c_void_p(_ptr(d_probes)), n, spp, seed, sample_base,
                                                 stream_base, C.c_void_p(_ptr(d_sh)), C.c_void_p(_ptr(d_samples)),
                                                 C.c_void_p(_ptr(d_misses)), C.c_void_p(_ptr(d_rays)), C.c_void_p(stream)))
+
+    def shade_probes(self, grid: rt_probe_grid, L, positions, normals) -> Tuple[np.ndarray, np.ndarray]:
+        """rt_shade_probes: the irradiance a grid of light probes (probe_grid; L (n_probes, 9, 3) as
+        probe_radiance_sh returns it, x fastest) gives at surface points: the trilinear blend of the cell's
+        eight probes, without those an any-hit query from the point cannot reach (grid.flags) or that hold a
+        NaN, then the nine-term dot product for the point's normal.  positions and normals as render_surfels
+        takes them.  Returns (irradiance (n, 3), weight (n,)): weight is the share of the trilinear weight that
+        contributed; 0 (and irradiance 0) where no probe did."""
+        if not hasattr(self.lib, "rt_shade_probes"):
+            raise RtError("this build of the library has no rt_shade_probes")
+        pts = _pack_surfels(positions, normals)
+        n = pts.shape[0]
+        coeffs = _grid_L(grid, L)
+        irr, w = np.zeros((n, 3), np.float64), np.zeros(n, np.float64)
+        _check(self.lib.rt_shade_probes(self.handle, C.byref(grid), coeffs.ctypes.data_as(C.POINTER(C.c_double)),
+                                        pts.ctypes.data_as(C.c_void_p), n, irr.ctypes.data_as(C.POINTER(rt_color)),
+                                        w.ctypes.data_as(C.POINTER(C.c_double))))
+        return irr, w
+
+    def shade_probes_device(self, grid: rt_probe_grid, d_L, d_points, n: int, d_irradiance, d_weight=0, stream: int = 0) -> None:
+        """rt_shade_probes_device: asynchronous shade_probes for n rt_surfel (64 B each) at d_points under the
+        grid's n_probes x 9 x 3 doubles at d_L, written to n x 3 doubles at d_irradiance and n doubles at
+        d_weight (0: not wanted) on `stream`.  The device arrays as torch tensors or as pointers (integers)."""
+        if not hasattr(self.lib, "rt_shade_probes_device"):
+            raise RtError("this build of the library has no rt_shade_probes_device")
+        _check(self.lib.rt_shade_probes_device(self.handle, C.byref(grid), C.c_void_p(_ptr(d_L)), C.c_void_p(_ptr(d_points)), n,
+                                               C.c_void_p(_ptr(d_irradiance)), C.c_void_p(_ptr(d_weight)), C.c_void_p(stream)))
+
+    def probe_segments_device(self, grid: rt_probe_grid, positions, normals) -> Tuple[np.ndarray, np.ndarray]:
+        """rt_debug_probe_segments_device on this scene's device: probe_segments_host's (rays, t_max) as the
+        device pass makes them, bit for bit the same."""
+        import torch
+
+        if not hasattr(self.lib, "rt_debug_probe_segments_device"):
+            raise RtError("this build of the library has no rt_debug_probe_segments_device")
+        pts = _pack_surfels(positions, normals)
+        n = pts.shape[0]
+        rays, t_max = np.zeros((n, 8), RAY_DTYPE), np.zeros((n, 8), np.float64)
+        with torch.cuda.device(self.device):
+            d_in = torch.from_numpy(pts.view(np.uint8).copy()).cuda()
+            d_rays = torch.zeros(max(rays.nbytes, 1), dtype=torch.uint8, device="cuda")
+            d_t = torch.zeros(max(n * 8, 1), dtype=torch.float64, device="cuda")
+            torch.cuda.synchronize()
+            _check(self.lib.rt_debug_probe_segments_device(C.byref(grid), C.c_void_p(d_in.data_ptr() if n else 0), n,
+                                                           C.c_void_p(d_rays.data_ptr()), C.c_void_p(d_t.data_ptr()), None))
+            torch.cuda.synchronize()
+            if n:
+                rays.view(np.uint8).reshape(-1)[:] = d_rays.cpu().numpy()[:rays.nbytes]
+                t_max.reshape(-1)[:] = d_t.cpu().numpy()[:n * 8]
+        return rays, t_max
 
     def surfel_rays(self, positions, normals, spp: int, seed: int, mode: int = RT_GATHER_DIFFUSE, sample_base: int = 0,
                     stream_base: int = 0) -> np.ndarray:

@@ -44,27 +44,6 @@ int fill_query(rt_scene* s, int kernel, int blocks_per_cu, const rt_ray* d_rays,
     return RT_OK;
 }
 
-} // namespace rtc
-
-namespace {
-
-// One launch over n <= kQueryLaunchMax rays on `st`, after the stream ordering is settled.
-int launch_rays(rt_scene* s, int32_t mode, const rt_ray* d_rays, unsigned n, rt_hit* d_hits, hipStream_t st)
-{
-    if (mode == RT_QUERY_EXACT) {
-        HIP_TRY(launch_query_exact(s->dev, d_rays, n, d_hits, st));
-        return RT_OK;
-    }
-    const int kernel = query_kernel(s);
-    QueryParams p{};
-    int grid = 0;
-    const int rc = fill_query(s, kernel, query_blocks_per_cu(kernel), d_rays, n, st, p, grid);
-    if (rc != RT_OK) return rc;
-    p.hits = reinterpret_cast<float4*>(d_hits);
-    HIP_TRY(launch_query(p, kernel, grid, st));
-    return RT_OK;
-}
-
 // rt_occluded_rays: one launch over n <= kQueryLaunchMax segments (d_t_max null: rays).
 int launch_segments(rt_scene* s, int32_t mode, const rt_ray* d_rays, const double* d_t_max, unsigned n,
                     unsigned char* d_out, hipStream_t st)
@@ -86,6 +65,27 @@ int launch_segments(rt_scene* s, int32_t mode, const rt_ray* d_rays, const doubl
     p.early = 1;
     if (const char* e = getenv("RTCORE_OCCLUDED_EARLY")) p.early = atoi(e) != 0;
     HIP_TRY(launch_occluded(p, kernel, grid, st));
+    return RT_OK;
+}
+
+} // namespace rtc
+
+namespace {
+
+// One launch over n <= kQueryLaunchMax rays on `st`, after the stream ordering is settled.
+int launch_rays(rt_scene* s, int32_t mode, const rt_ray* d_rays, unsigned n, rt_hit* d_hits, hipStream_t st)
+{
+    if (mode == RT_QUERY_EXACT) {
+        HIP_TRY(launch_query_exact(s->dev, d_rays, n, d_hits, st));
+        return RT_OK;
+    }
+    const int kernel = query_kernel(s);
+    QueryParams p{};
+    int grid = 0;
+    const int rc = fill_query(s, kernel, query_blocks_per_cu(kernel), d_rays, n, st, p, grid);
+    if (rc != RT_OK) return rc;
+    p.hits = reinterpret_cast<float4*>(d_hits);
+    HIP_TRY(launch_query(p, kernel, grid, st));
     return RT_OK;
 }
 

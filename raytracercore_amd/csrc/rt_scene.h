@@ -1,6 +1,6 @@
 // rt_scene.h -- the scene object behind the C ABI and what the API's translation units share
 // (rtcore_api.hip, scene_upload.hip, api_frame.hip, api_debug.hip, api_query.hip, api_select.hip, api_render_rays.hip,
-// api_render_pixels.hip, api_render_probes.hip, chunk_pipeline.hip, api_adaptive.hip, api_denoise.hip, api_reproject.hip).
+// api_render_pixels.hip, api_render_probes.hip, api_shade_probes.hip, chunk_pipeline.hip, api_adaptive.hip, api_denoise.hip, api_reproject.hip).
 #pragma once
 #include <algorithm>
 #include <array>
@@ -197,6 +197,13 @@ struct rt_scene {
     // rt_primary_hits_device: one chunk of camera rays, made and read on the caller's stream (its own
     // buffer: rt_query_rays fills query_rays from its copy stream)
     DevBuf<rt_ray> primary_rays;
+    // rt_shade_probes_device: one chunk's eight segments per point, their ends and the any-hit answers, made
+    // and read on the caller's stream; rt_shade_probes: the grid's L, one chunk of points and its results
+    DevBuf<rt_ray> probe_seg_rays;
+    DevBuf<double> probe_seg_t_max;
+    DevBuf<unsigned char> probe_seg_occluded;
+    DevBuf<double> shade_L, shade_out;
+    DevBuf<rt_surfel> shade_points;
     // run_items: the blocks per CU of each ItemSource's instance of `items_variant`
     int items_variant[ITEMS_SURFELS + 1] = {-1, -1, -1, -1, -1}, items_blocks_per_cu[ITEMS_SURFELS + 1] = {1, 1, 1, 1, 1};
     // the selection pass (api_select.hip): the caller's item list on the device, and the host-buffer
@@ -400,6 +407,10 @@ int query_kernel(const rt_scene* s);
 // kernel's ray dispenser is zeroed on `st` and its overflow area reserved.
 int fill_query(rt_scene* s, int kernel, int blocks_per_cu, const rt_ray* d_rays, unsigned n, hipStream_t st, QueryParams& p,
                int& grid);
+// rt_occluded_rays' launch over n <= kQueryLaunchMax segments on `st` (d_t_max null: rays), after the stream
+// ordering is settled; rt_shade_probes_device (api_shade_probes.hip) runs it over the segments it makes.
+int launch_segments(rt_scene* s, int32_t mode, const rt_ray* d_rays, const double* d_t_max, unsigned n, unsigned char* d_out,
+                    hipStream_t st);
 // api_render_pixels.hip: rt_render_pixels' list check (every entry below npix, none twice); null, or
 // what is wrong with entry *at
 const char* check_pixel_list(const uint32_t* pixels, int64_t n, uint64_t npix, int64_t* at);
