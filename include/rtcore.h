@@ -59,7 +59,10 @@ extern "C" {
                                    rt_render_probes_device, rt_debug_sh_basis and rt_debug_probe_fold, and
                                    rt_probe_grid, rt_probe_radiance_device, rt_debug_probe_radiance,
                                    rt_shade_probes, rt_shade_probes_device, rt_debug_probe_segments,
-                                   rt_debug_probe_segments_device and rt_debug_shade_probes */
+                                   rt_debug_probe_segments_device and rt_debug_shade_probes, and
+                                   rt_probe_moments, rt_probe_select_params, rt_render_probe_list_device,
+                                   rt_probe_select_device, rt_debug_probe_moments, rt_debug_probe_select and
+                                   rt_debug_probe_error */
 
 typedef enum rt_status {
     RT_OK = 0,
@@ -930,6 +933,117 @@ int rt_debug_sh_basis(const double* dirs_xyz, int64_t n, double* y9_out);
    RT_ERR_ARG for n < 0, spp <= 0 or a null pointer with n > 0. */
 int rt_debug_probe_fold(const rt_ray* rays, const float* rgb, const uint8_t* miss, int64_t n, int32_t spp,
                         rt_probe_sh* sh, uint32_t* samples, uint32_t* misses);
+
+/*
+ * Adaptive light probes: more samples of only the listed probes of a resident array, with the second
+ * moments of each probe's band-0/1 luminance coefficients, and the pass that turns those into the next list --
+ * what rt_render_pixels and rt_adaptive_select_device are to a frame.  A probe in a closed, evenly lit corner
+ * then stops after a fraction of the samples a probe beside a light needs.  A probe's work item is exactly
+ * one sample, so unlike rt_render_list's batch moments these are exact per-sample sums, independent of spp,
+ * and the misses' share is kept apart from the ambient colour as c[.][3] keeps it apart in the sums.
+ *
+ * The moments (normative).  rt_probe_moments rows l = 0 .. 3 are bands 0 and 1, in the order of Y0 .. Y3.
+ * Everything is added to what the array holds, per probe in sample order, fp64, every operation rounded on
+ * its own, no fused multiply-add; the direction and Y are the fold's:
+ *   a hit:          y = (0.299 * (double)col_r + 0.587 * (double)col_g) + 0.114 * (double)col_b, left to right
+ *                   (rt_render_pixels' Y_j);  x = y * Y_l;  m[l][0] = m[l][0] + x * x, the product rounded,
+ *                   then the sum
+ *   a primary miss: m[l][1] = m[l][1] + Y_l * Y_l
+ *   a sample of an invalid probe adds nothing.
+ * Column 1 stays free of the ambient colour: a hit and a miss are disjoint, so the sum of squares of
+ * x_l = Y_l * (hit ? y : A) is m[l][0] + A * A * m[l][1] for any ambient luminance A.
+ *
+ * rt_render_probe_list_device: rt_render_probes_device for a list of entry numbers into n_records probes
+ * resident at d_probes.  d_index holds n entries e = d_index[j]; NULL is the identity list, and n must then
+ * equal n_records.  Everything is added at entry e: d_sh, d_samples, d_misses and d_moments (which may be
+ * NULL) have n_records elements.  Sample k of entry e draws from (seed, stream_base + e, sample_base + k): it
+ * is rt_render_probes' sample k of probe e.
+ * What is promised (normative):
+ *   1. With the identity list and no moments, the result is rt_render_probes_device's bit for bit from equal
+ *      accumulator contents.
+ *   2. d_sh, d_samples, d_misses and the ray count are the same with and without d_moments.
+ *   3. d_moments equals rt_debug_probe_moments over the reported rays and the per-sample rt_render_rays
+ *      results (rt_debug_probe_fold's inputs), bit for bit.
+ *   4. An entry's accumulators depend on (seed, stream_base + e, the sample indices, the record, the traversal
+ *      mode) only: not on n, on n_records, on the entry's place in the list or on the stream.
+ *   5. One call of a + b samples equals a call of a samples followed by a call of b samples at
+ *      sample_base + a, bit for bit, moments included.
+ *   6. An entry >= n_records is skipped: not traced, nothing written.  An entry named twice is undefined (its
+ *      accumulators are updated by two threads).
+ * Bounds and errors.  rt_render_probes_device's with n as the list length: RT_ERR_ARG for a null scene, n < 0,
+ * spp <= 0; then, for n > 0, a null d_probes, d_sh, d_samples or d_misses, n_records <= 0, n_records >= 2^32,
+ * a null index with n != n_records, and 64 * ceil(n / 64) * P > 2^26, P = spp rounded up to a power of two.
+ * RT_ERR_STATE on a BVH2 scene.  n == 0 returns RT_OK and touches nothing.  Always the generic kernels; the
+ * counters of rt_scene_get_stats, an armed rt_debug_ray_log, rt_kernel_times and the scene-specialised kernels
+ * are left as they were; no camera needed; asynchronous on `stream`, ordered like the device-resident renders.
+ * Not part of it: an entry over host buffers.  The adaptive loop is device-resident by nature (its list never
+ * leaves the device), and rt_render_probes stays the host entry.
+ *
+ * The rule (normative).  Everything is fp64, every operation is rounded on its own, division and square root
+ * are IEEE.  With a probe's c = rt_probe_sh, m = rt_probe_moments, samples, misses, and the parameters P:
+ *   N  = samples + misses (64 bits), n = (double)N
+ *   A  = (0.299 * ambient.r + 0.587 * ambient.g) + 0.114 * ambient.b          AA = A * A
+ *   for l = 0 .. 3:
+ *     S_l = ((0.299 * c[l][0] + 0.587 * c[l][1]) + 0.114 * c[l][2]) + A * c[l][3]
+ *     T_l = m[l][0] + AA * m[l][1]
+ *     u_l = T_l - (S_l * S_l) / n      d_l = u_l / (n - 1.0)
+ *     v_l = u_l > (n * 2^-49) * T_l ? d_l : 0   (so 0 for a NaN)
+ *   The guard: T_l and S_l^2 / n are each n rounded additions and differ by up to (3 n + 13) 2^-53 T_l of rounding
+ *   alone; a difference not above n 2^-49 T_l is that rounding and not variance.  A probe whose coefficient l is the
+ *   same for every sample has v_l = 0 exactly; a relative variance below n 2^-49 cannot be told from it.
+ *   a0 = 3.141592653589793 * K0     a1 = 2.0943951023931953 * K1     p4 = 4.0 * 3.141592653589793
+ *   level = ((p4 * a0) * S_0) / n
+ *   se    = p4 * sqrt(((a0 * a0) * v_0 + (a1 * a1) * ((v_1 + v_2) + v_3)) / n)
+ * level is the luminance of the irradiance the probe gives averaged over all normals; se estimates the
+ * standard error of the band-0/1 irradiance a diffuse receiver reads, with the covariances between the
+ * coefficients left out: an estimate, not a bound.  active(probe) is, in this order:
+ *   1. N < min_samples   -> 1
+ *   2. N >= max_samples  -> 0
+ *   3. N < 2             -> 1
+ *   4. a d_l is NaN      -> 0
+ *   5. otherwise  se > rel_tol * (level > irr_floor ? level : irr_floor)
+ * So a NaN in c[0..3] or in m makes the probe inactive: it cannot converge, so it is not sampled for ever.  An
+ * invalid probe (all misses in no direction: c = m = 0) has se = 0 and stops at min_samples.
+ * rt_probe_select_device: the active entries' numbers into d_list in ascending order, from accumulators of
+ * n_records probes, on the calling thread's current device, asynchronous on `stream`.  *d_count receives the
+ * number of active entries, also when it exceeds cap; then only the first cap are stored.  Deterministic as
+ * rt_adaptive_select_device (a ballot per 64 entries, an exclusive scan, the write by ballot prefix), whose
+ * per-device temporary counts it shares; calls on one device are serialised by the caller.  RT_ERR_ARG for a
+ * null pointer (d_list may be NULL with cap = 0), rel_tol NaN or negative, irr_floor NaN or not above 0,
+ * n_records <= 0 or >= 2^32.
+ * rt_debug_probe_select: the host twin (host only): the same arguments on host arrays, the same rule
+ * function; returns the count (at most cap entries stored), or a negative rt_status.
+ * rt_debug_probe_error: host only; se_out[i] and level_out[i] of probe i as step 5 reads them, a quiet NaN
+ * each where N < 2.  RT_ERR_ARG for a null params, n < 0 or a null pointer with n > 0.
+ */
+typedef struct rt_probe_moments {   /* 64 B per probe */
+    double m[4][2];                 /* [l][0]: hits' sum of (y Y_l)^2; [l][1]: primary misses' sum of Y_l^2 */
+} rt_probe_moments;
+typedef struct rt_probe_select_params {   /* 48 B */
+    double   rel_tol;      /* converged when se <= rel_tol * max(level, irr_floor)                  */
+    double   irr_floor;    /* > 0; keeps dark probes from never converging                          */
+    rt_color ambient;      /* the ambient colour rt_probe_radiance_device is given for these probes */
+    uint32_t min_samples;  /* a probe with N < min_samples is always active                         */
+    uint32_t max_samples;  /* a probe with N >= max_samples is never active                         */
+} rt_probe_select_params;
+int rt_render_probe_list_device(rt_scene* scene, const rt_surfel* d_probes, int64_t n_records, const uint32_t* d_index,
+                                int64_t n, int32_t spp, uint64_t seed, uint64_t sample_base, uint64_t stream_base,
+                                rt_probe_sh* d_sh, uint32_t* d_samples, uint32_t* d_misses,
+                                rt_probe_moments* d_moments /* may be NULL */, unsigned long long* d_rays_count,
+                                void* stream);
+/* Host only, no device: the moments above over rt_debug_probe_fold's inputs (same layout and conventions),
+   added into moments (n).  RT_ERR_ARG for n < 0, spp <= 0 or a null pointer with n > 0. */
+int rt_debug_probe_moments(const rt_ray* rays, const float* rgb, const uint8_t* miss, int64_t n, int32_t spp,
+                           rt_probe_moments* moments);
+int rt_probe_select_device(const rt_probe_select_params* params, const rt_probe_sh* d_sh, const uint32_t* d_samples,
+                           const uint32_t* d_misses, const rt_probe_moments* d_moments, int64_t n_records,
+                           uint32_t* d_list, uint32_t cap, uint32_t* d_count, void* stream);
+int64_t rt_debug_probe_select(const rt_probe_select_params* params, const rt_probe_sh* sh, const uint32_t* samples,
+                              const uint32_t* misses, const rt_probe_moments* moments, int64_t n_records,
+                              uint32_t* list, uint32_t cap);
+int rt_debug_probe_error(const rt_probe_select_params* params, const rt_probe_sh* sh, const uint32_t* samples,
+                         const uint32_t* misses, const rt_probe_moments* moments, int64_t n, double* se_out,
+                         double* level_out);
 
 /*
  * Probe grids: the irradiance a regular grid of such probes gives at shading points, on the device.  Per

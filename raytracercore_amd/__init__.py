@@ -159,6 +159,18 @@ class rt_probe_sh(C.Structure):
     _fields_ = [("c", (C.c_double * 4) * 9)]
 
 
+class rt_probe_moments(C.Structure):
+    """64 B: the second moments of a probe's band-0/1 luminance coefficients, rows l = 0 .. 3 of (the hits' sum
+    of (y Y_l)^2, the primary misses' sum of Y_l^2) (rt_render_probe_list_device)."""
+    _fields_ = [("m", (C.c_double * 2) * 4)]
+
+
+class rt_probe_select_params(C.Structure):
+    """The selection rule of adaptive light probes (rt_probe_select_device), 48 B."""
+    _fields_ = [("rel_tol", C.c_double), ("irr_floor", C.c_double), ("ambient", rt_color), ("min_samples", C.c_uint32),
+                ("max_samples", C.c_uint32)]
+
+
 RT_PROBE_GRID_VISIBILITY = 1  # rt_probe_grid.flags: leave out the probes the point cannot see
 
 
@@ -264,6 +276,7 @@ RAY_DTYPE = np.dtype([("origin", np.float64, (4,)), ("direction", np.float64, (4
 BEAM_DTYPE = np.dtype([(f, np.float64, (4,)) for f in
                        ("origin", "direction", "origin_du", "origin_dv", "direction_du", "direction_dv")])
 SURFEL_DTYPE = np.dtype([("position", np.float64, (4,)), ("normal", np.float64, (4,))])
+PROBE_MOMENTS_DTYPE = np.dtype([("m", np.float64, (4, 2))])  # rt_probe_moments
 HIT_DTYPE = np.dtype([
     ("prim_id", np.int32), ("inside", np.int32), ("distance", np.float64),
     ("position", np.float32, (3,)), ("normal", np.float32, (3,)), ("reserved", np.int32, (2,)),
@@ -278,7 +291,8 @@ _OPTIONAL = ("rt_query_rays", "rt_query_rays_device", "rt_camera_rays", "rt_sele
              "rt_render_beams", "rt_render_beams_device", "rt_camera_beams",
              "rt_render_surfels", "rt_render_surfels_device", "rt_render_list", "rt_render_list_device",
              "rt_occluded_surfels", "rt_occluded_surfels_device", "rt_render_probes", "rt_render_probes_device",
-             "rt_probe_radiance_device", "rt_shade_probes", "rt_shade_probes_device")
+             "rt_probe_radiance_device", "rt_shade_probes", "rt_shade_probes_device", "rt_render_probe_list_device",
+             "rt_probe_select_device")
 
 _lib: Optional[C.CDLL] = None
 
@@ -408,6 +422,15 @@ def load_library(path: str = "") -> C.CDLL:
         "rt_debug_sh_basis": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
         "rt_debug_probe_fold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, P(rt_probe_sh),
                                           P(C.c_uint32), P(C.c_uint32)]),
+        "rt_render_probe_list_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
+                                                  C.c_uint64, C.c_uint64, C.c_uint64] + [C.c_void_p] * 6),
+        "rt_debug_probe_moments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+        "rt_probe_select_device": (C.c_int, [P(rt_probe_select_params)] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p,
+                                             C.c_uint32, C.c_void_p, C.c_void_p]),
+        "rt_debug_probe_select": (C.c_int64, [P(rt_probe_select_params)] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p,
+                                              C.c_uint32]),
+        "rt_debug_probe_error": (C.c_int, [P(rt_probe_select_params)] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p,
+                                           C.c_void_p]),
         "rt_probe_radiance_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, rt_color, C.c_void_p,
                                                C.c_void_p]),
         "rt_debug_probe_radiance": (C.c_int, [P(rt_probe_sh), P(C.c_uint32), P(C.c_uint32), C.c_int64, rt_color,
@@ -904,6 +927,93 @@ def probe_radiance_device(d_sh, d_samples, d_misses, n: int, ambient, d_L, strea
         raise RtError("this build of the library has no rt_probe_radiance_device")
     _check(lib.rt_probe_radiance_device(C.c_void_p(_ptr(d_sh)), C.c_void_p(_ptr(d_samples)), C.c_void_p(_ptr(d_misses)), n,
                                         _ambient_arg(ambient), C.c_void_p(_ptr(d_L)), C.c_void_p(stream)))
+
+
+def probe_moments_host(rays, rgb, miss, out=None) -> np.ndarray:
+    """rt_debug_probe_moments (host code, no GPU): render_probe_list_device's moments over probe_fold_host's
+    inputs (rays (n, spp) of RAY_DTYPE, rgb (n, spp, 3), miss (n, spp)).  Returns the moments f64 [n, 4, 2], new
+    or the caller's `out`, which the call adds into."""
+    lib = load_library()
+    if not hasattr(lib, "rt_debug_probe_moments"):
+        raise RtError("this build of the library has no rt_debug_probe_moments")
+    r = np.ascontiguousarray(rays, RAY_DTYPE)
+    if r.ndim != 2:
+        raise ValueError("rays must be an (n, spp) RAY_DTYPE array")
+    n, spp = r.shape
+    col = np.ascontiguousarray(rgb, np.float32)
+    ms = np.ascontiguousarray(np.asarray(miss) != 0, np.uint8)
+    if col.shape != (n, spp, 3) or ms.shape != (n, spp):
+        raise ValueError("rgb must be (n, spp, 3) and miss (n, spp)")
+    mom = np.zeros((n, 4, 2), np.float64) if out is None else out
+    if mom.shape != (n, 4, 2) or mom.dtype != np.float64 or not mom.flags.c_contiguous:
+        raise ValueError("out must be a C-contiguous f64 [n, 4, 2] array")
+    _check(lib.rt_debug_probe_moments(r.ctypes.data_as(C.c_void_p), col.ctypes.data_as(C.c_void_p),
+                                      ms.ctypes.data_as(C.c_void_p), n, spp, mom.ctypes.data_as(C.c_void_p)))
+    return mom
+
+
+def probe_select_params(rel_tol: float, min_samples: int, max_samples: int, ambient=(0.0, 0.0, 0.0),
+                        irr_floor: float = 1e-3) -> rt_probe_select_params:
+    """rt_probe_select_params; ambient as three floats or an rt_color.  The library checks the values."""
+    return rt_probe_select_params(float(rel_tol), float(irr_floor), _ambient_arg(ambient), int(min_samples), int(max_samples))
+
+
+def _probe_acc_host(sh, samples, misses, moments):
+    c = np.ascontiguousarray(sh, np.float64)
+    if c.ndim != 3 or c.shape[1:] != (9, 4):
+        raise ValueError("sh must be an (n, 9, 4) array")
+    n = c.shape[0]
+    ns, nm = np.ascontiguousarray(samples, np.uint32), np.ascontiguousarray(misses, np.uint32)
+    mom = np.ascontiguousarray(moments, np.float64)
+    if ns.shape != (n,) or nm.shape != (n,) or mom.shape != (n, 4, 2):
+        raise ValueError("samples and misses must be (n,) arrays and moments (n, 4, 2)")
+    return c, ns, nm, mom, n
+
+
+def probe_select_device(params: rt_probe_select_params, d_sh, d_samples, d_misses, d_moments, n_records: int, d_list,
+                        cap: int, d_count, stream: int = 0) -> None:
+    """rt_probe_select_device: from n_records probes' device accumulators (render_probe_list_device's) the
+    entry numbers of the probes that still need samples, ascending, into d_list (at most cap), their number into
+    the uint32 at d_count.  Works on the current device; asynchronous on `stream`.  The device arrays as torch
+    tensors or as pointers (integers)."""
+    lib = load_library()
+    if not hasattr(lib, "rt_probe_select_device"):
+        raise RtError("this build of the library has no rt_probe_select_device")
+    _check(lib.rt_probe_select_device(C.byref(params), C.c_void_p(_ptr(d_sh)), C.c_void_p(_ptr(d_samples)),
+                                      C.c_void_p(_ptr(d_misses)), C.c_void_p(_ptr(d_moments)), n_records,
+                                      C.c_void_p(0 if d_list is None else _ptr(d_list)), cap, C.c_void_p(_ptr(d_count)),
+                                      C.c_void_p(stream)))
+
+
+def probe_select_host(params: rt_probe_select_params, sh, samples, misses, moments,
+                      cap: Optional[int] = None) -> Tuple[np.ndarray, int]:
+    """rt_debug_probe_select, the host twin of probe_select_device (no GPU): sh (n, 9, 4), samples and misses
+    (n,), moments (n, 4, 2).  Returns (the first min(count, cap) list entries, count)."""
+    lib = load_library()
+    if not hasattr(lib, "rt_debug_probe_select"):
+        raise RtError("this build of the library has no rt_debug_probe_select")
+    c, ns, nm, mom, n = _probe_acc_host(sh, samples, misses, moments)
+    cap = n if cap is None else int(cap)
+    out = np.zeros(max(cap, 1), np.uint32)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    k = lib.rt_debug_probe_select(C.byref(params), ptr(c), ptr(ns), ptr(nm), ptr(mom), n, ptr(out), cap)
+    if k < 0:
+        _check(int(k))
+    return out[:min(int(k), cap)].copy(), int(k)
+
+
+def probe_error(params: rt_probe_select_params, sh, samples, misses, moments) -> Tuple[np.ndarray, np.ndarray]:
+    """rt_debug_probe_error (host code, no GPU): (se, level) per probe as the selection rule's last step reads
+    them: the estimated standard error of the band-0/1 irradiance and its mean luminance; NaN where a probe has
+    fewer than two samples."""
+    lib = load_library()
+    if not hasattr(lib, "rt_debug_probe_error"):
+        raise RtError("this build of the library has no rt_debug_probe_error")
+    c, ns, nm, mom, n = _probe_acc_host(sh, samples, misses, moments)
+    se, level = np.zeros(n, np.float64), np.zeros(n, np.float64)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    _check(lib.rt_debug_probe_error(C.byref(params), ptr(c), ptr(ns), ptr(nm), ptr(mom), n, ptr(se), ptr(level)))
+    return se, level
 
 
 def _grid_L(grid: rt_probe_grid, L) -> np.ndarray:
@@ -1404,6 +1514,86 @@ class GpuRaytracer:
         _check(self.lib.rt_render_probes_device(self.handle, C.c_void_p(_ptr(d_probes)), n, spp, seed, sample_base,
                                                 stream_base, C.c_void_p(_ptr(d_sh)), C.c_void_p(_ptr(d_samples)),
                                                 C.c_void_p(_ptr(d_misses)), C.c_void_p(_ptr(d_rays)), C.c_void_p(stream)))
+
+    def render_probe_list_device(self, d_probes, n_records: int, d_index, n: int, spp: int, seed: int, sample_base: int,
+                                 stream_base: int, d_sh, d_samples, d_misses, d_moments=0, d_rays=0, stream: int = 0) -> None:
+        """rt_render_probe_list_device: asynchronous probes for the n entries listed (uint32 entry numbers at
+        d_index, or None: every entry, n == n_records) of the n_records rt_surfel resident at d_probes, added at
+        the entry into n_records rt_probe_sh at d_sh, uint32 each at d_samples and d_misses and, where given,
+        rt_probe_moments (64 B each: [n_records, 4, 2] doubles) at d_moments (d_rays: one uint64 ray counter or
+        0) on `stream`; 64 * ceil(n / 64) * (spp rounded up to a power of two) must not pass 2^26.  The device
+        arrays as torch tensors or as pointers (integers)."""
+        if not hasattr(self.lib, "rt_render_probe_list_device"):
+            raise RtError("this build of the library has no rt_render_probe_list_device")
+        _check(self.lib.rt_render_probe_list_device(self.handle, C.c_void_p(_ptr(d_probes)), n_records,
+                                                    C.c_void_p(0 if d_index is None else _ptr(d_index)), n, spp, seed,
+                                                    sample_base, stream_base, C.c_void_p(_ptr(d_sh)),
+                                                    C.c_void_p(_ptr(d_samples)), C.c_void_p(_ptr(d_misses)),
+                                                    C.c_void_p(_ptr(d_moments)), C.c_void_p(_ptr(d_rays)),
+                                                    C.c_void_p(stream)))
+
+    def bake_probes_adaptive(self, positions, rel_tol: float, min_spp: int, max_spp: int, batch_spp: int, seed: int = 0,
+                             normals=None, ambient=None, irr_floor: float = 1e-3, stream_base: int = 0,
+                             sample_base: int = 0):
+        """gather_adaptive's loop for light probes: render until the estimated standard error of every probe's
+        band-0/1 irradiance is at most rel_tol of its mean luminance (rtcore.h, "adaptive light probes"), with
+        the probes, the accumulators and the list held on this scene's device.  Each iteration:
+        rt_probe_select_device builds the ascending list of probes that still need samples; the list's length
+        is read (one 4-byte copy, the loop's only synchronisation); rt_render_probe_list_device adds batch_spp
+        samples of the listed probes at sample_base + iteration * batch_spp.  The loop stops when the list is
+        empty.  A probe that leaves the list never comes back (its accumulators no longer change), so every
+        listed probe has N = iteration * batch_spp.  min_spp and max_spp are rounded up to multiples of
+        batch_spp.  positions and normals as render_probes takes them; ambient (three floats or an rt_color)
+        defaults to the scene's.
+        Returns device tensors sh (n, 9, 4) f64, samples, misses (n,) i32 (the uint32 bits), moments (n, 4, 2)
+        f64, spp (n,) i64, and counts, lists, rays, params."""
+        import torch
+
+        if batch_spp <= 0 or min_spp <= 0 or max_spp < min_spp:
+            raise ValueError("need batch_spp > 0 and 0 < min_spp <= max_spp")
+        if normals is None and not (isinstance(positions, np.ndarray) and positions.dtype == SURFEL_DTYPE):
+            pos = np.asarray(positions, np.float64)
+            normals = np.zeros_like(pos)
+            if pos.ndim == 2 and pos.shape[1] >= 3:
+                normals[:, 2] = 1.0
+        probes = _pack_surfels(positions, normals)
+        n = probes.shape[0]
+        if n == 0:
+            raise ValueError("no probes")
+        if ambient is None:
+            ambient = self.params.ambient
+        up = lambda v: -(-int(v) // batch_spp) * batch_spp  # noqa: E731
+        par = probe_select_params(rel_tol, up(min_spp), up(max_spp), ambient, irr_floor)
+        dev = torch.device("cuda", self.device)
+        with torch.cuda.device(dev):
+            d_probes = torch.from_numpy(probes.view(np.uint8).copy()).to(dev)
+            acc = {"sh": torch.zeros((n, 9, 4), dtype=torch.float64, device=dev),
+                   "samples": torch.zeros(n, dtype=torch.int32, device=dev),
+                   "misses": torch.zeros(n, dtype=torch.int32, device=dev),
+                   "moments": torch.zeros((n, 4, 2), dtype=torch.float64, device=dev)}
+            d_count = torch.zeros(1, dtype=torch.int32, device=dev)
+            d_rays = torch.zeros(1, dtype=torch.int64, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            counts, lists = [], []
+            while True:
+                lst = torch.empty(n if not counts else counts[-1], dtype=torch.int32, device=dev)
+                probe_select_device(par, acc["sh"], acc["samples"], acc["misses"], acc["moments"], n, lst, lst.numel(),
+                                    d_count, stream=stream)
+                m = int(d_count.item()) & 0xFFFFFFFF
+                if m == 0:
+                    break
+                if m > lst.numel():
+                    raise RtError("bake_probes_adaptive: the list of active probes grew")
+                lst = lst[:m]
+                self.render_probe_list_device(d_probes, n, lst, m, batch_spp, seed,
+                                              int(sample_base) + len(counts) * batch_spp, stream_base, acc["sh"],
+                                              acc["samples"], acc["misses"], acc["moments"], d_rays, stream)
+                counts.append(m)
+                lists.append(lst)
+            torch.cuda.synchronize(dev)
+        acc["spp"] = acc["samples"].to(torch.int64) + acc["misses"].to(torch.int64)
+        acc.update(counts=counts, lists=lists, rays=int(d_rays.item()), params=par)
+        return acc
 
     def shade_probes(self, grid: rt_probe_grid, L, positions, normals) -> Tuple[np.ndarray, np.ndarray]:
         """rt_shade_probes: the irradiance a grid of light probes (probe_grid; L (n_probes, 9, 3) as

@@ -3,9 +3,9 @@
 // of pixels that still need samples, in the path kernels' 8x8 block order, and its host twin, the same
 // rule function compiled for the CPU.
 #include <cmath>
-#include <mutex>
 
 #include "rt_scene.h"
+#include "select_scan.h"
 
 namespace {
 
@@ -114,16 +114,6 @@ __global__ void __launch_bounds__(256) adaptive_write_kernel(SelectArgs A, const
     pixels[at] = (uint32_t)(by * 8 + (lane >> 3)) * (uint32_t)A.w + (uint32_t)(bx * 8 + (lane & 7));
 }
 
-// The pass's temporary memory, the library's own, one per device: a mask and a count per 8x8 block.
-// Calls on one device share it, so a call on another stream than the last is ordered after it.
-struct SelectScratch {
-    unsigned long long* masks = nullptr;
-    unsigned int* counts = nullptr;
-    size_t blocks = 0;
-    hipEvent_t done = nullptr;
-    hipStream_t last = nullptr;
-    bool any = false;
-};
 constexpr int kMaxDevices = 64;
 SelectScratch g_scratch[kMaxDevices]; // (never freed: the runtime may be gone when statics are destroyed)
 std::mutex g_scratch_mutex;
@@ -146,6 +136,51 @@ int check_select(const char* name, const rt_adaptive_params* P, const void* sum,
 
 } // namespace
 
+namespace rtc {
+
+int select_begin(const char* name, size_t n_blocks, hipStream_t st, SelectPass& pass)
+{
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev < 0 || dev >= kMaxDevices) {
+        set_error(std::string(name) + ": device index out of range");
+        return RT_ERR_ARG;
+    }
+    pass.lock = std::unique_lock<std::mutex>(g_scratch_mutex);
+    SelectScratch& S = g_scratch[dev];
+    pass.S = &S;
+    if (!S.done) HIP_TRY(hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
+    if (n_blocks > S.blocks) { // (hipFree waits for the device, so no queued pass still reads the old arrays)
+        if (S.masks) (void)hipFree(S.masks);
+        if (S.counts) (void)hipFree(S.counts);
+        S.masks = nullptr;
+        S.counts = nullptr;
+        S.blocks = 0;
+        HIP_TRY(hipMalloc(&S.masks, n_blocks * sizeof(unsigned long long)));
+        HIP_TRY(hipMalloc(&S.counts, n_blocks * sizeof(unsigned int)));
+        S.blocks = n_blocks;
+    }
+    if (S.any && st != S.last) HIP_TRY(hipStreamWaitEvent(st, S.done, 0));
+    return RT_OK;
+}
+
+void select_scan(SelectPass& pass, int n_blocks, unsigned int* d_total, hipStream_t st)
+{
+    hipLaunchKernelGGL(adaptive_scan_kernel, dim3(1), dim3(1024), 0, st, pass.S->counts, n_blocks, d_total);
+}
+
+int select_end(SelectPass& pass, hipStream_t st)
+{
+    SelectScratch& S = *pass.S;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(S.done, st));
+    S.last = st;
+    S.any = true;
+    return RT_OK;
+}
+
+} // namespace rtc
+
 extern "C" {
 
 int rt_adaptive_select_device(const rt_adaptive_params* P, const double* d_sum, const uint32_t* d_samples,
@@ -159,39 +194,19 @@ int rt_adaptive_select_device(const rt_adaptive_params* P, const double* d_sum, 
         set_error("rt_adaptive_select_device: bad argument (null pointer)");
         return RT_ERR_ARG;
     }
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev < 0 || dev >= kMaxDevices) {
-        set_error("rt_adaptive_select_device: device index out of range");
-        return RT_ERR_ARG;
-    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     SelectArgs A{*P, d_sum, d_samples, d_misses, d_q, d_batches, plane ? (size_t)plane : (size_t)width * (size_t)height,
                  width, height, (width + 7) / 8, 0};
     A.n_blocks = A.blocks_x * ((height + 7) / 8);
-    std::lock_guard<std::mutex> lock(g_scratch_mutex);
-    SelectScratch& S = g_scratch[dev];
-    if (!S.done) HIP_TRY(hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
-    if ((size_t)A.n_blocks > S.blocks) { // (hipFree waits for the device, so no queued pass still reads the old arrays)
-        if (S.masks) (void)hipFree(S.masks);
-        if (S.counts) (void)hipFree(S.counts);
-        S.masks = nullptr;
-        S.counts = nullptr;
-        S.blocks = 0;
-        HIP_TRY(hipMalloc(&S.masks, (size_t)A.n_blocks * sizeof(unsigned long long)));
-        HIP_TRY(hipMalloc(&S.counts, (size_t)A.n_blocks * sizeof(unsigned int)));
-        S.blocks = (size_t)A.n_blocks;
-    }
-    if (S.any && st != S.last) HIP_TRY(hipStreamWaitEvent(st, S.done, 0));
+    SelectPass pass;
+    rc = select_begin("rt_adaptive_select_device", (size_t)A.n_blocks, st, pass);
+    if (rc != RT_OK) return rc;
     const unsigned grid = (unsigned)((A.n_blocks + 3) / 4);
-    hipLaunchKernelGGL(adaptive_count_kernel, dim3(grid), dim3(256), 0, st, A, S.masks, S.counts);
-    hipLaunchKernelGGL(adaptive_scan_kernel, dim3(1), dim3(1024), 0, st, S.counts, A.n_blocks, d_count);
-    if (cap > 0) hipLaunchKernelGGL(adaptive_write_kernel, dim3(grid), dim3(256), 0, st, A, S.masks, S.counts, d_pixels, cap);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(S.done, st));
-    S.last = st;
-    S.any = true;
-    return RT_OK;
+    hipLaunchKernelGGL(adaptive_count_kernel, dim3(grid), dim3(256), 0, st, A, pass.S->masks, pass.S->counts);
+    select_scan(pass, A.n_blocks, d_count, st);
+    if (cap > 0)
+        hipLaunchKernelGGL(adaptive_write_kernel, dim3(grid), dim3(256), 0, st, A, pass.S->masks, pass.S->counts, d_pixels, cap);
+    return select_end(pass, st);
 }
 
 int64_t rt_debug_adaptive_select(const rt_adaptive_params* P, const double* sum, const uint32_t* samples, const uint32_t* misses,

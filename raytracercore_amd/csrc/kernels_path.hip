@@ -45,6 +45,7 @@ __device__ __forceinline__ bool known_zero(float c)
 #include "rt_surfel.h"
 #ifndef __HIPCC_RTC__ // (the probes' fold is no part of a scene-specialised build)
 #include "rt_sh.h"
+#include "rt_probe_error.h"
 #endif
 #ifdef RT_SCENE_CONST
 // rt_jit.cpp generates this header per scene (and camera, for the grouped order): the launch's
@@ -3086,20 +3087,30 @@ __global__ void accumulate_list_kernel(PathParams p, const uint32_t* index, size
 // rt_sh.h: fp64, product and sum each rounded on its own, in sample order from what the accumulators hold.
 // recs null: sh, samples and misses of the probe; else recs[i], which came up with the caller's sums and
 // zero counts and goes down to the host entry.  The 36 sums stay in registers; no LDS, no atomics.
-__global__ void __launch_bounds__(256) accumulate_probes_kernel(PathParams p, rt_probe_sh* sh, uint32_t* samples,
-                                                                uint32_t* misses, ProbeRec* recs)
+// (fold_probe: list position i's partials into the accumulators of entry e; the two kernels below.)
+// LIST (rt_render_probe_list): the record, the stream's key and the accumulators are entry e's, the partials
+// list position i's.  MOM: the entry's rt_probe_moments (rt_probe_error.h) as eight more sums in registers.
+template <bool LIST, bool MOM>
+__device__ __forceinline__ void fold_probe(const PathParams& p, size_t i, size_t e, rt_probe_sh* sh, uint32_t* samples,
+                                           uint32_t* misses, ProbeRec* recs, rt_probe_moments* mom)
 {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)p.n_rays) return;
-    double* const acc = recs ? &recs[i].sh.c[0][0] : &sh[i].c[0][0];
+    double* const acc = !LIST && recs ? &recs[e].sh.c[0][0] : &sh[e].c[0][0];
     double c[kShCoeffs][4];
 #pragma unroll
     for (int l = 0; l < kShCoeffs; l++)
 #pragma unroll
         for (int j = 0; j < 4; j++) c[l][j] = acc[4 * l + j];
+    [[maybe_unused]] double m0[kProbeMomentRows], m1[kProbeMomentRows];
+    if constexpr (MOM) {
+#pragma unroll
+        for (int l = 0; l < kProbeMomentRows; l++) {
+            m0[l] = mom[e].m[l][0];
+            m1[l] = mom[e].m[l][1];
+        }
+    }
     uint32_t ns = 0, nm = 0;
-    const double2* const rows = p.ray_list + 4 * i;
-    const rt_key2 pkey = rt_rng_pixel_key(p.seed_key, p.stream_base + (unsigned long long)i);
+    const double2* const rows = p.ray_list + 4 * e;
+    const rt_key2 pkey = rt_rng_pixel_key(p.seed_key, p.stream_base + (unsigned long long)e);
     const float4* const row = p.partial + ((((i >> 6) << p.log2_chunks) << 6) + (i & 63));
     for (int k = 0; k < p.spp; k++) { // (chunk == 1: chunk k is sample k)
         const float4 v = row[(size_t)k << 6];
@@ -3118,6 +3129,7 @@ __global__ void __launch_bounds__(256) accumulate_probes_kernel(PathParams p, rt
             nm++;
 #pragma unroll
             for (int l = 0; l < kShCoeffs; l++) c[l][3] = __dadd_rn(c[l][3], Y[l]);
+            if constexpr (MOM) probe_moments_miss(m1, Y);
         } else if (w & 0xFFFFu) {
             ns++;
             const double r = (double)v.x, g = (double)v.y, b = (double)v.z;
@@ -3127,19 +3139,50 @@ __global__ void __launch_bounds__(256) accumulate_probes_kernel(PathParams p, rt
                 c[l][1] = __dadd_rn(c[l][1], __dmul_rn(g, Y[l]));
                 c[l][2] = __dadd_rn(c[l][2], __dmul_rn(b, Y[l]));
             }
+            if constexpr (MOM) probe_moments_hit(m0, v.x, v.y, v.z, Y);
         }
     }
 #pragma unroll
     for (int l = 0; l < kShCoeffs; l++)
 #pragma unroll
         for (int j = 0; j < 4; j++) acc[4 * l + j] = c[l][j];
-    if (recs) {
-        recs[i].samples += ns;
-        recs[i].misses += nm;
-    } else {
-        samples[i] += ns;
-        misses[i] += nm;
+    if constexpr (MOM) {
+#pragma unroll
+        for (int l = 0; l < kProbeMomentRows; l++) {
+            mom[e].m[l][0] = m0[l];
+            mom[e].m[l][1] = m1[l];
+        }
     }
+    if (!LIST && recs) {
+        recs[e].samples += ns;
+        recs[e].misses += nm;
+    } else {
+        samples[e] += ns;
+        misses[e] += nm;
+    }
+}
+
+__global__ void __launch_bounds__(256) accumulate_probes_kernel(PathParams p, rt_probe_sh* sh, uint32_t* samples,
+                                                                uint32_t* misses, ProbeRec* recs)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)p.n_rays) return;
+    fold_probe<false, false>(p, i, i, sh, samples, misses, recs, nullptr);
+}
+
+// rt_render_probe_list: the same fold for a launch with an index list (run_rays, records not gathered): list
+// position i's rows are samples of entry e = index[i] (null: i), whose record, stream and accumulators they
+// go with; an entry at or past n_records opened no item and is skipped.  mom (MOM): the entry's moments.
+template <bool MOM>
+__global__ void __launch_bounds__(256) accumulate_probe_list_kernel(PathParams p, const uint32_t* index, size_t n_records,
+                                                                    rt_probe_sh* sh, uint32_t* samples, uint32_t* misses,
+                                                                    rt_probe_moments* mom)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)p.n_rays) return;
+    const size_t e = index ? (size_t)index[i] : i;
+    if (e >= n_records) return;
+    fold_probe<true, MOM>(p, i, e, sh, samples, misses, nullptr, mom);
 }
 
 // SampleSet.GetOutput / GetColorCode (SampleSet.cs:50-113) per pixel of planar accumulators.
@@ -3539,6 +3582,21 @@ hipError_t launch_accumulate_probes(const PathParams& p, rt_probe_sh* d_sh, uint
     if (p.n_rays == 0) return hipSuccess;
     hipLaunchKernelGGL(accumulate_probes_kernel, dim3((p.n_rays + 255u) / 256u), dim3(256), 0, stream, p, d_sh, d_samples,
                        d_misses, d_recs);
+    return hipGetLastError();
+}
+
+hipError_t launch_accumulate_probe_list(const PathParams& p, const uint32_t* d_index, size_t n_records, rt_probe_sh* d_sh,
+                                        uint32_t* d_samples, uint32_t* d_misses, rt_probe_moments* d_moments,
+                                        hipStream_t stream)
+{
+    if (p.n_rays == 0) return hipSuccess;
+    const dim3 grid((p.n_rays + 255u) / 256u);
+    if (d_moments)
+        hipLaunchKernelGGL(accumulate_probe_list_kernel<true>, grid, dim3(256), 0, stream, p, d_index, n_records, d_sh,
+                           d_samples, d_misses, d_moments);
+    else
+        hipLaunchKernelGGL(accumulate_probe_list_kernel<false>, grid, dim3(256), 0, stream, p, d_index, n_records, d_sh,
+                           d_samples, d_misses, d_moments);
     return hipGetLastError();
 }
 

@@ -434,6 +434,12 @@ struct ProbeRec {
 // d_recs null: added to d_sh, d_samples, d_misses (p.n_rays each); else to d_recs[p.n_rays] in place.
 hipError_t launch_accumulate_probes(const PathParams& p, rt_probe_sh* d_sh, uint32_t* d_samples, uint32_t* d_misses,
                                     ProbeRec* d_recs, hipStream_t stream);
+// rt_render_probe_list: launch_accumulate_probes for a launch with an index list over n_records resident
+// records (d_index null: the identity): list position i's samples go into d_sh, d_samples, d_misses and, where
+// given, d_moments (rt_probe_error.h) at the entry d_index[i]; an entry at or past n_records is skipped.
+hipError_t launch_accumulate_probe_list(const PathParams& p, const uint32_t* d_index, size_t n_records, rt_probe_sh* d_sh,
+                                        uint32_t* d_samples, uint32_t* d_misses, rt_probe_moments* d_moments,
+                                        hipStream_t stream);
 // planar row-major accumulators (w*h) -> TileRec[w*h] in x*h + y order
 hipError_t launch_tile_host_layout(int w, int h, const double* d_sum, const uint32_t* d_samples,
                                   const uint32_t* d_misses, TileRec* d_out, hipStream_t stream);

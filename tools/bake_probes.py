@@ -2,6 +2,7 @@
 
 usage: python tools/bake_probes.py SCENE --grid NX NY NZ [--bounds X0 Y0 Z0 X1 Y1 Z1] --spp N [--seed S]
                                    [--traversal MODE] [--show K] [--out probes.npz]
+                                   [--tol T [--min A] [--max B] [--batch C]]
 
 SCENE is a scene file (or the name of one shipped in tests/golden/scenes).  The probes are the cell centres of
 an NX x NY x NZ grid over --bounds (default: the box of the scene's primitives without the planes,
@@ -9,6 +10,12 @@ rc.scene_bound, shrunk by 5 % on every side).  render_probes takes N RT_GATHER_S
 keeps them as 27 spherical-harmonic sums and the projection of the directions that met nothing;
 probe_radiance_sh closes those with the scene's ambient colour.  Writes positions [n, 3], L [n, 9, 3],
 samples [n], misses [n] and the grid to the .npz.
+
+--tol T bakes adaptively (GpuRaytracer.bake_probes_adaptive): every probe gets samples in batches of C
+(--batch, default 16), at least A (--min, default 64) and at most B (--max, default --spp), until the estimated
+standard error of its band-0/1 irradiance is at most T of its mean luminance.  The .npz then also holds the
+samples each probe took (spp [n]), and the total is printed against n x B.  A probe whose samples so far all came
+back black has an estimated error of zero and stops at A: choose --min so that a probe finds the scene's lights.
 
 For the first K probes (--show, default 3) and the six axis normals it prints sh_irradiance(L, normal) beside
 pi x gather_mean of a COSINE render_surfels of the same N samples at the same point: the irradiance by its
@@ -47,6 +54,16 @@ def bake_probes(gpu, positions, spp: int, ambient, seed: int = 0):
     return rc.probe_radiance_sh(sh, ns, ms, ambient), ns, ms, rays
 
 
+def bake_probes_tol(gpu, positions, tol: float, min_spp: int, max_spp: int, batch: int, ambient, seed: int = 0):
+    """(L [n, 9, 3], samples, misses, rays, spp [n]) of bake_probes_adaptive at the positions."""
+    import raytracercore_amd as rc
+
+    res = gpu.bake_probes_adaptive(positions, tol, min_spp, max_spp, batch, seed=seed, ambient=ambient)
+    sh = res["sh"].cpu().numpy()
+    ns, ms = (res[k].cpu().numpy().view(np.uint32) for k in ("samples", "misses"))
+    return rc.probe_radiance_sh(sh, ns, ms, ambient), ns, ms, res["rays"], res["spp"].cpu().numpy()
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("scene")
@@ -57,9 +74,16 @@ def main(argv=None) -> int:
     ap.add_argument("--traversal", default="AUTO", choices=["AUTO", "BRUTE", "GROUPED", "BVH"])
     ap.add_argument("--show", type=int, default=3)
     ap.add_argument("--out", default="probes.npz")
+    ap.add_argument("--tol", type=float, help="bake adaptively to this relative error of the band-0/1 irradiance")
+    ap.add_argument("--min", type=int, default=64, dest="min_spp")
+    ap.add_argument("--max", type=int, dest="max_spp", help="default: --spp")
+    ap.add_argument("--batch", type=int, default=16)
     a = ap.parse_args(argv)
     if min(a.grid) < 1 or a.spp < 1:
         ap.error("--grid and --spp must be >= 1")
+    max_spp = a.max_spp if a.max_spp is not None else a.spp
+    if a.tol is not None and (a.tol < 0 or a.batch < 1 or a.min_spp < 1 or max_spp < a.min_spp):
+        ap.error("--tol needs T >= 0, --batch >= 1 and 1 <= --min <= --max")
 
     import raytracercore_amd as rc
 
@@ -77,7 +101,11 @@ def main(argv=None) -> int:
     amb = scene.params.ambient
     gpu = rc.GpuRaytracer(scene, 0, traversal=getattr(rc, "RT_TRAVERSAL_" + a.traversal))
     try:
-        L, ns, ms, rays = bake_probes(gpu, positions, a.spp, amb, a.seed)
+        if a.tol is None:
+            L, ns, ms, rays = bake_probes(gpu, positions, a.spp, amb, a.seed)
+            taken = None
+        else:
+            L, ns, ms, rays, taken = bake_probes_tol(gpu, positions, a.tol, a.min_spp, max_spp, a.batch, amb, a.seed)
         k = min(a.show, len(positions))
         rows = []
         for i in range(k):
@@ -86,9 +114,16 @@ def main(argv=None) -> int:
             rows.append((rc.sh_irradiance(L[i], AXES), np.pi * rc.gather_mean(s, cn, cm, amb)))
     finally:
         gpu.close()
-    np.savez(a.out, positions=positions, L=L, samples=ns, misses=ms, grid=np.array(a.grid), bounds=np.array(bounds))
+    extra = {} if taken is None else {"spp": taken}
+    np.savez(a.out, positions=positions, L=L, samples=ns, misses=ms, grid=np.array(a.grid), bounds=np.array(bounds), **extra)
+    if taken is None:
+        how = f"{a.spp} spp"
+    else:
+        cap = -(-max_spp // a.batch) * a.batch
+        how = (f"rel_tol {a.tol}: {int(taken.sum())} samples of {len(positions)} x {cap} = {len(positions) * cap} "
+               f"({int((taken < cap).sum())} probes stopped early, {int(taken.min())} .. {int(taken.max())} spp)")
     print(f"{os.path.basename(path)}: {a.grid[0]}x{a.grid[1]}x{a.grid[2]} = {len(positions)} probes over "
-          f"{np.round(bounds, 4).tolist()}, {a.spp} spp, {rays} rays, {int(ms.sum())} of {int((ns + ms).sum())} samples met "
+          f"{np.round(bounds, 4).tolist()}, {how}, {rays} rays, {int(ms.sum())} of {int((ns + ms).sum())} samples met "
           f"nothing -> {a.out}")
     names = ("+x", "-x", "+y", "-y", "+z", "-z")
     for i, (e_sh, e_cos) in enumerate(rows):
