@@ -1105,8 +1105,9 @@ int rt_debug_probe_error(const rt_probe_select_params* params, const rt_probe_sh
  * `stream`, ordered like the device-resident renders, and works in chunks of 2^16 points (RTCORE_QUERY_CHUNK
  * / 8: one any-hit launch of at most 2^19 segments, 73 B of per-scene scratch each); rt_shade_probes uploads
  * L once and takes the points in the same chunks, 64 B up and 32 B down per point.
- * Not part of it: DDGI's backface "wrap" weight and its Chebyshev depth moments; a shortened segment end
- * (probes belong in the air); RT_QUERY_EXACT; a grid that is not axis-aligned; adding into the outputs.
+ * Not part of it: DDGI's backface "wrap" weight and its Chebyshev depth moments (these are "probe depth
+ * maps", below: rt_shade_probes_depth_device); a shortened segment end (probes belong in the air);
+ * RT_QUERY_EXACT; a grid that is not axis-aligned; adding into the outputs.
  */
 #define RT_PROBE_GRID_VISIBILITY 1u
 typedef struct rt_probe_grid {   /* 80 B, five 16-byte rows */
@@ -1138,6 +1139,114 @@ int rt_debug_probe_segments(const rt_probe_grid* grid, const rt_surfel* points, 
    NULL = all 0. */
 int rt_debug_shade_probes(const rt_probe_grid* grid, const double* L, const rt_surfel* points, int64_t n,
                           const uint8_t* occluded, rt_color* irradiance, double* weight);
+
+/*
+ * Probe depth maps: the visibility of a probe grid without a ray at shading time.  The grid's
+ * RT_PROBE_GRID_VISIBILITY traces eight any-hit segments per shading point; here the bake stores, with every
+ * probe, an octahedral map of the first two moments of the distance it sees, and the shading pass weighs each
+ * corner of a point's cell by a one-sided Chebyshev bound on "the probe sees at least this far in the point's
+ * direction" (DDGI's visibility test), optionally times DDGI's backface "wrap" weight.  It traces no ray, keeps
+ * no scratch and needs no scene.  The bake also counts the samples that met a back face (rt_hit.inside): a
+ * probe with a large share of them sits inside geometry.
+ *
+ * Everything below is normative and fp64 as "probe grids" is: every operation rounded on its own, nothing
+ * contracted, IEEE division and square root, no library function.  sgn(a) = a >= 0 ? 1 : -1 (so sgn(-0.0) = 1).
+ *
+ * The map.  R = 8; texel t = ty * 8 + tx, 64 per probe.
+ * Direction T_t of a texel:  u = (double)(2 tx + 1) / 8 - 1, v likewise (both exact);  z = (1 - |u|) - |v|;
+ *   z < 0:  x = (1 - |v|) * sgn(u),  y = (1 - |u|) * sgn(v);  else x = u, y = v;
+ *   T = (x, y, z) / sqrt((x*x + y*y) + z*z), component by component.
+ * Texel of a vector (x, y, z), finite and not zero, of any length:  s1 = (|x| + |y|) + |z|,  u = x / s1,
+ *   v = y / s1;  z < 0:  u' = (1 - |v|) * sgn(x),  v' = (1 - |u|) * sgn(y);  else u' = u, v' = v;
+ *   tx = (int)((u' + 1) * 4) held to [0, 7], ty likewise from v'.  The texel of T_t is t.
+ * Accumulators, rt_probe_depth: s[0][t] = sum of w, s[1][t] = sum of w d, s[2][t] = sum of w d^2.
+ * Counts, four uint32 per probe: hits, hits with rt_hit.inside != 0 (these are hits too), misses, skipped.
+ *
+ * The bake (rt_render_probe_depth_device).  Sample k of probe i is sample k of surfel i of "radiance queries"
+ * in RT_GATHER_SPHERE mode: its ray is the one rt_debug_surfel_rays_device reports for (seed, sample_base,
+ * stream_base), so a depth bake and an rt_render_probes bake with the same three look in the same directions;
+ * its hit is what rt_query_rays_device(RT_QUERY_FAST) answers for that ray on this scene in its traversal
+ * mode.  Added to what the arrays hold, per probe in sample order k = 0 .. spp - 1:
+ *   a direction of all zeros (an invalid probe):  skipped += 1, nothing else;
+ *   else  d = hit (prim_id >= 0) and distance < d_max ? distance : d_max;  hits (and inside hits) or misses += 1;
+ *   for every texel t, with (x, y, z) the ray's direction:  c = (x * T_x + y * T_y) + z * T_z;  c not > 0 adds
+ *   nothing;  else w = c squared `sharpness` times (w = w * w),
+ *     s[0][t] += w;   s[1][t] += w * d;   s[2][t] += (w * d) * d,   each product rounded, then each sum.
+ * What is promised:
+ *   1. The device result equals rt_debug_probe_depth_fold over the reported rays and the query's answers, bit
+ *      for bit.
+ *   2. A probe's result depends on (seed, stream_base + i, the sample indices, the record, the params, the
+ *      traversal mode) only: not on n, on list position, on chunking or on the stream.
+ *   3. A call of a + b samples equals a call of a samples followed by one of b samples at sample_base + a into
+ *      the same arrays, bit for bit.
+ * Calls.  `params` is a host pointer.  RT_ERR_ARG, before anything is launched, for what rt_render_probes_device
+ * refuses (a null scene, n < 0, spp <= 0, then for n > 0 a null pointer), for params that break a rule of the
+ * struct and for spp > 2^19 (split by sample_base).  n == 0 returns RT_OK and touches nothing.  RT_ERR_STATE on
+ * a BVH2 scene.  Always the generic kernels; no camera is needed; the counters of rt_scene_get_stats, an armed
+ * rt_debug_ray_log, rt_kernel_times and the scene-specialised kernels are left as they were.  Asynchronous on
+ * `stream`, ordered like the device-resident renders; chunks of max(1, 2^19 / spp) whole probes
+ * (RTCORE_QUERY_CHUNK samples), 64 + 48 B of per-scene scratch per sample.  No host-buffer entry.
+ *
+ * The close (rt_probe_depth_close_device).  D: n x 64 x 2 doubles, D[p][t] = (s[1][t] / s[0][t],
+ * s[2][t] / s[0][t]) = (mu, m2); where s[0][t] is not > 0 both are a quiet NaN.  A texel one of whose two
+ * values is not finite is ABSENT.
+ *
+ * The shading (rt_shade_probes_depth_device).  The grid is "probe grids"' with flags == 0.  Point, cell,
+ * corners and t_c are exactly that section's.  For each visited corner, with the probe's position q and
+ * o_a = p_a + bias * n^_a as its segments form them:  v = o - q,  r = sqrt((vx*vx + vy*vy) + vz*vz).
+ *   r not > 0 or not finite:  c = 1, wrap = 1.
+ *   else  (mu, m2) = D[probe][texel of v],  r_c = r < d_max ? r : d_max;
+ *     the texel absent, or r_c not > mu:  c = 1;
+ *     else  var = m2 - mu * mu,  var = var > var_floor ? var : var_floor,  delta = r_c - mu,
+ *           c = var / (var + delta * delta),  then c = (c * c) * c;
+ *     with RT_PROBE_DEPTH_WRAP:  h = (1 - ((vx * n^x + vy * n^y) + vz * n^z) / r) * 0.5,  wrap = h * h + 0.2
+ *     (1.2 for a normal that faces the probe, 0.2 for one that faces away);  without it wrap = 1.
+ *   t' = (t_c * c) * wrap.
+ * Blend: that section's, corners ascending, with t' in place of t_c over the corners that are visited, present
+ * and have t' > 0:  W = W + t',  B = B + t' * L_c;  the irradiance formula is the same; W == 0 gives
+ * irradiance 0 and weight 0.
+ * What is promised:
+ *   1. The device result equals rt_debug_shade_probes_depth, bit for bit.
+ *   2. A point's result depends on the grid, the params, L, D and the record only.
+ *   3. With every texel of D absent and no wrap flag the result equals rt_shade_probes_device on the same grid
+ *      (flags 0), bit for bit (t_c * 1 is exact).
+ * Calls.  grid and params are host pointers.  Both entries run on the calling thread's current device, as
+ * rt_probe_radiance_device does.  RT_ERR_ARG, before anything is launched, for a null grid or params, a grid
+ * or params that break a rule of their struct, grid flags other than 0 (RT_PROBE_GRID_VISIBILITY included),
+ * n < 0, then for n > 0 a null L, D, points or irradiance pointer; n == 0 returns RT_OK and touches nothing.
+ * The close: RT_ERR_ARG for n < 0, n >= 2^25 or a null pointer with n > 0.  Outputs are written, not added to;
+ * d_weight may be NULL.
+ * Not part of it: a host-buffer bake; bilinear lookup across the octahedral seams; probe relocation (the
+ * backface share only enables it); fusing the fold into rt_render_probes' launch.
+ */
+#define RT_PROBE_DEPTH_WRAP 1u
+typedef struct rt_probe_depth_params {   /* 32 B */
+    double   d_max;       /* finite, > 0: distances are held to it; a miss counts as d_max       */
+    double   var_floor;   /* finite, > 0: the least variance the Chebyshev test works with       */
+    int32_t  sharpness;   /* 0 .. 8: a sample's weight in a texel is its cosine squared this often */
+    uint32_t flags;       /* RT_PROBE_DEPTH_WRAP: the shading multiplies by the wrap weight      */
+    uint32_t reserved[2]; /* 0 */
+} rt_probe_depth_params;
+typedef struct rt_probe_depth {   /* 1536 B per probe: three rows of 64 texels, texel index fastest */
+    double s[3][64];
+} rt_probe_depth;
+int rt_render_probe_depth_device(rt_scene* scene, const rt_surfel* d_probes, int64_t n, int32_t spp, uint64_t seed,
+                                 uint64_t sample_base, uint64_t stream_base, const rt_probe_depth_params* params,
+                                 rt_probe_depth* d_depth, uint32_t* d_counts, void* stream);
+/* Its fold on the host, no device: rays and hits are n * spp of each, probe i's at [i * spp, (i + 1) * spp). */
+int rt_debug_probe_depth_fold(const rt_probe_depth_params* params, const rt_ray* rays, const rt_hit* hits, int64_t n,
+                              int32_t spp, rt_probe_depth* depth, uint32_t* counts);
+int rt_probe_depth_close_device(const rt_probe_depth* d_depth, int64_t n, double* d_D, void* stream);
+int rt_debug_probe_depth_close(const rt_probe_depth* depth, int64_t n, double* D);
+int rt_shade_probes_depth_device(const rt_probe_grid* grid, const rt_probe_depth_params* params, const double* d_L,
+                                 const double* d_D, const rt_surfel* d_points, int64_t n, rt_color* d_irradiance,
+                                 double* d_weight, void* stream);
+int rt_debug_shade_probes_depth(const rt_probe_grid* grid, const rt_probe_depth_params* params, const double* L,
+                                const double* D, const rt_surfel* points, int64_t n, rt_color* irradiance, double* weight);
+/* The two texel rules on the host: the 64 directions T_t as 64 x 3 doubles; the texels of n vectors (3 doubles
+   each; -1 for one that is zero or not finite). */
+int rt_debug_oct_texel_dirs(double* dirs_out);
+int rt_debug_oct_texel(const double* vectors_xyz, int64_t n, int32_t* texels_out);
 
 /* ---------------------------------------------------- indexed radiance queries --- */
 /*

@@ -189,6 +189,20 @@ def probe_grid(origin, step, dims, visibility: bool = True, bias: float = 0.0) -
                          float(bias))
 
 
+RT_PROBE_DEPTH_WRAP = 1  # rt_probe_depth_params.flags: the shading multiplies by the backface wrap weight
+
+
+class rt_probe_depth_params(C.Structure):
+    """The parameters of probe depth maps (rt_render_probe_depth_device, rt_shade_probes_depth_device), 32 B."""
+    _fields_ = [("d_max", C.c_double), ("var_floor", C.c_double), ("sharpness", C.c_int32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 2)]
+
+
+def probe_depth_params(d_max: float, sharpness: int = 5, var_floor: float = 1e-4, wrap: bool = False) -> rt_probe_depth_params:
+    """rt_probe_depth_params; the library checks the values."""
+    return rt_probe_depth_params(float(d_max), float(var_floor), int(sharpness), RT_PROBE_DEPTH_WRAP if wrap else 0)
+
+
 class rt_hit(C.Structure):
     """One answer of rt_query_rays (Hit.cs): 48 B, offsets in include/rtcore.h."""
     _fields_ = [
@@ -292,7 +306,8 @@ _OPTIONAL = ("rt_query_rays", "rt_query_rays_device", "rt_camera_rays", "rt_sele
              "rt_render_surfels", "rt_render_surfels_device", "rt_render_list", "rt_render_list_device",
              "rt_occluded_surfels", "rt_occluded_surfels_device", "rt_render_probes", "rt_render_probes_device",
              "rt_probe_radiance_device", "rt_shade_probes", "rt_shade_probes_device", "rt_render_probe_list_device",
-             "rt_probe_select_device")
+             "rt_probe_select_device", "rt_render_probe_depth_device", "rt_probe_depth_close_device",
+             "rt_shade_probes_depth_device")
 
 _lib: Optional[C.CDLL] = None
 
@@ -444,6 +459,18 @@ def load_library(path: str = "") -> C.CDLL:
         "rt_debug_probe_segments": (C.c_int, [P(rt_probe_grid), C.c_void_p, C.c_int64, C.c_void_p, P(C.c_double)]),
         "rt_debug_shade_probes": (C.c_int, [P(rt_probe_grid), P(C.c_double), C.c_void_p, C.c_int64, C.c_void_p,
                                             P(rt_color), P(C.c_double)]),
+        "rt_render_probe_depth_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_uint64,
+                                                   C.c_uint64, P(rt_probe_depth_params), C.c_void_p, C.c_void_p, C.c_void_p]),
+        "rt_debug_probe_depth_fold": (C.c_int, [P(rt_probe_depth_params), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                                C.c_void_p, C.c_void_p]),
+        "rt_probe_depth_close_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+        "rt_debug_probe_depth_close": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+        "rt_shade_probes_depth_device": (C.c_int, [P(rt_probe_grid), P(rt_probe_depth_params), C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "rt_debug_shade_probes_depth": (C.c_int, [P(rt_probe_grid), P(rt_probe_depth_params), C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+        "rt_debug_oct_texel_dirs": (C.c_int, [C.c_void_p]),
+        "rt_debug_oct_texel": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
         "rt_render_list": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                      C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, P(rt_color), P(C.c_uint32),
                                      P(C.c_uint32), P(C.c_double), P(C.c_uint32), P(C.c_uint64)]),
@@ -1062,6 +1089,157 @@ def shade_probes_host(grid: rt_probe_grid, L, positions, normals, occluded=None)
     return irr, w
 
 
+def _oct_sgn(a: np.ndarray) -> np.ndarray:
+    return np.where(a >= 0.0, 1.0, -1.0)
+
+
+def oct_texel_dirs() -> np.ndarray:
+    """The unit directions T_t of the 64 texels of a probe's 8 x 8 octahedral depth map (rtcore.h, "probe depth
+    maps"), t = ty * 8 + tx, as (64, 3) doubles: the definition in numpy, operation by operation."""
+    t = np.arange(64)
+    u = (2 * (t & 7) + 1).astype(np.float64) / 8.0 - 1.0
+    v = (2 * (t >> 3) + 1).astype(np.float64) / 8.0 - 1.0
+    z = (1.0 - np.abs(u)) - np.abs(v)
+    x = np.where(z < 0.0, (1.0 - np.abs(v)) * _oct_sgn(u), u)
+    y = np.where(z < 0.0, (1.0 - np.abs(u)) * _oct_sgn(v), v)
+    ln = np.sqrt((x * x + y * y) + z * z)
+    return np.stack([x / ln, y / ln, z / ln], axis=-1)
+
+
+def oct_texel(v) -> np.ndarray:
+    """The texel (0 .. 63) of vectors v (..., 3), finite and not zero, of any length, by the same definition."""
+    a = np.asarray(v, np.float64)
+    x, y, z = a[..., 0], a[..., 1], a[..., 2]
+    s1 = (np.abs(x) + np.abs(y)) + np.abs(z)
+    u, w = x / s1, y / s1
+    uo = np.where(z < 0.0, (1.0 - np.abs(w)) * _oct_sgn(x), u)
+    wo = np.where(z < 0.0, (1.0 - np.abs(u)) * _oct_sgn(y), w)
+    tx = np.clip(((uo + 1.0) * 4.0).astype(np.int64), 0, 7)
+    ty = np.clip(((wo + 1.0) * 4.0).astype(np.int64), 0, 7)
+    return (ty * 8 + tx).astype(np.int32)
+
+
+def oct_texel_dirs_host() -> np.ndarray:
+    """rt_debug_oct_texel_dirs (host code, no GPU): oct_texel_dirs by the kernels' function compiled for the CPU."""
+    lib = load_library()
+    if not hasattr(lib, "rt_debug_oct_texel_dirs"):
+        raise RtError("this build of the library has no rt_debug_oct_texel_dirs")
+    out = np.zeros((64, 3), np.float64)
+    _check(lib.rt_debug_oct_texel_dirs(out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def oct_texel_host(v) -> np.ndarray:
+    """rt_debug_oct_texel (host code, no GPU): oct_texel by the kernels' function; -1 for a vector that is zero
+    or not finite."""
+    lib = load_library()
+    if not hasattr(lib, "rt_debug_oct_texel"):
+        raise RtError("this build of the library has no rt_debug_oct_texel")
+    a = np.ascontiguousarray(v, np.float64)
+    if a.shape[-1:] != (3,):
+        raise ValueError("v must be (..., 3)")
+    out = np.zeros(a.shape[:-1], np.int32)
+    _check(lib.rt_debug_oct_texel(a.ctypes.data_as(C.c_void_p), out.size, out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def _depth_out(n: int, out):
+    """The depth bake's `out` = (depth f64 [n, 3, 64], counts u32 [n, 4]), new zeroed arrays for None."""
+    if out is None:
+        return np.zeros((n, 3, 64), np.float64), np.zeros((n, 4), np.uint32)
+    depth, counts = out
+    if (depth.dtype != np.float64 or depth.shape != (n, 3, 64) or counts.dtype != np.uint32 or counts.shape != (n, 4)
+            or not depth.flags.c_contiguous or not counts.flags.c_contiguous):
+        raise ValueError("out must be contiguous (f64 [n, 3, 64], u32 [n, 4])")
+    return depth, counts
+
+
+def probe_depth_fold_host(params: rt_probe_depth_params, rays, hits, out=None) -> Tuple[np.ndarray, np.ndarray]:
+    """rt_debug_probe_depth_fold (host code, no GPU): render_probe_depth's accumulation over per-sample results.
+    rays (n, spp) RAY_DTYPE as surfel_rays reports them in RT_GATHER_SPHERE mode, hits (n, spp) HIT_DTYPE as
+    query_rays answers for them.  Added into out = (depth [n, 3, 64], counts [n, 4]); returns them."""
+    lib = load_library()
+    if not hasattr(lib, "rt_debug_probe_depth_fold"):
+        raise RtError("this build of the library has no rt_debug_probe_depth_fold")
+    r, h = np.ascontiguousarray(rays, RAY_DTYPE), np.ascontiguousarray(hits, HIT_DTYPE)
+    if r.ndim != 2 or r.shape != h.shape:
+        raise ValueError("rays and hits must be (n, spp)")
+    n, spp = r.shape
+    depth, counts = _depth_out(n, out)
+    _check(lib.rt_debug_probe_depth_fold(C.byref(params), r.ctypes.data_as(C.c_void_p), h.ctypes.data_as(C.c_void_p), n, spp,
+                                         depth.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p)))
+    return depth, counts
+
+
+def probe_depth_close_host(depth) -> np.ndarray:
+    """rt_debug_probe_depth_close (host code, no GPU): D (n, 64, 2) = (mean distance, mean squared distance) per
+    texel from the accumulators (n, 3, 64); NaN where a texel has no weight."""
+    lib = load_library()
+    if not hasattr(lib, "rt_debug_probe_depth_close"):
+        raise RtError("this build of the library has no rt_debug_probe_depth_close")
+    a = np.ascontiguousarray(depth, np.float64)
+    if a.ndim != 3 or a.shape[1:] != (3, 64):
+        raise ValueError("depth must be (n, 3, 64)")
+    D = np.zeros((a.shape[0], 64, 2), np.float64)
+    _check(lib.rt_debug_probe_depth_close(a.ctypes.data_as(C.c_void_p), a.shape[0], D.ctypes.data_as(C.c_void_p)))
+    return D
+
+
+def probe_depth_close_device(d_depth, n: int, d_D, stream: int = 0) -> None:
+    """rt_probe_depth_close_device: D (n x 64 x 2 doubles at d_D) from the depth bake's device accumulators, on
+    the current device, asynchronous on `stream`.  The device arrays as torch tensors or as pointers."""
+    lib = load_library()
+    if not hasattr(lib, "rt_probe_depth_close_device"):
+        raise RtError("this build of the library has no rt_probe_depth_close_device")
+    _check(lib.rt_probe_depth_close_device(C.c_void_p(_ptr(d_depth)), n, C.c_void_p(_ptr(d_D)), C.c_void_p(stream)))
+
+
+def _grid_D(grid: rt_probe_grid, D) -> np.ndarray:
+    a = np.ascontiguousarray(D, np.float64)
+    n = int(grid.dims[0]) * int(grid.dims[1]) * int(grid.dims[2])
+    if a.size != n * 128 or a.shape[-2:] != (64, 2):
+        raise ValueError("D must hold nx * ny * nz probes of (64, 2) moments")
+    return a.reshape(n, 64, 2)
+
+
+def shade_probes_depth_host(grid: rt_probe_grid, L, D, params: rt_probe_depth_params, positions,
+                            normals) -> Tuple[np.ndarray, np.ndarray]:
+    """rt_debug_shade_probes_depth (host code, no GPU): shade_probes_depth's blend, bit for bit.  Returns
+    (irradiance (n, 3), weight (n,))."""
+    lib = load_library()
+    if not hasattr(lib, "rt_debug_shade_probes_depth"):
+        raise RtError("this build of the library has no rt_debug_shade_probes_depth")
+    pts = _pack_surfels(positions, normals)
+    n = pts.shape[0]
+    coeffs, moments = _grid_L(grid, L), _grid_D(grid, D)
+    irr, w = np.zeros((n, 3), np.float64), np.zeros(n, np.float64)
+    _check(lib.rt_debug_shade_probes_depth(C.byref(grid), C.byref(params), coeffs.ctypes.data_as(C.c_void_p),
+                                           moments.ctypes.data_as(C.c_void_p), pts.ctypes.data_as(C.c_void_p), n,
+                                           irr.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p)))
+    return irr, w
+
+
+def shade_probes_depth_device(grid: rt_probe_grid, params: rt_probe_depth_params, d_L, d_D, d_points, n: int, d_irradiance,
+                              d_weight=0, stream: int = 0) -> None:
+    """rt_shade_probes_depth_device: asynchronous depth-weighted shading of n rt_surfel at d_points under the
+    grid's L (n_probes x 9 x 3 doubles) and D (n_probes x 64 x 2 doubles), written to n x 3 doubles at
+    d_irradiance and n doubles at d_weight (0: not wanted), on the current device and `stream`."""
+    lib = load_library()
+    if not hasattr(lib, "rt_shade_probes_depth_device"):
+        raise RtError("this build of the library has no rt_shade_probes_depth_device")
+    _check(lib.rt_shade_probes_depth_device(C.byref(grid), C.byref(params), C.c_void_p(_ptr(d_L)), C.c_void_p(_ptr(d_D)),
+                                            C.c_void_p(_ptr(d_points)), n, C.c_void_p(_ptr(d_irradiance)),
+                                            C.c_void_p(_ptr(d_weight)), C.c_void_p(stream)))
+
+
+def probe_backface_share(counts) -> np.ndarray:
+    """Inside hits divided by hits of the depth bake's counts (..., 4) = (hits, inside hits, misses, skipped):
+    the share of a probe's hits that met a back face; near 1 for a probe inside geometry.  NaN without a hit."""
+    c = np.asarray(counts, np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(c[..., 0] > 0, c[..., 1] / c[..., 0], np.nan)
+
+
 def ambient_occlusion(occluded, samples) -> np.ndarray:
     """1 - occluded / samples of occluded_surfels' counts: the share of a point's sample segments that
     reach their end unhindered (in RT_GATHER_COSINE mode the ambient occlusion term).  NaN where a point has
@@ -1621,6 +1799,75 @@ class GpuRaytracer:
             raise RtError("this build of the library has no rt_shade_probes_device")
         _check(self.lib.rt_shade_probes_device(self.handle, C.byref(grid), C.c_void_p(_ptr(d_L)), C.c_void_p(_ptr(d_points)), n,
                                                C.c_void_p(_ptr(d_irradiance)), C.c_void_p(_ptr(d_weight)), C.c_void_p(stream)))
+
+    def render_probe_depth_device(self, d_probes, n: int, spp: int, seed: int, sample_base: int, stream_base: int,
+                                  params: rt_probe_depth_params, d_depth, d_counts, stream: int = 0) -> None:
+        """rt_render_probe_depth_device: asynchronous depth bake for n rt_surfel (64 B each) at d_probes, added into
+        n rt_probe_depth (1536 B each: [n, 3, 64] doubles) at d_depth and n x 4 uint32 at d_counts on `stream`.
+        The device arrays as torch tensors or as pointers (integers)."""
+        if not hasattr(self.lib, "rt_render_probe_depth_device"):
+            raise RtError("this build of the library has no rt_render_probe_depth_device")
+        _check(self.lib.rt_render_probe_depth_device(self.handle, C.c_void_p(_ptr(d_probes)), n, spp, seed, sample_base,
+                                                     stream_base, C.byref(params), C.c_void_p(_ptr(d_depth)),
+                                                     C.c_void_p(_ptr(d_counts)), C.c_void_p(stream)))
+
+    def render_probe_depth(self, positions, spp: int, seed: int, d_max: float, sharpness: int = 5, normals=None,
+                           sample_base: int = 0, stream_base: int = 0, out=None, close: bool = True):
+        """Probe depth maps (rtcore.h, "probe depth maps"): spp RT_GATHER_SPHERE samples per point, the ones
+        render_probes takes for the same (seed, sample_base, stream_base), folded into each probe's 8 x 8
+        octahedral map of distance moments.  positions (n, 3) with normals None (any unit normal: a sphere
+        sample's distribution does not depend on it, its directions do) or as render_surfels takes them.
+        Everything stays on this scene's device; returns a dict of torch tensors: depth (n, 3, 64) f64, counts
+        (n, 4) int32 holding the uint32 counts (hits, inside hits, misses, skipped), and with close D (n, 64, 2)
+        f64 for shade_probes_depth.  out: a dict from an earlier call to add into (sample_base continues)."""
+        import torch
+
+        if normals is None and not (hasattr(positions, "dtype") and positions.dtype == SURFEL_DTYPE):
+            p = np.asarray(positions, np.float64)
+            normals = np.tile([0.0, 0.0, 1.0] + [0.0] * (p.shape[1] - 3), (p.shape[0], 1))
+        probes = _pack_surfels(positions, normals)
+        n = probes.shape[0]
+        params = probe_depth_params(d_max, sharpness)
+        with torch.cuda.device(self.device):
+            dev = torch.device("cuda", self.device)
+            d_probes = torch.from_numpy(probes.view(np.uint8).copy()).to(dev)
+            acc = out if out is not None else {"depth": torch.zeros((n, 3, 64), dtype=torch.float64, device=dev),
+                                               "counts": torch.zeros((n, 4), dtype=torch.int32, device=dev)}
+            if tuple(acc["depth"].shape) != (n, 3, 64) or tuple(acc["counts"].shape) != (n, 4):
+                raise ValueError("out does not hold n probes")
+            torch.cuda.synchronize()
+            self.render_probe_depth_device(d_probes, n, spp, seed, sample_base, stream_base, params, acc["depth"],
+                                           acc["counts"])
+            if close:
+                acc["D"] = torch.empty((n, 64, 2), dtype=torch.float64, device=dev)
+                probe_depth_close_device(acc["depth"], n, acc["D"])
+            torch.cuda.synchronize()
+        return acc
+
+    def shade_probes_depth(self, grid: rt_probe_grid, L, D, params: rt_probe_depth_params, positions,
+                           normals) -> Tuple[np.ndarray, np.ndarray]:
+        """rt_shade_probes_depth_device on this scene's device: shade_probes without a ray, each corner weighed by
+        a Chebyshev test of the point's distance against the probe's depth map D (and by the wrap weight with
+        RT_PROBE_DEPTH_WRAP).  grid with flags 0 (probe_grid(..., visibility=False)); L (n_probes, 9, 3) and D
+        (n_probes, 64, 2) as numpy arrays or device tensors.  Returns (irradiance (n, 3), weight (n,))."""
+        import torch
+
+        pts = _pack_surfels(positions, normals)
+        n = pts.shape[0]
+        with torch.cuda.device(self.device):
+            dev = torch.device("cuda", self.device)
+            d_L = L if hasattr(L, "data_ptr") else torch.from_numpy(_grid_L(grid, L).copy()).to(dev)
+            d_D = D if hasattr(D, "data_ptr") else torch.from_numpy(_grid_D(grid, D).copy()).to(dev)
+            n_probes = int(grid.dims[0]) * int(grid.dims[1]) * int(grid.dims[2])
+            if d_L.numel() != n_probes * 27 or d_D.numel() != n_probes * 128 or d_L.dtype != torch.float64 or d_D.dtype != torch.float64:
+                raise ValueError("L and D must hold nx * ny * nz probes of (9, 3) and (64, 2) doubles")
+            d_pts = torch.from_numpy(pts.view(np.uint8).copy()).to(dev)
+            d_irr = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+            d_w = torch.zeros(n, dtype=torch.float64, device=dev)
+            torch.cuda.synchronize()
+            shade_probes_depth_device(grid, params, d_L.contiguous(), d_D.contiguous(), d_pts, n, d_irr, d_w)
+            torch.cuda.synchronize()
+            return d_irr.cpu().numpy(), d_w.cpu().numpy()
 
     def probe_segments_device(self, grid: rt_probe_grid, positions, normals) -> Tuple[np.ndarray, np.ndarray]:
         """rt_debug_probe_segments_device on this scene's device: probe_segments_host's (rays, t_max) as the

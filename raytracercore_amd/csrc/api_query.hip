@@ -68,10 +68,6 @@ int launch_segments(rt_scene* s, int32_t mode, const rt_ray* d_rays, const doubl
     return RT_OK;
 }
 
-} // namespace rtc
-
-namespace {
-
 // One launch over n <= kQueryLaunchMax rays on `st`, after the stream ordering is settled.
 int launch_rays(rt_scene* s, int32_t mode, const rt_ray* d_rays, unsigned n, rt_hit* d_hits, hipStream_t st)
 {
@@ -88,6 +84,10 @@ int launch_rays(rt_scene* s, int32_t mode, const rt_ray* d_rays, unsigned n, rt_
     HIP_TRY(launch_query(p, kernel, grid, st));
     return RT_OK;
 }
+
+} // namespace rtc
+
+namespace {
 
 // Argument and state checks shared by both entry points; RT_OK with *empty set for n == 0.
 int check_query(rt_scene* s, int32_t mode, const void* rays, int64_t n, const void* hits, const char* name, bool* empty)

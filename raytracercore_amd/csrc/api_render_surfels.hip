@@ -48,6 +48,20 @@ __global__ void __launch_bounds__(256) surfel_rays_kernel(const double2* __restr
 
 } // namespace
 
+namespace rtc { // (declared in rt_scene.h: api_probe_depth.hip makes its sample rays by the same launch)
+
+int launch_surfel_rays(int32_t mode, const rt_surfel* d_surfels, unsigned long long total, unsigned spp, uint64_t seed,
+                       uint64_t sample_base, uint64_t stream_base, rt_ray* d_rays_out, hipStream_t st)
+{
+    const unsigned blocks = (unsigned)std::min<unsigned long long>((total + 255) / 256, 1u << 16);
+    surfel_rays_kernel<<<blocks, 256, 0, st>>>(reinterpret_cast<const double2*>(d_surfels), total, spp, mode, rt_rng_seed_key(seed),
+                                               sample_base, stream_base, reinterpret_cast<double2*>(d_rays_out));
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+} // namespace rtc
+
 extern "C" {
 
 int rt_render_surfels_device(rt_scene* s, int32_t mode, const rt_surfel* d_surfels, int64_t n, int32_t spp, uint64_t seed,
@@ -83,13 +97,8 @@ int rt_debug_surfel_rays_device(int32_t mode, const rt_surfel* d_surfels, int64_
         set_error("rt_debug_surfel_rays_device: n x spp too large");
         return RT_ERR_ARG;
     }
-    const unsigned long long total = (unsigned long long)n * (unsigned long long)spp;
-    const unsigned blocks = (unsigned)std::min<unsigned long long>((total + 255) / 256, 1u << 16);
-    surfel_rays_kernel<<<blocks, 256, 0, static_cast<hipStream_t>(stream)>>>(
-        reinterpret_cast<const double2*>(d_surfels), total, (unsigned)spp, mode, rt_rng_seed_key(seed), sample_base, stream_base,
-        reinterpret_cast<double2*>(d_rays_out));
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
+    return launch_surfel_rays(mode, d_surfels, (unsigned long long)n * (unsigned long long)spp, (unsigned)spp, seed, sample_base,
+                              stream_base, d_rays_out, static_cast<hipStream_t>(stream));
 }
 
 } // extern "C"

@@ -1,6 +1,6 @@
 // rt_scene.h -- the scene object behind the C ABI and what the API's translation units share
 // (rtcore_api.hip, scene_upload.hip, api_frame.hip, api_debug.hip, api_query.hip, api_select.hip, api_render_rays.hip,
-// api_render_pixels.hip, api_render_probes.hip, api_shade_probes.hip, chunk_pipeline.hip, api_adaptive.hip, api_denoise.hip, api_reproject.hip).
+// api_render_pixels.hip, api_render_probes.hip, api_shade_probes.hip, api_probe_depth.hip, chunk_pipeline.hip, api_adaptive.hip, api_denoise.hip, api_reproject.hip).
 #pragma once
 #include <algorithm>
 #include <array>
@@ -203,6 +203,10 @@ struct rt_scene {
     DevBuf<double> probe_seg_t_max;
     DevBuf<unsigned char> probe_seg_occluded;
     DevBuf<double> shade_L, shade_out;
+    // rt_render_probe_depth_device: one chunk's sample rays and their closest hits, made and read on the
+    // caller's stream
+    DevBuf<rt_ray> probe_depth_rays;
+    DevBuf<rt_hit> probe_depth_hits;
     DevBuf<rt_surfel> shade_points;
     // run_items: the blocks per CU of each ItemSource's instance of `items_variant`
     int items_variant[ITEMS_SURFELS + 1] = {-1, -1, -1, -1, -1}, items_blocks_per_cu[ITEMS_SURFELS + 1] = {1, 1, 1, 1, 1};
@@ -411,6 +415,12 @@ int fill_query(rt_scene* s, int kernel, int blocks_per_cu, const rt_ray* d_rays,
 // ordering is settled; rt_shade_probes_device (api_shade_probes.hip) runs it over the segments it makes.
 int launch_segments(rt_scene* s, int32_t mode, const rt_ray* d_rays, const double* d_t_max, unsigned n, unsigned char* d_out,
                     hipStream_t st);
+// rt_query_rays' launch over n <= kQueryLaunchMax rays on `st`, after the stream ordering is settled;
+// rt_render_probe_depth_device (api_probe_depth.hip) runs it over the sample rays it makes.
+int launch_rays(rt_scene* s, int32_t mode, const rt_ray* d_rays, unsigned n, rt_hit* d_hits, hipStream_t st);
+// api_render_surfels.hip: rt_debug_surfel_rays_device's launch for total = n x spp samples on `st`.
+int launch_surfel_rays(int32_t mode, const rt_surfel* d_surfels, unsigned long long total, unsigned spp, uint64_t seed,
+                       uint64_t sample_base, uint64_t stream_base, rt_ray* d_rays_out, hipStream_t st);
 // api_render_pixels.hip: rt_render_pixels' list check (every entry below npix, none twice); null, or
 // what is wrong with entry *at
 const char* check_pixel_list(const uint32_t* pixels, int64_t n, uint64_t npix, int64_t* at);

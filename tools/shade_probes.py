@@ -1,7 +1,7 @@
 """A primitive lit from a grid of light probes, from the bake to the irradiance on the device.
 
 usage: python tools/shade_probes.py SCENE --grid NX NY NZ --spp N [--prim P] --size W H [--offset E] [--flip]
-                                    [--seed S] [--traversal MODE] [--out PREFIX]
+                                    [--seed S] [--traversal MODE] [--out PREFIX] [--depth]
        python tools/shade_probes.py --mesh --grid ...
 
 SCENE is a scene file (or the name of one shipped in tests/golden/scenes; --mesh: the procedural 1 M-triangle
@@ -18,6 +18,12 @@ luminance of the gather) to pi x gather_mean of a COSINE render_surfels of the s
 points -- the irradiance by its own estimator -- and the share of texels with weight < 1 and with weight 0.
 The difference is Monte Carlo noise on both sides plus what nine coefficients and a trilinear blend cannot
 hold.  Information, not a test.
+
+--depth: also bakes the probes' depth maps (render_probe_depth, the same N samples in the same directions, d_max
+twice the grid's diagonal step, sharpness 5) and shades the texels a third way, rt_shade_probes_depth_device, into
+PREFIX_depth.npy / PREFIX_depth_weight.npy; prints its difference to the gather as for the other two, and how the
+depth test agrees with the rays over the (texel, corner) pairs that have a segment: the share of ray-hidden
+corners whose Chebyshev weight c is below 0.5, and the share of ray-visible corners with c >= 0.5.
 """
 from __future__ import annotations
 
@@ -91,8 +97,29 @@ def bake_grid_device(rc, torch, gpu, positions, spp: int, seed: int, ambient):
     return d_L, int(d_count.item())
 
 
+def corner_chebyshev(rc, grid, D, rays, t_max, d_max: float, var_floor: float):
+    """The Chebyshev weight c of every (point, corner) pair with a segment (t_max > 0; 1 elsewhere), from the
+    segments rt_debug_probe_segments_device reports: the probe is the segment's end, v = -direction * t_max its
+    vector to the point (numpy, not the kernels' rounding: information)."""
+    d, t = rays["direction"][..., :3], t_max[..., None]
+    q = rays["origin"][..., :3] + d * t
+    idx = np.rint((q - np.array(grid.origin)) / np.array(grid.step)).astype(np.int64)
+    idx = np.clip(idx, 0, np.array(grid.dims) - 1)
+    probe = (idx[..., 2] * grid.dims[1] + idx[..., 1]) * grid.dims[0] + idx[..., 0]
+    has = t_max > 0
+    v = np.where(has[..., None], -d * t, [0.0, 0.0, 1.0])
+    m = D[probe, rc.oct_texel(v)]
+    mu, m2 = m[..., 0], m[..., 1]
+    r = np.minimum(t_max, d_max)
+    with np.errstate(invalid="ignore"):
+        var = np.maximum(m2 - mu * mu, var_floor)
+        c = (var / (var + (r - mu) ** 2)) ** 3
+        return np.where(has & np.isfinite(mu) & np.isfinite(m2) & (r > mu), c, 1.0)
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--depth", action="store_true")
     ap.add_argument("scene", nargs="?", default="bounce.txt")
     ap.add_argument("--mesh", action="store_true")
     ap.add_argument("--grid", type=int, nargs=3, required=True, metavar=("NX", "NY", "NZ"))
@@ -140,6 +167,19 @@ def main(argv=None) -> int:
         gather = np.pi * rc.gather_mean(d_sum.cpu().numpy().reshape(3, n).T, d_ns.cpu().numpy().view(np.uint32),
                                         d_nm.cpu().numpy().view(np.uint32), amb)
         absent = int(torch.isnan(d_L).any(dim=2).any(dim=1).sum().item())
+        if a.depth:
+            d_max = 2.0 * float(np.linalg.norm(np.array(flat.step)))
+            P = rc.probe_depth_params(d_max, 5)
+            acc = gpu.render_probe_depth(positions, a.spp, a.seed, d_max, sharpness=5)
+            d_Ed = torch.empty((n, 3), dtype=torch.float64, device="cuda")
+            d_Wd = torch.empty(n, dtype=torch.float64, device="cuda")
+            rc.shade_probes_depth_device(flat, P, d_L, acc["D"], d_pts, n, d_Ed, d_Wd)
+            torch.cuda.synchronize()
+            Ed, Wd = d_Ed.cpu().numpy(), d_Wd.cpu().numpy()
+            seg, t_max = gpu.probe_segments_device(grid, pos.reshape(-1, 3), nrm.reshape(-1, 3))
+            occ = np.asarray(gpu.occluded_rays(seg.reshape(-1), None, t_max.reshape(-1))).reshape(n, 8) != 0
+            cheb = corner_chebyshev(rc, grid, acc["D"].cpu().numpy(), seg, t_max, d_max, P.var_floor)
+            counts = acc["counts"].cpu().numpy().view(np.uint32).astype(np.int64)
     finally:
         gpu.close()
 
@@ -155,12 +195,26 @@ def main(argv=None) -> int:
     scale = max(float(np.nanmean(ref)), 1e-300)
     print(f"{name} primitive {p}, {W}x{H} texels lit from {a.grid[0]}x{a.grid[1]}x{a.grid[2]} = {len(positions)} probes "
           f"({absent} absent), {a.spp} spp, {rays} rays in the bake; mean luminance of pi x COSINE gather {scale:.5f}")
-    for label, e, lit in (("visibility", E, Wt > 0), ("no visibility", E0, np.ones(n, bool))):
+    ways = [("visibility", E, Wt > 0), ("no visibility", E0, np.ones(n, bool))]
+    if a.depth:
+        ways.append(("depth maps", Ed, Wd > 0))
+        np.save(a.out + "_depth.npy", image(Ed))
+        np.save(a.out + "_depth_weight.npy", image(Wd)[..., 0])
+    for label, e, lit in ways:
         d = np.abs(e @ LUM - ref)[lit] / scale
         print(f"  {label:14s} mean |difference| {float(np.nanmean(d)) if d.size else float('nan'):.4f}, max "
               f"{float(np.nanmax(d)) if d.size else float('nan'):.4f} of that mean, over {int(lit.sum())} texels with a probe")
     print(f"  weight < 1 at {float((Wt < 1 - 1e-12).mean()):.4f} of the texels, weight 0 at {float((Wt == 0).mean()):.4f}"
           f" -> {a.out}.npy, {a.out}_flat.npy, {a.out}_weight.npy, {a.out}.ppm, {a.out}_flat.ppm")
+    if a.depth:
+        has = t_max > 0
+        hidden, visible = has & occ, has & ~occ
+        share = lambda sel, ok: float((ok & sel).sum()) / max(int(sel.sum()), 1)
+        print(f"  depth against rays over {int(has.sum())} (texel, corner) pairs: {int(hidden.sum())} ray-hidden, of them c < 0.5 at "
+              f"{share(hidden, cheb < 0.5):.4f}; {int(visible.sum())} ray-visible, of them c >= 0.5 at {share(visible, cheb >= 0.5):.4f}; "
+              f"depth weight < 1 at {float((Wd < 1 - 1e-12).mean()):.4f} of the texels, 0 at {float((Wd == 0).mean()):.4f}; "
+              f"d_max {d_max:.4g}, inside hits {int(counts[:, 1].sum())} of {int(counts[:, 0].sum())} hits, "
+              f"{int((rc.probe_backface_share(counts) > 0.5).sum())} probes with a backface share above 0.5")
     return 0
 
 
