@@ -1,7 +1,7 @@
 // api_occluded_surfels.hip -- the C ABI's occlusion counts for surfels (include/rtcore.h, "occlusion
 // queries", rt_occluded_surfels): rt_occluded_rays with the sample's direction drawn on the device about
 // the surfel's normal (rt_surfel.h) and the answers counted per surfel.  The kernels are
-// kernels_path.hip's occluded_surfels_*; here the launch planning (how many launches the 32-bit work
+// kernels_query.hip's occluded_surfels_*; here the launch planning (how many launches the 32-bit work
 // indices need, the brute-force kernels' sample blocks) and the two entry points.  The host entry runs
 // the chunk pipeline in rt_occluded_rays' buffers: a surfel has an rt_ray's size.
 #include <cstdlib>

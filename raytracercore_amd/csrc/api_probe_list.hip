@@ -5,7 +5,7 @@
 // index list in the launch record, as rt_render_list_device's; refill's list_entry reads only the list, the
 // record count and item_ray's list position, and set_item_order only chunks, pool and ranges, so neither
 // cares that the chunks are not make_params_rays'.  The fold is accumulate_probe_list_kernel
-// (kernels_path.hip).  The selection pass shares rt_adaptive_select_device's scan and scratch
+// (kernels_fold.hip).  The selection pass shares rt_adaptive_select_device's scan and scratch
 // (select_scan.h).  Here too: the host twins, second compilations of rt_probe_error.h.
 #include <cmath>
 #include <limits>

@@ -2,7 +2,7 @@
 // point, the sums of its RT_GATHER_SPHERE gather samples weighted by the nine L2 spherical-harmonic basis
 // functions of each sample's direction.  A probe launch is rt_render_surfels' own (run_rays over the SURFELS
 // instances of the path kernels, untouched) planned with one sample per work item (make_params_probes), so
-// that a partial row is one sample; accumulate_probes_kernel (kernels_path.hip) draws each sample's direction
+// that a partial row is one sample; accumulate_probes_kernel (kernels_fold.hip) draws each sample's direction
 // again and folds the rows in sample order.  Here: the two entry points and the host twins of the basis and
 // of the fold, second compilations of rt_sh.h.
 #include <cstring>

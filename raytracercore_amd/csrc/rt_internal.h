@@ -222,7 +222,7 @@ inline void set_scene_bound(PathScene& ps, const SceneBound& b)
 // A compact leaf's primitives share their kind and test flags, held in the reference (lf: bit 0 sphere,
 // bit 1 Mirror, 2 TwoSided, 3 Invert, 4 transformed), so the leaf step reads only their 48-B rows
 // (the TestRec without its meta row: 3 vector loads per primitive instead of 4).  The builders emit
-// generic leaves; compact_leaves (kernels_path.hip) rewrites every homogeneous one after the upload.
+// generic leaves; compact_leaves (kernels_fold.hip) rewrites every homogeneous one after the upload.
 constexpr int kLeafCompact = 1 << 30;
 constexpr int kLeafCompactMaxFirst = 1 << 23;
 constexpr int kLeafGenericMaxSlots = 1 << 27; // slots a generic leaf code can address (rt_scene_create refuses more)

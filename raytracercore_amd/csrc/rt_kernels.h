@@ -352,7 +352,7 @@ hipError_t launch_select_rays(const DevScene& s, const rt_select_item* d_items, 
 // (RT_WIDE_STACK = 16-entry stack), both + kStackOverflow entries in global memory;
 // lds stages the shading records in LDS.
 int path_variant(int kernel, bool lds);
-constexpr int kStackOverflow = 44; // = RT_STACK_OVF (kernels_path.hip)
+constexpr int kStackOverflow = 44; // (rt_trace.h asserts that the kernels' RT_STACK_OVF is the same)
 constexpr int kTestSpares = 3;     // zero TestRecs after the BVH-order records (leaf steps of up to 4 loads)
 int path_wide_stack();              // LDS entries of the wide BVH kernel's stack (RT_WIDE_STACK)
 size_t path_lds_bytes(const DevScene& s);   // dynamic LDS of the staged (lds) variants
@@ -366,6 +366,16 @@ size_t path_dyn_lds(const DevScene& s, int variant); // all dynamic LDS of a var
 // and are never instrumented.
 hipError_t launch_path(const DevScene& s, const CameraF* d_cam, const PathParams* d_params, int variant,
                        int grid_blocks, hipStream_t stream, bool stats, ItemSource src = ITEMS_TILE);
+// Blocks of 256 threads a CU can hold of a kernel, at least 1 (also when the runtime cannot say).
+template <class KernelT>
+inline int blocks_per_cu(KernelT kernel, size_t dyn_lds = 0)
+{
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, reinterpret_cast<const void*>(kernel), 256, dyn_lds) != hipSuccess ||
+        n < 1)
+        n = 1;
+    return n;
+}
 // vn: scene has vertex-normal triangles
 int path_blocks_per_cu(int variant, size_t dyn_lds, bool stats, bool vn, ItemSource src = ITEMS_TILE);
 // The trace-only kernel (waves per SIMD 6 / 7 / 8 with LDS stacks of 20 / 16 / 16 entries): blocks

@@ -1,6 +1,6 @@
 // rt_probe_error.h -- the second moments of a light probe's band-0/1 luminance coefficients and the rule
 // that stops on them (include/rtcore.h, "adaptive light probes", rt_probe_moments, rt_probe_select_params):
-// the one copy of the arithmetic that the probes' list fold (kernels_path.hip, accumulate_probe_list_kernel),
+// the one copy of the arithmetic that the probes' list fold (kernels_fold.hip, accumulate_probe_list_kernel),
 // the selection pass (api_probe_list.hip) and the host twins rt_debug_probe_moments, rt_debug_probe_error and
 // rt_debug_probe_select compile.  fp64, every operation rounded on its own, as rt_sh.h, whose sh_mul and
 // sh_add carry every product and sum here; division and square root are IEEE on both sides.

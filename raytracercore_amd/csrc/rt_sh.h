@@ -1,5 +1,5 @@
 // rt_sh.h -- the nine L2 real spherical-harmonic basis functions of a direction (include/rtcore.h, "light
-// probes", rt_probe_sh): the one copy of the arithmetic that the probes' fold kernel (kernels_path.hip,
+// probes", rt_probe_sh): the one copy of the arithmetic that the probes' fold kernel (kernels_fold.hip,
 // accumulate_probes_kernel) and the host twins rt_debug_sh_basis and rt_debug_probe_fold
 // (api_render_probes.hip) compile.  fp64, every operation rounded on its own: no contraction (the pragma; the
 // Makefile says so too), the device side through __dmul_rn / __dadd_rn as fold_entry's moments.

@@ -19,7 +19,7 @@ __device__ __forceinline__ V3 v3(float x, float y, float z) { return V3{x, y, z}
 __device__ __forceinline__ V3 operator*(V3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
 __device__ __forceinline__ float dot(V3 a, V3 b) { return fmaf(a.x, b.x, fmaf(a.y, b.y, a.z * b.z)); }
 // kfma: a product with a scene or camera field, which the scene-specialised build of kernels_path.hip
-// drops when the field is a literal zero (known_zero, defined there before this header is included and
+// drops when the field is a literal zero (known_zero, defined in rt_trace.h before it includes this header and
 // announced by RT_HAVE_KNOWN_ZERO); nothing is known anywhere else.
 #ifndef RT_HAVE_KNOWN_ZERO
 __device__ __forceinline__ bool known_zero(float) { return false; }

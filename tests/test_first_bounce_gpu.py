@@ -3,7 +3,7 @@
 In the iteration of the flat brute-force tile kernel in which every live lane of a wave holds a camera
 ray (in a rounds ticket: once per round), a wave whose lanes are of one 8x8 block tests only the units
 of the flat order whose bit is set in the block's mask (unit_masks, block_cull.cpp; trace_units,
-kernels_path.hip).
+rt_trace.h).
 RTCORE_FIRST_BOUNCE=0 turns that off for the launches that follow.  A unit that is left out could not
 have been met, so sums (byte for byte), samples, misses and the ray count must be the same with and
 without: on the scene-specialised build and the generic one, for bounce.txt's cameras outside the room

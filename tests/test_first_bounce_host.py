@@ -2,7 +2,7 @@
 
 In the camera-ray iteration of a rounds ticket a wave of one 8x8 block tests only the test units of the
 flat order whose bit is set in the block's mask (unit_masks, block_cull.cpp; trace_units,
-kernels_path.hip).  That is sound only if no camera ray of a block can meet a unit whose bit is clear.
+rt_trace.h).  That is sound only if no camera ray of a block can meet a unit whose bit is clear.
 For every live block and every such unit: the fp64 oracle's primary_ids over the block's pixels names
 no primitive of the unit; and the rays of all four corners of every pixel and of seeded jittered
 positions, formed in numpy float32 as camera_ray forms them, miss in fp64 the unit's own box, built here

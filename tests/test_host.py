@@ -398,17 +398,20 @@ def test_grouped_order_records(rc, name):
 
 def test_experiment_patches_apply():
     """Cost experiments live in tools/exp_patch.py, not in the product kernel: every patch's anchors
-    occur exactly once in kernels_path.hip, and the kernel holds no experiment switches."""
+    occur exactly once over the tracing sources it patches (rt_trace.h, kernels_path.hip and
+    kernels_query.hip), and none of them holds an experiment switch."""
     import importlib.util
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     spec = importlib.util.spec_from_file_location("exp_patch", os.path.join(root, "tools", "exp_patch.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    src = open(os.path.join(root, "raytracercore_amd", "csrc", "kernels_path.hip")).read()
-    assert "RT_EXP_" not in src and "exp_sink" not in src
+    assert mod.FILES == ["rt_trace.h", "kernels_path.hip", "kernels_query.hip"]
+    srcs = {f: open(os.path.join(root, "raytracercore_amd", "csrc", f)).read() for f in mod.FILES}
+    for f, src in srcs.items():
+        assert "RT_EXP_" not in src and "exp_sink" not in src, f
     for name in mod.PATCHES:
-        assert mod.apply(src, [name]) != src, name
+        assert mod.apply(srcs, [name]) != srcs, name
 
 
 def test_vertexnormal_rehit_test_matches_oracle(rc):

@@ -1,13 +1,15 @@
 """Cost experiments on the path kernels, kept out of the product source.
 
 Copies raytracercore_amd/csrc (and include/) into raytracercore_amd/variants/NAME/tree, applies the
-named textual patches below to the copy of kernels_path.hip, and builds the library there
+named textual patches below to the copies of the tracing sources (FILES: rt_trace.h, kernels_path.hip
+and kernels_query.hip), and builds the library there
 (raytracercore_amd/variants/NAME/librtcore_hip.so; load it with RTCORE_LIB=<path>).  The copy's
 sources are what its scene-specialised builds embed, so the patches reach them too.
 
 usage: python tools/exp_patch.py NAME PATCH[,PATCH...] ["EXTRA hipcc flags"]
        python tools/exp_patch.py --list
-A patch is a list of (anchor, replacement) pairs; every anchor must occur exactly once.
+A patch is a list of (anchor, replacement) pairs; every anchor must occur exactly once in the three
+files together.
 """
 from __future__ import annotations
 
@@ -18,6 +20,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "raytracercore_amd", "csrc")
+FILES = ["rt_trace.h", "kernels_path.hip", "kernels_query.hip"]  # what the patches may touch
 
 TRACE_CALL = ("            if (query)\n"
               "                trace_brute<CULL, STATS>(sc, groups, tests, rects, frames, boxes, xf, S.o, S.d, S.prev, b, cnt.tris,\n"
@@ -211,14 +214,21 @@ PATCHES = {
 }
 
 
-def apply(src: str, names: list[str]) -> str:
+def read_sources(csrc: str = CSRC) -> dict[str, str]:
+    return {f: open(os.path.join(csrc, f)).read() for f in FILES}
+
+
+def apply(srcs: dict[str, str], names: list[str]) -> dict[str, str]:
+    """srcs: file name -> text (read_sources); returns the patched copy."""
+    srcs = dict(srcs)
     for name in names:
         for anchor, repl in PATCHES[name]:
-            n = src.count(anchor)
+            n = sum(s.count(anchor) for s in srcs.values())
             if n != 1:
-                sys.exit(f"patch {name}: anchor found {n} times:\n{anchor}")
-            src = src.replace(anchor, repl)
-    return src
+                sys.exit(f"patch {name}: anchor found {n} times in {', '.join(FILES)}:\n{anchor}")
+            for f in srcs:
+                srcs[f] = srcs[f].replace(anchor, repl)
+    return srcs
 
 
 def main() -> None:
@@ -238,11 +248,9 @@ def main() -> None:
     shutil.copytree(os.path.join(ROOT, "include"), os.path.join(tree, "include"))
     dst = os.path.join(tree, "raytracercore_amd", "csrc")  # the repository's layout (source_hash.py)
     shutil.copytree(CSRC, dst, ignore=shutil.ignore_patterns("_obj*"))
-    kp = os.path.join(dst, "kernels_path.hip")
-    with open(kp) as f:
-        src = f.read()
-    with open(kp, "w") as f:
-        f.write(apply(src, names))
+    for fname, text in apply(read_sources(dst), names).items():
+        with open(os.path.join(dst, fname), "w") as f:
+            f.write(text)
     jobs = str(min(16, os.cpu_count() or 8))
     lib = os.path.join(out, "librtcore_hip.so")  # the library alone: the copy has no tests/host for worker_host
     subprocess.run(["make", "-s", "-C", dst, "-j" + jobs, "OUT=" + out, "EXTRA=" + extra, lib], check=True)

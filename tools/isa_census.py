@@ -3,7 +3,7 @@
 
 Reads the disassembly of a code object built with -g (tools/jit_isa.py HEADER 0 OUT -g for the
 scene-specialised kernel), attributes every VALU instruction by its inline chain (llvm-symbolizer -i)
-to the innermost kernels_path.hip function that is not a one-line helper (dot, madd, rcp, ...:
+to the innermost function of the kernel sources (SOURCES) that is not a one-line helper (dot, madd, rcp, ...:
 their instructions count for the caller; rtcore_rng.h code counts as "rng"), and counts the
 instructions per class with the gfx950 issue costs of DESIGN.md §3.2 (tools/micro/valu_forms.hip):
 
@@ -25,6 +25,7 @@ import subprocess
 import sys
 
 LLVM = "/opt/rocm/lib/llvm/bin/"
+SOURCES = ("rt_trace.h", "kernels_path.hip", "kernels_query.hip", "kernels_fold.hip")
 # one-line helpers whose instructions are charged to the function that calls them
 HELPERS = {"dot", "dot3", "dot4", "xyz", "v3", "madd", "kfma", "kmul", "known_zero", "cross", "rcp", "fsqrt", "normalize",
            "vmin", "vmax", "vmin3", "vmax3", "vmax0", "vmax1", "operator+", "operator-", "operator*", "xf_point", "xf_dir",
@@ -66,7 +67,7 @@ def section(block):
     for short, loc in chain:
         if "rtcore_rng.h" in loc:
             return "rng"
-        if "kernels_path.hip" in loc and short not in HELPERS:
+        if any(s in loc for s in SOURCES) and short not in HELPERS:
             return short
     return chain[-1][0] if chain else "?"
 

@@ -7,7 +7,7 @@ import subprocess
 import sys
 
 CSRC = os.environ.get("RTCORE_CSRC") or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "raytracercore_amd", "csrc")
-NAMES = ["rt_jit_prelude.h", "kernels_path.hip", "../../include/rtcore_rng.h", "rt_kernels.h", "rt_internal.h",
+NAMES = ["rt_jit_prelude.h", "kernels_path.hip", "rt_trace.h", "../../include/rtcore_rng.h", "rt_kernels.h", "rt_internal.h",
          "rt_beam.h", "rt_surfel.h", "../../include/rtcore.h"]
 
 
@@ -15,8 +15,9 @@ def main():
     header, grouped, out = sys.argv[1], sys.argv[2], sys.argv[3]
     extra = sys.argv[4:]
     rtc = C.CDLL("/opt/rocm/lib/libhiprtc.so")
-    names = NAMES + ["rt_scene_const.h"]
-    texts = [open(os.path.join(CSRC, n), "rb").read() for n in NAMES] + [open(header, "rb").read()]
+    srcs = [n for n in NAMES if os.path.exists(os.path.join(CSRC, n))]  # (RTCORE_CSRC may name a checkout from before rt_trace.h)
+    names = srcs + ["rt_scene_const.h"]
+    texts = [open(os.path.join(CSRC, n), "rb").read() for n in srcs] + [open(header, "rb").read()]
     main_src = (b'#include "rt_jit_prelude.h"\n#define RT_SCENE_CONST\n#define RT_SCENE_CONST_GROUPED ' +
                 grouped.encode() + b'\n#include "kernels_path.hip"\n')
     prog = C.c_void_p()

@@ -1,13 +1,17 @@
 #!/usr/bin/env python3
-"""Register / occupancy / LDS report of the path kernels (compiles kernels_path.hip for gfx950)."""
+"""Register / occupancy / LDS report of every kernel of the kernel translation units (the Makefile's
+KERNEL_SRCS), compiled for gfx950; run from the repository root."""
 import re
 import subprocess
 import sys
 
+KERNEL_SRCS = ["kernels_exact.hip", "kernels_path.hip", "kernels_query.hip", "kernels_fold.hip"]
 extra = sys.argv[1:]
-cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "--offload-arch=gfx950", "-x", "hip", "-c",
-       "raytracercore_amd/csrc/kernels_path.hip", "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"] + extra
-out = subprocess.run(cmd, capture_output=True, text=True).stderr
+out = ""
+for src in KERNEL_SRCS:
+    cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "--offload-arch=gfx950", "-x", "hip",
+           "-c", "raytracercore_amd/csrc/" + src, "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"] + extra
+    out += subprocess.run(cmd, capture_output=True, text=True).stderr
 cur = None
 rows = {}
 for line in out.splitlines():

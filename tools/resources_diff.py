@@ -2,8 +2,10 @@
 """Compare two -Rpass-analysis=kernel-resource-usage logs kernel by kernel (full mangled names).
 
 usage: resources_diff.py PARENT.log BRANCH.log
-Each log is the stderr of `hipcc ... -c kernels_path.hip -o /dev/null -Rpass-analysis=kernel-resource-usage`
-(`make -C raytracercore_amd/csrc resources` shows the flags).  Prints the kernels only one side has and
+Each log is the stderr of `hipcc ... -c FILE -o /dev/null -Rpass-analysis=kernel-resource-usage` for one kernel
+translation unit or, one after the other in one log, for several (the Makefile's KERNEL_SRCS: kernels_exact.hip,
+kernels_path.hip, kernels_query.hip, kernels_fold.hip; `make -C raytracercore_amd/csrc resources` shows the flags
+and prints such a log).  Prints the kernels only one side has and
 every figure that differs for a kernel both have; exit status 1 if a common kernel differs.
 """
 import re
