@@ -326,6 +326,19 @@ int rt_debug_block_units(const rt_prim* prims, int32_t n_prims, const rt_camera*
    256 MiB.  Returns 1 (on), 0 (off) or a negative rt_status. */
 int rt_debug_start_rows(int32_t kernel, const rt_camera* camera, int32_t w, int32_t h, int32_t spp, int32_t chunks,
                         int32_t grid_blocks, int32_t flags, int64_t* info);
+/* Host only (no device needed): the two decisions of launch overlap.  Returns 1 when a
+   launch runs on a launch set's own stream, beside the tail of the launch before it, 0 when it runs
+   serially on the caller's stream, or a negative rt_status.  launch_flags: 1 the launch is
+   rt_render_device's or rt_render_bands_device's (no other entry overlaps), 8 it repeats the width,
+   height and samples of the launch before it through those entries (no other launch overlaps),
+   16 it runs a BVH kernel (only the brute-force kernels overlap), 2 instrumented (rt_scene_set_stats), 4 tracing (rt_trace_paths); partial_bytes: the launch's partials, which a second
+   set holds again (over 4 GiB: serial); RTCORE_LAUNCH_OVERLAP=0, read per launch, turns it off.  *wait
+   gets what an overlapped launch waits for before it rewrites state the other set's path kernel may be
+   reading, from change_flags: 1 the pixel keys are rebuilt (a new seed), 2 a fresh cull record is
+   uploaded, 4 it replaces a cached one, 8 the scene-specialised kernel is rebuilt, 16 a work buffer
+   grows -- 0 nothing, 1 the other set's path kernel on the set's stream, 2 the same on the host (memory
+   is freed: flags 4, 8, 16). */
+int rt_debug_launch_overlap(int32_t launch_flags, uint64_t partial_bytes, int32_t change_flags, int32_t* wait);
 /* Measurement of a wavefront split's traversal stage.  rt_debug_ray_log: while
    the next instrumented launch of a BVH kernel runs (rt_scene_set_stats; one launch only, then
    logging is off again), the kernel appends every finished query
@@ -1594,8 +1607,19 @@ int rt_last_kernel_ms(rt_scene* scene, float* ms);
 /* Durations in ms of the last n path-tracing kernels launched on this scene, oldest first
  * (1 <= n <= 64 and n <= the launches so far, else RT_ERR_ARG).  Each launch records its own
  * event pair in a ring of 64, so a caller can queue up to 64 launches without a host sync and
- * read their times afterwards.  Waits for those kernels. */
+ * read their times afterwards.  Waits for those kernels.
+ * A time is the time the launch had to itself: t_end[k] - max(t_start[k], t_end[k - 1]), k - 1 the
+ * launch recorded before it.  rt_render_device and rt_render_bands_device run consecutive launches on
+ * two internal streams, so that a launch's path kernel begins in the SIMDs the one before it is leaving
+ * (launch overlap; RTCORE_LAUNCH_OVERLAP=0 turns it off): its start event fires
+ * while its predecessor still runs, and the raw pair would count that time twice.  For a launch that
+ * began after its predecessor ended, this is the raw event pair.  The times of n consecutive launches
+ * add up to no more than the time from the first one's start to the last one's end. */
 int rt_kernel_times(rt_scene* scene, int32_t n, float* ms);
+/* The same n entries as their raw event pairs, t_end[k] - t_start[k]: what rt_kernel_times returned before
+ * launch overlap, and still returns for a launch that began after its predecessor ended (a debug entry:
+ * tests compare the two). */
+int rt_debug_kernel_times_raw(rt_scene* scene, int32_t n, float* ms);
 
 /*
  * Instrumentation (profiling builds of the measurement, not the render): while enabled, the

@@ -307,7 +307,7 @@ _OPTIONAL = ("rt_query_rays", "rt_query_rays_device", "rt_camera_rays", "rt_sele
              "rt_occluded_surfels", "rt_occluded_surfels_device", "rt_render_probes", "rt_render_probes_device",
              "rt_probe_radiance_device", "rt_shade_probes", "rt_shade_probes_device", "rt_render_probe_list_device",
              "rt_probe_select_device", "rt_render_probe_depth_device", "rt_probe_depth_close_device",
-             "rt_shade_probes_depth_device")
+             "rt_shade_probes_depth_device", "rt_debug_launch_overlap", "rt_debug_kernel_times_raw")
 
 _lib: Optional[C.CDLL] = None
 
@@ -398,6 +398,8 @@ def load_library(path: str = "") -> C.CDLL:
                                  [P(C.c_int32), P(C.c_int32), C.c_int64, P(C.c_float), P(C.c_uint8), P(C.c_uint64),
                                   C.c_int64, P(C.c_int32)]),
         "rt_debug_start_rows": (C.c_int, [C.c_int32, P(rt_camera)] + [C.c_int32] * 6 + [P(C.c_int64)]),
+        "rt_debug_launch_overlap": (C.c_int, [C.c_int32, C.c_uint64, C.c_int32, P(C.c_int32)]),
+        "rt_debug_kernel_times_raw": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_float)]),
         "rt_debug_ray_log": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
         "rt_debug_vn_rehit": (C.c_int, [P(C.c_double), P(C.c_double), P(C.c_double), C.c_int32, C.c_double,
                                         C.c_double, P(C.c_float), P(C.c_int32), P(C.c_double), P(C.c_double)]),
@@ -706,6 +708,24 @@ def start_rows(kernel: int, camera: rt_camera, w: int, h: int, spp: int, chunks:
     if on < 0:
         _check(on)
     return {"on": bool(on), "rows": int(info[0]), "bytes": int(info[1]), "chunk": int(info[2])}
+
+
+def launch_overlap(device_entry: bool = True, repeats: bool = True, bvh: bool = False, instrumented: bool = False, tracing: bool = False, partial_bytes: int = 0,
+                   pkeys_rebuilt: bool = False, cull_fresh: bool = False, cull_replaced: bool = False,
+                   jit_rebuilt: bool = False, buffer_grown: bool = False) -> Tuple[bool, int]:
+    """rt_debug_launch_overlap (host code, no GPU): (whether such a launch overlaps the one before it, what it
+    waits for before it rewrites shared state: 0 nothing, 1 the other launch set's path kernel on the set's
+    stream, 2 the same on the host)."""
+    lib = load_library()
+    wait = C.c_int32(-1)
+    on = lib.rt_debug_launch_overlap(int(bool(device_entry)) | int(bool(instrumented)) << 1 | int(bool(tracing)) << 2
+                                     | int(bool(repeats)) << 3 | int(bool(bvh)) << 4,
+                                     int(partial_bytes),
+                                     int(bool(pkeys_rebuilt)) | int(bool(cull_fresh)) << 1 | int(bool(cull_replaced)) << 2
+                                     | int(bool(jit_rebuilt)) << 3 | int(bool(buffer_grown)) << 4, C.byref(wait))
+    if on < 0:
+        _check(on)
+    return bool(on), int(wait.value)
 
 
 def ref_bvh_export(prims: Sequence[rt_prim]) -> Tuple[np.ndarray, np.ndarray, int, int]:
@@ -2365,6 +2385,12 @@ class GpuRaytracer:
         (n <= 64): launches queued without a host sync, timed afterwards."""
         out = (C.c_float * max(n, 1))()
         _check(self.lib.rt_kernel_times(self.handle, n, out))
+        return [float(v) for v in out[:n]]
+
+    def kernel_times_raw(self, n: int) -> List[float]:
+        """rt_debug_kernel_times_raw: the same n entries as their raw event pairs (end - start)."""
+        out = (C.c_float * max(n, 1))()
+        _check(self.lib.rt_debug_kernel_times_raw(self.handle, n, out))
         return [float(v) for v in out[:n]]
 
     STAT_NAMES = ("node_visits", "tri_tests", "sph_tests", "cyc_start", "cyc_trace", "cyc_shade", "wave_iters",

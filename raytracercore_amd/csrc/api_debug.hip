@@ -616,6 +616,20 @@ int rt_debug_start_rows(int32_t kernel, const rt_camera* camera, int32_t w, int3
     return sr.on ? 1 : 0;
 }
 
+// Host only: run_path's two decisions about launch overlap (launch_overlaps, overlap_wait).
+int rt_debug_launch_overlap(int32_t launch_flags, uint64_t partial_bytes, int32_t change_flags, int32_t* wait)
+{
+    if (launch_flags < 0 || launch_flags > 31 || change_flags < 0 || change_flags > 31 || !wait) {
+        set_error("rt_debug_launch_overlap: bad argument");
+        return RT_ERR_ARG;
+    }
+    const OverlapChange c{(change_flags & 1) != 0, (change_flags & 2) != 0, (change_flags & 4) != 0,
+                          (change_flags & 8) != 0, (change_flags & 16) != 0};
+    *wait = (int32_t)overlap_wait(c);
+    return launch_overlaps((launch_flags & 1) != 0, (launch_flags & 8) != 0, (launch_flags & 16) != 0, (launch_flags & 2) != 0, (launch_flags & 4) != 0,
+                           (size_t)partial_bytes) ? 1 : 0;
+}
+
 int rt_parse_scene(const char* text, rt_scene_params* params, rt_prim* prims, int32_t* n_prims, rt_camera* cameras,
                    int32_t* n_cameras)
 {

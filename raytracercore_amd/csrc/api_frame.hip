@@ -149,9 +149,10 @@ int rt_render_bands_device(rt_scene* s, int32_t band, int32_t band_stride, int32
     PathParams p = make_params(s, 0, 0, W, rows, spp, seed, sample_base);
     set_band(p, band, band_stride, band_offset);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    int rc = run_path(s, p, d_rays, st);
+    int rc = run_path(s, p, d_rays, st, true, true);
     if (rc != RT_OK) return rc;
-    HIP_TRY(launch_accumulate(p, sum, n, m, st, (size_t)plane));
+    HIP_TRY(launch_accumulate(p, sum, n, m, st, (size_t)plane, s->open_set >= 0 ? s->set_rays.p + s->open_set : nullptr,
+                              d_rays));
     return end_op(s, st);
 }
 

@@ -12,9 +12,16 @@ namespace rtc {
 namespace {
 
 // plane: element stride between the R, G and B planes of sum (>= w*h; a gather slot may be taller
-// than the band set written into it)
-__global__ void accumulate_kernel(PathParams p, double* sum, uint32_t* samples, uint32_t* misses, size_t plane)
+// than the band set written into it).  set_rays (an overlapped launch, run_path): the launch set's own
+// ray counter, which the path kernel added into; one thread moves it into the caller's and zeroes it, so
+// the caller's counter changes in its stream's order and the path kernel touches no caller memory.
+__global__ void accumulate_kernel(PathParams p, double* sum, uint32_t* samples, uint32_t* misses, size_t plane,
+                                  unsigned long long* set_rays, unsigned long long* rays)
 {
+    if (set_rays && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+        atomicAdd(rays, *set_rays);
+        *set_rays = 0;
+    }
     const int x = blockIdx.x * 16 + (threadIdx.x & 15);
     const int y = blockIdx.y * 16 + (threadIdx.x >> 4);
     if (x >= p.w || y >= p.h) return;
@@ -424,11 +431,12 @@ __global__ void compact_nodes_kernel(NodeF* __restrict__ n2, int n_n2, Node4Q* _
 } // namespace
 
 hipError_t launch_accumulate(const PathParams& p, double* d_sum, uint32_t* d_samples, uint32_t* d_misses, hipStream_t stream,
-                             size_t plane)
+                             size_t plane, unsigned long long* d_set_rays, unsigned long long* d_rays)
 {
     if (plane == 0) plane = (size_t)p.w * p.h;
     dim3 grid((p.w + 15) / 16, (p.h + 15) / 16);
-    hipLaunchKernelGGL(accumulate_kernel, grid, dim3(256), 0, stream, p, d_sum, d_samples, d_misses, plane);
+    hipLaunchKernelGGL(accumulate_kernel, grid, dim3(256), 0, stream, p, d_sum, d_samples, d_misses, plane, d_set_rays,
+                       d_rays);
     return hipGetLastError();
 }
 

@@ -280,6 +280,23 @@ StartRowsPlan plan_start_rows(int kernel, bool instrumented, bool vertex_normals
     return StartRowsPlan{true, chunk, bytes};
 }
 
+// Launch overlap: which launches run beside their predecessor's tail, and what such a launch waits for
+// before it rewrites what the other set's kernel reads (launch_params.h).
+bool launch_overlaps(bool device_entry, bool repeats, bool bvh, bool instrumented, bool tracing, size_t partial_bytes)
+{
+    if (!device_entry || !repeats || bvh || instrumented || tracing || partial_bytes > kOverlapSetCap) return false;
+    if (const char* e = getenv("RTCORE_LAUNCH_OVERLAP"))
+        if (atoi(e) == 0) return false;
+    return true;
+}
+
+OverlapWait overlap_wait(const OverlapChange& c)
+{
+    if (c.cull_replaced || c.jit_rebuilt || c.buffer_grown) return kOverlapHostWait; // memory is freed
+    if (c.pkeys_rebuilt || c.cull_fresh) return kOverlapStreamWait;
+    return kOverlapNoWait;
+}
+
 // Band-set launch: tile row r is frame row ((r / band) * stride + offset) * band + r % band; the
 // kernel divides by a shift for power-of-two bands, else by the fp32 reciprocal.
 void set_band(PathParams& p, int band, int stride, int offset)

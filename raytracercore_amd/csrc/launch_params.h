@@ -49,6 +49,29 @@ struct StartRowsPlan {
 StartRowsPlan plan_start_rows(int kernel, bool instrumented, bool vertex_normals, int camera_kind, bool dof, int chunk,
                               int grid_blocks);
 
+// Launch overlap (run_path, scene_upload.hip; rt_scene::LaunchSet).  launch_overlaps: whether a launch runs
+// on a launch set's own stream beside the previous launch's tail: only the device entries that repeat in
+// a progressive render (rt_render_device, rt_render_bands_device) and only a launch that repeats the
+// width, height and samples of the one before it through those entries (a progressive render does; a
+// small launch beside a large one would wait for the slots the large one's persistent waves hold, end
+// after its successor, and rt_kernel_times could no longer say which time was whose), only the brute-force kernels
+// (the BVH kernel is bound by the vector-memory pipeline, and a second kernel's waves beside its last ones cost
+// the 1M-triangle launch more than the tail gives: 38.75-38.79 -> 39.32-39.46 ms per step), never an
+// instrumented or tracing launch, not when the second set's partials would exceed kOverlapSetCap bytes,
+// and not under RTCORE_LAUNCH_OVERLAP=0 (read per launch).
+constexpr size_t kOverlapSetCap = 4ull << 30; // (the 1M-triangle 1080p x 64 spp launch: 2.1 GB)
+bool launch_overlaps(bool device_entry, bool repeats, bool bvh, bool instrumented, bool tracing, size_t partial_bytes);
+// overlap_wait: what an overlapped launch waits for before it touches state that the other set's path
+// kernel, possibly in flight, reads: nothing when the launch rewrites none of it; the other set's
+// path_done on its stream when it rebuilds the pixel keys (a new seed) or uploads a fresh cull record;
+// the same on the host when memory is freed: a cull entry replaced, a scene-specialised kernel rebuilt,
+// a work buffer grown.
+enum OverlapWait { kOverlapNoWait = 0, kOverlapStreamWait = 1, kOverlapHostWait = 2 };
+struct OverlapChange {
+    bool pkeys_rebuilt, cull_fresh, cull_replaced, jit_rebuilt, buffer_grown;
+};
+OverlapWait overlap_wait(const OverlapChange& c);
+
 // A band set (band, stride, offset) is frame rows {y : (y / band) % stride == offset}.
 int band_set_rows(int H, int band, int stride, int offset);
 int band_slot_rows(int H, int band, int stride); // largest band set of the split

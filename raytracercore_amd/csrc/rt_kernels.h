@@ -396,9 +396,11 @@ hipError_t compact_leaves(const TestRec* d_tests, int n_records, float4* d_rows,
                           Node4Q* d_nodes4, int n_nodes4, bool rewrite, hipStream_t stream);
 
 // partial -> fp64 planar accumulators (d_sum planes R | G | B, each `plane` doubles apart;
-// 0 = w*h), d_samples, d_misses (row-major w*h), added to.
+// 0 = w*h), d_samples, d_misses (row-major w*h), added to.  d_set_rays (an overlapped launch): the
+// launch set's ray counter, moved into d_rays and zeroed.
 hipError_t launch_accumulate(const PathParams& p, double* d_sum, uint32_t* d_samples, uint32_t* d_misses,
-                             hipStream_t stream, size_t plane = 0);
+                             hipStream_t stream, size_t plane = 0, unsigned long long* d_set_rays = nullptr,
+                             unsigned long long* d_rays = nullptr);
 // SampleSet.GetOutput over planar accumulators (row-major w*h) -> ARGB codes.
 hipError_t launch_tonemap(int w, int h, const double* d_sum, const uint32_t* d_samples, const uint32_t* d_misses,
                           rt_color back, double back_alpha, double exposure, int32_t* d_argb, hipStream_t stream);

@@ -256,7 +256,13 @@ struct rt_scene {
         HostBuf<unsigned int> host;
         hipEvent_t up = nullptr;
     };
+    // At least 3 entries, for launch overlap: a replaced entry's fresh record is uploaded on a launch set's
+    // stream, which is behind both sets' path kernels and the set's own previous fold but not behind
+    // the fold of the other set's latest launch, still queued on the caller's stream, which reads its
+    // launch's record too.  The entry replaced is the least recently used, so with 3 or more entries it
+    // is neither that launch's nor the one's before it; with 2 or fewer this would be a race.
     static constexpr int kCullEntries = 4;
+    static_assert(kCullEntries >= 3, "launch overlap: a replaced cull entry must not be one of the last two launches'");
     std::array<CullEntry, kCullEntries> cull_cache;
     uint64_t cull_clock = 0;
     FlatUnits units;            // the flat order's test units and their boxes (scene_records.h), with the bound
@@ -264,11 +270,39 @@ struct rt_scene {
     bool has_camera = false;
     bool flat_overflow = false; // the flat brute-force order exceeds GroupRec's counts (BruteOrder::overflow)
     hipStream_t stream = nullptr;
-    // Timing of the path kernels: the i-th launch records the event pair i % kTimeRing, so a caller
-    // can queue up to that many launches before it reads their durations (rt_kernel_times).
-    static constexpr int kTimeRing = 64;
-    std::array<hipEvent_t, kTimeRing> t_start{}, t_end{};
+    // Timing of the path kernels: the i-th launch records the event pair i % kTimeSlots, so a caller
+    // can queue up to kTimeRing launches before it reads their durations (rt_kernel_times).  One pair
+    // more than that is kept: the oldest entry's time is measured from its predecessor's end when the
+    // two overlapped (launch overlap, below).
+    static constexpr int kTimeRing = 64, kTimeSlots = kTimeRing + 1;
+    std::array<hipEvent_t, kTimeSlots> t_start{}, t_end{};
     uint64_t launches = 0;
+    // Launch overlap (run_path): rt_render_device and rt_render_bands_device alternate between two
+    // launch sets, so that launch k + 1's path kernel, queued on its set's own stream, enters the SIMDs
+    // that launch k's last waves leave.  A set is the work buffers a path kernel writes (partials,
+    // dispensers, start rows, stack overflow area, a ray counter of its own in set_rays), the stream its
+    // path kernel runs on and two events: path_done (after the path kernel, on the set's stream) and
+    // fold_done (after the fold of its partials, on the caller's stream; the set's next launch waits for
+    // it).  Set 0's buffers are the scene's (partial, counter, starts, stack_ovf above), which every other
+    // operation uses, serially, once both sets are idle (done_ev below covers both folds); alt holds set 1's.
+    struct LaunchSet {
+        hipStream_t stream = nullptr;
+        hipEvent_t path_done = nullptr, fold_done = nullptr;
+        bool path_recorded = false, fold_recorded = false;
+        bool after_serial = false; // a serial operation ran since the set's last launch: wait for done_ev
+        bool after_shared = false; // the other set's stream rewrote shared state since: wait for shared_ev
+    };
+    std::array<LaunchSet, 2> sets;
+    struct {
+        DevBuf<unsigned int> counter;
+        DevBuf<float4> starts, partial;
+        DevBuf<int> stack_ovf;
+    } alt;
+    DevBuf<unsigned long long> set_rays; // one counter per set: the path kernel adds, the fold moves it to the caller's
+    hipEvent_t shared_ev = nullptr;      // after a set's stream rewrote pixel keys or a cull record
+    uint64_t overlapped = 0;             // overlapped launches so far (launch k of them uses set k & 1)
+    int prev_w = 0, prev_h = 0, prev_spp = 0; // the previous launch of the two entries (launch_overlaps: repeats)
+    int open_set = -1;                   // the set of the overlapped launch whose fold end_op closes, or -1
     // Launches share per-scene scratch (partials, work counter, stack overflow area).  The end of
     // the last render operation is recorded here; an operation on a different stream waits for it.
     hipEvent_t done_ev = nullptr;
@@ -295,10 +329,16 @@ struct rt_scene {
             (void)hipStreamSynchronize(copy_stream);
             (void)hipStreamDestroy(copy_stream);
         }
-        for (int i = 0; i < kTimeRing; i++) {
+        for (int i = 0; i < kTimeSlots; i++) {
             if (t_start[i]) (void)hipEventDestroy(t_start[i]);
             if (t_end[i]) (void)hipEventDestroy(t_end[i]);
         }
+        for (LaunchSet& l : sets) { // (the streams are synchronised by rt_scene_destroy)
+            if (l.path_done) (void)hipEventDestroy(l.path_done);
+            if (l.fold_done) (void)hipEventDestroy(l.fold_done);
+            if (l.stream) (void)hipStreamDestroy(l.stream);
+        }
+        if (shared_ev) (void)hipEventDestroy(shared_ev);
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -328,7 +368,11 @@ int prepare_jit(rt_scene* s);
 int check_tile(rt_scene* s, int x0, int y0, int w, int h);
 PathParams make_params(rt_scene* s, int x0, int y0, int w, int h, int spp, uint64_t seed, uint64_t base,
                        double chunk_npix = 0.0);
-int run_path(rt_scene* s, PathParams& p, unsigned long long* d_rays, hipStream_t stream, bool timed = true);
+// may_overlap: the launch may run on a launch set's own stream (rt_scene::LaunchSet).  When it does,
+// s->open_set names the set on return: the caller folds the partials on `stream` (run_path has made it
+// wait for the path kernel), hands the fold set_rays.p + open_set to move into d_rays, and calls end_op.
+int run_path(rt_scene* s, PathParams& p, unsigned long long* d_rays, hipStream_t stream, bool timed = true,
+             bool may_overlap = false);
 int upload_params(rt_scene* s, const PathParams& p, hipStream_t stream, const PathParams** d_out);
 int end_op(rt_scene* s, hipStream_t stream);
 int queue_copy(rt_scene* s, CopyPlan& plan, const void* d_src, size_t a, size_t b, size_t rec_bytes, int k,

@@ -118,7 +118,15 @@ int rt_scene_create(const rt_scene_params* params, const rt_prim* prims, int32_t
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     s->n_cu = prop.multiProcessorCount;
     HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    for (int i = 0; i < rt_scene::kTimeRing; i++) {
+    // the launch sets' streams, created one after the other: the runtime deals hardware queues to streams
+    // in the order they are created, and two streams on one queue run in submission order
+    for (rt_scene::LaunchSet& l : s->sets) {
+        HIP_TRY(hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(&l.path_done, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&l.fold_done, hipEventDisableTiming));
+    }
+    HIP_TRY(hipEventCreateWithFlags(&s->shared_ev, hipEventDisableTiming));
+    for (int i = 0; i < rt_scene::kTimeSlots; i++) {
         HIP_TRY(hipEventCreate(&s->t_start[i]));
         HIP_TRY(hipEventCreate(&s->t_end[i]));
     }
@@ -139,6 +147,8 @@ int rt_scene_create(const rt_scene_params* params, const rt_prim* prims, int32_t
     rc = resolve_traversal(s.get());
     if (rc != RT_OK) return rc;
     HIP_TRY(s->rays.reserve(1));
+    HIP_TRY(s->set_rays.reserve(2));
+    HIP_TRY(hipMemset(s->set_rays.p, 0, 2 * sizeof(unsigned long long)));
     *out_scene = s.release();
     return RT_OK;
 }
@@ -213,6 +223,8 @@ void rt_scene_destroy(rt_scene* s)
     if (!s) return;
     (void)hipSetDevice(s->device);
     (void)hipStreamSynchronize(s->stream);
+    for (rt_scene::LaunchSet& l : s->sets)
+        if (l.stream) (void)hipStreamSynchronize(l.stream);
     delete s;
 }
 
@@ -229,9 +241,10 @@ int rt_render_device(rt_scene* s, int32_t x0, int32_t y0, int32_t w, int32_t h, 
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     PathParams p = make_params(s, x0, y0, w, h, spp, seed, sample_base);
-    rc = run_path(s, p, d_rays, st);
+    rc = run_path(s, p, d_rays, st, true, true);
     if (rc != RT_OK) return rc;
-    HIP_TRY(launch_accumulate(p, d_sum, d_samples, d_misses, st));
+    HIP_TRY(launch_accumulate(p, d_sum, d_samples, d_misses, st, 0, s->open_set >= 0 ? s->set_rays.p + s->open_set : nullptr,
+                              d_rays));
     return end_op(s, st);
 }
 
@@ -243,8 +256,35 @@ int rt_kernel_times(rt_scene* s, int32_t n, float* ms)
         return RT_ERR_ARG;
     }
     HIP_TRY(hipSetDevice(s->device));
+    // The time a launch had to itself: t_end[k] - max(t_start[k], t_end[k - 1]).  An overlapped launch's
+    // start event fires while the launch before it still runs, and the raw pair would count that time
+    // twice; for a serial launch the predecessor ended before the start, and this is the raw pair.
     for (int i = 0; i < n; i++) { // oldest first
-        const int slot = (int)((s->launches - (uint64_t)n + (uint64_t)i) % rt_scene::kTimeRing);
+        const uint64_t k = s->launches - (uint64_t)n + (uint64_t)i;
+        const int slot = (int)(k % rt_scene::kTimeSlots);
+        HIP_TRY(hipEventSynchronize(s->t_end[slot]));
+        HIP_TRY(hipEventElapsedTime(ms + i, s->t_start[slot], s->t_end[slot]));
+        if (k > 0) {
+            const int prev = (int)((k - 1) % rt_scene::kTimeSlots);
+            float since = 0.0f;
+            HIP_TRY(hipEventSynchronize(s->t_end[prev]));
+            HIP_TRY(hipEventElapsedTime(&since, s->t_end[prev], s->t_end[slot]));
+            if (since > 0.0f && since < ms[i]) ms[i] = since;
+        }
+    }
+    return RT_OK;
+}
+
+// rt_kernel_times' entries as the raw event pairs t_end[k] - t_start[k] (tests: what rt_kernel_times makes of them).
+int rt_debug_kernel_times_raw(rt_scene* s, int32_t n, float* ms)
+{
+    if (!s || !ms || n < 1 || n > rt_scene::kTimeRing || (uint64_t)n > s->launches) {
+        set_error("rt_debug_kernel_times_raw: bad argument");
+        return RT_ERR_ARG;
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    for (int i = 0; i < n; i++) {
+        const int slot = (int)((s->launches - (uint64_t)n + (uint64_t)i) % rt_scene::kTimeSlots);
         HIP_TRY(hipEventSynchronize(s->t_end[slot]));
         HIP_TRY(hipEventElapsedTime(ms + i, s->t_start[slot], s->t_end[slot]));
     }

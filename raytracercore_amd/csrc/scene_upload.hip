@@ -517,7 +517,7 @@ int check_tile(rt_scene* s, int x0, int y0, int w, int h)
 // and again after a group-order change.  Returns 1 when it is to be launched, 0 to launch the
 // generic kernel: JIT off, the instrumented kernel, a BVH or unstaged variant, or a failed build
 // (the generic kernel computes the same; the failure is kept in s->jit.error).
-int prepare_jit(rt_scene* s)
+static bool jit_eligible(const rt_scene* s)
 {
     // Both brute-force orders (RTCORE_JIT_GROUPED=0 leaves the grouped one generic).  The grouped
     // order's group loop is unrolled by pragma: left to the compiler's heuristics it stayed a loop
@@ -525,8 +525,13 @@ int prepare_jit(rt_scene* s)
     // unrolled, die.txt C3 36.6 -> 30.9 ms.
     const char* eg = getenv("RTCORE_JIT_GROUPED");
     const bool grouped_ok = !(eg && eg[0] == '0');
-    const bool eligible = jit_enabled() && !s->stats_on &&
-                          (s->variant == path_variant(0, true) || (grouped_ok && s->variant == path_variant(1, true)));
+    return jit_enabled() && !s->stats_on &&
+           (s->variant == path_variant(0, true) || (grouped_ok && s->variant == path_variant(1, true)));
+}
+
+int prepare_jit(rt_scene* s)
+{
+    const bool eligible = jit_eligible(s);
     if (!eligible) {
         s->jit.status = 0;
         return 0;
@@ -624,6 +629,14 @@ int upload_params(rt_scene* s, const PathParams& p, hipStream_t stream, const Pa
 // blocks) and every larger launch is culled.  Read per launch, like RTCORE_SCENE_BOUND:
 // RTCORE_BLOCK_CULL=0 turns it off, RTCORE_BLOCK_CULL_MIN=<blocks> sets the threshold.
 constexpr int kCullMinBlocks = 4096;
+// Both launch sets' path kernels have ended (host wait): before memory they may read is freed.
+static int wait_sets_host(rt_scene* s)
+{
+    for (rt_scene::LaunchSet& l : s->sets)
+        if (l.path_recorded) HIP_TRY(hipEventSynchronize(l.path_done));
+    return RT_OK;
+}
+
 static int plan_block_cull(rt_scene* s, const PathParams& p, rt_scene::CullEntry*& ent, bool& fresh)
 {
     ent = nullptr;
@@ -651,6 +664,11 @@ static int plan_block_cull(rt_scene* s, const PathParams& p, rt_scene::CullEntry
         for (rt_scene::CullEntry& e : s->cull_cache)
             if (age(e) < age(*c)) c = &e;
         c->valid = false;
+        // an entry is replaced and its record may be reallocated: a path kernel of either launch set,
+        // queued on the set's own stream, may still read it (overlap_wait's cull_replaced case, waited
+        // for here where the entry is chosen; a miss is rare, once per camera and window)
+        const int wrc = wait_sets_host(s);
+        if (wrc != RT_OK) return wrc;
         if (c->up) HIP_TRY(hipEventSynchronize(c->up)); // the previous upload has read the pinned words
         else HIP_TRY(hipEventCreateWithFlags(&c->up, hipEventDisableTiming));
         std::vector<unsigned char> dead;
@@ -701,8 +719,22 @@ static int plan_block_cull(rt_scene* s, const PathParams& p, rt_scene::CullEntry
 }
 
 // Launch the path kernel for p (work buffers sized here), timing it with the scene's events.
-int run_path(rt_scene* s, PathParams& p, unsigned long long* d_rays, hipStream_t stream, bool timed)
+// may_overlap (rt_render_device, rt_render_bands_device): the launch runs on a launch set's own stream
+// when launch_overlaps allows it (rt_scene::LaunchSet, launch_params.h: a launch that repeats the one
+// before it in width, height and samples).  Launch k of these uses set k & 1.
+// Its stream waits for the fold of the set's previous launch (fold_done, two launches ago), then runs what
+// the caller's stream runs for a serial launch -- a fresh cull record's upload, the dispenser memset, a
+// pixel-key rebuild, the parameter upload, the path kernel -- and records path_done; the caller's stream
+// waits for path_done, and the caller queues the fold there.  The path kernel does not wait for the
+// caller's stream: it reads and writes library-owned memory only (its rays go to the set's counter, which
+// the fold moves into d_rays), so it starts as soon as the previous launch's last waves leave room.
+// What both sets read -- pixel keys, cull records, the scene-specialised kernel -- is not rewritten
+// while the other set's kernel can be in flight (overlap_wait), and a rewrite on one set's stream is
+// waited for by the other's next launch (shared_ev).  Every other launch runs on `stream` with set 0's
+// buffers: `stream` is behind both sets' folds (its own order, or done_ev), hence behind both path kernels.
+int run_path(rt_scene* s, PathParams& p, unsigned long long* d_rays, hipStream_t stream, bool timed, bool may_overlap)
 {
+    s->open_set = -1;
     // A brute-force launch is planned over the blocks that can see the scene (block_cull.h): tickets,
     // item ranges, n_pad, the item total and the partial buffer over the n_live live blocks in their
     // original order.  Chunks, samples per item and pool stay the window's, so an item holds the same
@@ -730,11 +762,48 @@ int run_path(rt_scene* s, PathParams& p, unsigned long long* d_rays, hipStream_t
         set_error("tile x spp too large for one launch; split the tile");
         return RT_ERR_ARG;
     }
-    HIP_TRY(s->partial.reserve(need));
-    HIP_TRY(s->counter.reserve(kMaxSplit * kSplitStride));
-    p.partial = s->partial.p;
-    p.counter = s->counter.p;
-    p.rays = d_rays;
+    const bool repeats = may_overlap && p.w == s->prev_w && p.h == s->prev_h && p.spp == s->prev_spp;
+    if (may_overlap) s->prev_w = p.w, s->prev_h = p.h, s->prev_spp = p.spp;
+    const bool overlap = may_overlap && timed && launch_overlaps(true, repeats, (s->variant >> 1) >= 2, s->stats_on, s->tracing, need * sizeof(float4));
+    const int set = overlap ? (int)(s->overlapped & 1) : 0;
+    rt_scene::LaunchSet& ls = s->sets[set];
+    const hipStream_t st = overlap ? ls.stream : stream; // the path kernel's stream
+    DevBuf<float4>& partial = set ? s->alt.partial : s->partial;
+    DevBuf<unsigned int>& counter = set ? s->alt.counter : s->counter;
+    DevBuf<float4>& starts = set ? s->alt.starts : s->starts;
+    DevBuf<int>& stack_ovf = set ? s->alt.stack_ovf : s->stack_ovf;
+    int grid = s->n_cu * (s->stats_on ? s->stats_blocks_per_cu : s->blocks_per_cu);
+    const size_t stack_need = s->variant >= 4 ? (size_t)grid * 256 * kStackOverflow : 0;
+    static const bool pkeys_on = !(getenv("RTCORE_PIXEL_KEYS") && getenv("RTCORE_PIXEL_KEYS")[0] == '0');
+    const bool pkeys_use = (s->variant >> 1) < 2 && !s->stats_on && pkeys_on;
+    const bool pkeys_rebuild = pkeys_use && (!s->pkeys_valid || s->pkeys_seed != p.seed);
+    if (overlap) {
+        // (a grown start-row buffer is seen below, once the grid is known: its reserve waits there)
+        // (prepare_jit would look at the build again: a new variant or group order)
+        const bool jit_stale = jit_eligible(s) && (s->jit.variant != s->variant || s->jit.gen != s->jit_gen);
+        const OverlapChange change{pkeys_rebuild, cull && cull_fresh, false /* waited for in plan_block_cull */, jit_stale,
+                                   need > partial.n || (size_t)(kMaxSplit * kSplitStride) > counter.n || stack_need > stack_ovf.n};
+        // (The host waits are belt and braces: hipFree synchronises the device and a module's eviction
+        // does too, which the serial path has always relied on; here the order is also written down.)
+        const OverlapWait w = overlap_wait(change);
+        rt_scene::LaunchSet& other = s->sets[set ^ 1];
+        if (w == kOverlapHostWait) {
+            const int wrc = wait_sets_host(s);
+            if (wrc != RT_OK) return wrc;
+            if (ls.fold_recorded) HIP_TRY(hipEventSynchronize(ls.fold_done)); // the fold reads the buffer that grows
+        } else if (w == kOverlapStreamWait && other.path_recorded) {
+            HIP_TRY(hipStreamWaitEvent(st, other.path_done, 0));
+        }
+        if (ls.fold_recorded) HIP_TRY(hipStreamWaitEvent(st, ls.fold_done, 0));
+        if (ls.after_serial && s->any_op) HIP_TRY(hipStreamWaitEvent(st, s->done_ev, 0));
+        if (ls.after_shared) HIP_TRY(hipStreamWaitEvent(st, s->shared_ev, 0));
+        ls.after_serial = ls.after_shared = false;
+    }
+    HIP_TRY(partial.reserve(need));
+    HIP_TRY(counter.reserve(kMaxSplit * kSplitStride));
+    p.partial = partial.p;
+    p.counter = counter.p;
+    p.rays = overlap ? s->set_rays.p + set : d_rays;
     p.stats = s->stats_on ? (s->tracing ? s->trace_stats.p : s->stats_buf.p) : nullptr;
     // rt_debug_ray_log arms the next instrumented BVH launch only, so a buffer the caller frees
     // afterwards is never written (rt_trace_paths' launch is not one of them)
@@ -742,21 +811,23 @@ int run_path(rt_scene* s, PathParams& p, unsigned long long* d_rays, hipStream_t
     p.ray_log_n = s->ray_log_n;
     p.ray_log_cap = s->ray_log_cap;
     if (p.ray_log) s->ray_log = nullptr;
-    // order after the previous operation when it ran on another stream (shared scratch)
+    // order after the previous operation when it ran on another stream (shared scratch; an overlapped
+    // launch: the fold's order among the caller's streams)
     if (s->any_op && stream != s->last_stream) HIP_TRY(hipStreamWaitEvent(stream, s->done_ev, 0));
+    bool shared_written = false;
     if (cull && cull_fresh) { // a new record: after the operations that read the entry's previous one
         const size_t words = cull->masks ? cull_masks_at((unsigned)cull->n_live, (unsigned)cull->n_blocks) + 2 * (size_t)cull->n_live
                                          : (size_t)kCullTable + (size_t)cull->n_live + (size_t)cull->n_blocks;
-        HIP_TRY(hipMemcpyAsync(cull->dev.p, cull->host.p, words * sizeof(unsigned int), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipEventRecord(cull->up, stream));
+        HIP_TRY(hipMemcpyAsync(cull->dev.p, cull->host.p, words * sizeof(unsigned int), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(cull->up, st));
         cull->valid = true;
+        shared_written = true;
     }
-    HIP_TRY(hipMemsetAsync(p.counter, 0, sizeof(unsigned int) * kSplitStride * p.n_split, stream));
-    int grid = s->n_cu * (s->stats_on ? s->stats_blocks_per_cu : s->blocks_per_cu);
+    HIP_TRY(hipMemsetAsync(p.counter, 0, sizeof(unsigned int) * kSplitStride * p.n_split, st));
     p.stack_ovf = nullptr;
     if (s->variant >= 4) { // BVH kernels: the stacks' global overflow area
-        HIP_TRY(s->stack_ovf.reserve((size_t)grid * 256 * kStackOverflow));
-        p.stack_ovf = s->stack_ovf.p;
+        HIP_TRY(stack_ovf.reserve(stack_need));
+        p.stack_ovf = stack_ovf.p;
     }
     const int jit = s->tracing ? 0 : prepare_jit(s); // (rt_trace_paths: the generic kernel, the build's state untouched)
     int jit_grid = jit ? s->n_cu * s->jit.blocks_per_cu : 0;
@@ -778,21 +849,21 @@ int run_path(rt_scene* s, PathParams& p, unsigned long long* d_rays, hipStream_t
         if (jit) jit_grid = s->n_cu * std::min(s->jit.blocks_per_cu, cap);
         else grid = s->n_cu * std::min(s->blocks_per_cu, cap);
     }
-    const int tslot = (int)(s->launches % rt_scene::kTimeRing);
-    if (timed) HIP_TRY(hipEventRecord(s->t_start[tslot], stream));
+    const int tslot = (int)(s->launches % rt_scene::kTimeSlots);
+    if (timed) HIP_TRY(hipEventRecord(s->t_start[tslot], st));
     fill_launch(s->dev, s->variant, p);
     // The brute-force kernels read each item's pixel key (two lowbias32 rounds of the seed key and
     // the frame pixel index, rtcore_rng.h) from a per-scene table, built here once per seed (a
     // ~10-us kernel on the launch stream): the same keys, without hashing in the loop.
     // RTCORE_PIXEL_KEYS=0 hashes per item (A/B).
     p.pkeys = nullptr;
-    static const bool pkeys_on = !(getenv("RTCORE_PIXEL_KEYS") && getenv("RTCORE_PIXEL_KEYS")[0] == '0');
-    if ((s->variant >> 1) < 2 && !s->stats_on && pkeys_on) {
-        if (!s->pkeys_valid || s->pkeys_seed != p.seed) {
+    if (pkeys_use) {
+        if (pkeys_rebuild) {
             HIP_TRY(s->pkeys.reserve((size_t)s->params.width * (size_t)s->params.height));
-            HIP_TRY(launch_pixel_keys(p.seed_key, s->params.width, s->params.height, s->pkeys.p, stream));
+            HIP_TRY(launch_pixel_keys(p.seed_key, s->params.width, s->params.height, s->pkeys.p, st));
             s->pkeys_valid = true;
             s->pkeys_seed = p.seed;
+            shared_written = true;
         }
         p.pkeys = s->pkeys.p;
     }
@@ -802,24 +873,39 @@ int run_path(rt_scene* s, PathParams& p, unsigned long long* d_rays, hipStream_t
     const StartRowsPlan sr = plan_start_rows(s->variant >> 1, s->stats_on || s->tracing, s->dev.n_vn > 0, s->camf.kind,
                                              s->camf.dof != 0.0f, p.chunk, jit ? jit_grid : grid);
     if (sr.on) {
-        HIP_TRY(s->starts.reserve(sr.bytes / sizeof(float4)));
-        p.starts = s->starts.p;
+        if (overlap && sr.bytes / sizeof(float4) > starts.n && starts.n > 0) { // overlap_wait's buffer_grown case
+            const int wrc = wait_sets_host(s); // (the set's previous kernel read the buffer that grows)
+            if (wrc != RT_OK) return wrc;
+        }
+        HIP_TRY(starts.reserve(sr.bytes / sizeof(float4)));
+        p.starts = starts.p;
         p.start_rows = sr.rows;
     }
+    if (overlap && shared_written) { // the other set's next launch reads what this stream has just queued
+        HIP_TRY(hipEventRecord(s->shared_ev, st));
+        s->sets[set ^ 1].after_shared = true;
+    }
     const PathParams* pa = nullptr;
-    const int urc = upload_params(s, p, stream, &pa);
+    const int urc = upload_params(s, p, st, &pa);
     if (urc != RT_OK) return urc;
     if (jit) {
         const CameraF* ca = s->camf_d.p;
         void* args[] = {&ca, &pa};
         HIP_TRY(hipModuleLaunchKernel(s->jit.fn, jit_grid, 1, 1, 256, 1, 1,
-                                      (unsigned)path_dyn_lds(s->dev, s->variant), stream, args, nullptr));
+                                      (unsigned)path_dyn_lds(s->dev, s->variant), st, args, nullptr));
     } else {
-        HIP_TRY(launch_path(s->dev, s->camf_d.p, pa, s->variant, grid, stream, s->stats_on));
+        HIP_TRY(launch_path(s->dev, s->camf_d.p, pa, s->variant, grid, st, s->stats_on));
     }
     if (timed) {
-        HIP_TRY(hipEventRecord(s->t_end[tslot], stream));
+        HIP_TRY(hipEventRecord(s->t_end[tslot], st));
         s->launches++;
+    }
+    if (overlap) {
+        HIP_TRY(hipEventRecord(ls.path_done, st));
+        ls.path_recorded = true;
+        HIP_TRY(hipStreamWaitEvent(stream, ls.path_done, 0));
+        s->overlapped++;
+        s->open_set = set;
     }
     return RT_OK;
 }
@@ -830,6 +916,14 @@ int end_op(rt_scene* s, hipStream_t stream)
     HIP_TRY(hipEventRecord(s->done_ev, stream));
     s->last_stream = stream;
     s->any_op = true;
+    if (s->open_set >= 0) { // an overlapped launch's fold: the set's next launch waits for it
+        rt_scene::LaunchSet& ls = s->sets[s->open_set];
+        HIP_TRY(hipEventRecord(ls.fold_done, stream));
+        ls.fold_recorded = true;
+        s->open_set = -1;
+    } else { // a serial operation used set 0's buffers or rewrote shared state: both sets' next launches follow it
+        for (rt_scene::LaunchSet& l : s->sets) l.after_serial = true;
+    }
     return RT_OK;
 }
 
