@@ -62,7 +62,9 @@ extern "C" {
                                    rt_debug_probe_segments_device and rt_debug_shade_probes, and
                                    rt_probe_moments, rt_probe_select_params, rt_render_probe_list_device,
                                    rt_probe_select_device, rt_debug_probe_moments, rt_debug_probe_select and
-                                   rt_debug_probe_error */
+                                   rt_debug_probe_error, and rt_obscurance, rt_obscurance_surfels_device,
+                                   rt_obscurance_select_device, rt_debug_obscurance_fold,
+                                   rt_debug_obscurance_select and rt_debug_obscurance_error */
 
 typedef enum rt_status {
     RT_OK = 0,
@@ -600,8 +602,9 @@ int rt_occluded_rays_device(rt_scene* scene, int32_t mode, const rt_ray* d_rays,
  *   rt_occluded_rays' chunks (2^19 surfels, RTCORE_QUERY_CHUNK, two resident, the copies beside the kernels)
  *   and buffers.
  * Not part of it: RT_QUERY_EXACT (the answer is defined through the fp32 ray; the exact any-hit kernel stays
- *   a per-ray entry), a falloff weight, and a loop that adapts spp to the counts (the standard error of an
- *   occluded share p over N samples is sqrt(p (1 - p) / N): no moments are needed).
+ *   a per-ray entry).  A falloff weight, the bent normal and a loop that adapts spp to the result exist under
+ *   another name: rt_obscurance_surfels_device and rt_obscurance_select_device ("obscurance at surfels"), which
+ *   pay for them with a closest-hit query; these counts remain the cheap path.
  */
 struct rt_surfel; /* (defined under "radiance queries") */
 int rt_occluded_surfels_device(rt_scene* scene, int32_t gather_mode, const struct rt_surfel* d_surfels, int64_t n_records,
@@ -1260,6 +1263,100 @@ int rt_debug_shade_probes_depth(const rt_probe_grid* grid, const rt_probe_depth_
    each; -1 for one that is zero or not finite). */
 int rt_debug_oct_texel_dirs(double* dirs_out);
 int rt_debug_oct_texel(const double* vectors_xyz, int64_t n, int32_t* texels_out);
+
+/*
+ * Obscurance at surfels: occlusion that fades with distance, the bent normal, and the loop that adapts the
+ * sample count.  rt_occluded_surfels counts a point's blocked sample segments with an any-hit query; here each
+ * sample takes the closest hit, so that a hit weighs by how near it is, and the directions are kept: per entry
+ * the sum of the weights (ambient obscurance), of their squares (the variance a stopping rule needs) and of the
+ * unoccluded directions (the bent normal).  Plain counts stay the cheap path: rt_occluded_surfels moves 4 B per
+ * point and stops at the first hit; this entry traces to the closest hit and moves 112 B per sample through
+ * per-scene scratch.
+ *
+ * Everything below is normative and fp64 as "probe grids" is: every operation rounded on its own, nothing
+ * contracted, IEEE division and square root, no library function.
+ *
+ * The ray.  Sample k of entry e is the ray rt_debug_surfel_rays_device reports for sample k of record e in
+ *   gather_mode with (seed, stream_base + e, sample_base + k).  It is keyed by the entry number, not by the list
+ *   position.
+ * The hit.  Its hit is what rt_query_rays_device(RT_QUERY_FAST) answers for that ray on this scene in its
+ *   traversal mode (BRUTE, GROUPED, or BVH with either builder).
+ * The accumulation, per entry, samples ascending k = 0 .. spp - 1, into what the record already holds:
+ *   a ray whose direction is all zeros (an invalid surfel):  samples += 1, nothing else.  Every listed entry
+ *     below n_records therefore gets exactly samples += spp, as rt_occluded_surfels promises;
+ *   else  in = prim_id >= 0 and distance < radius  (a NaN distance is not in);  samples += 1;
+ *     not in:  w = 0;
+ *     in:  hits += 1;  power == 0:  w = 1;  else  x = distance / radius,  b = 1 - x held to [0, 1]
+ *          (b < 0 gives 0, b > 1 gives 1),  w = b multiplied by b another power - 1 times, left to right;
+ *     o += w;   o2 += w * w;   v = 1 - w;   bent[a] += v * d[a] for a = x, y, z,   each product rounded, then each
+ *     sum.  d is the reported ray's direction, a widened fp32.
+ * What is promised:
+ *   1. The device result equals rt_debug_obscurance_fold over the reported rays and the query's answers, bit for
+ *      bit.
+ *   2. An entry's result depends on (seed, stream_base + e, the sample indices, the record, the params, the
+ *      traversal mode) only: not on n, on n_records, on the entry's place in the list, on chunking or on the
+ *      stream.
+ *   3. A call of a + b samples equals a call of a samples followed by one of b samples at sample_base + a into
+ *      the same array, bit for bit.
+ * The list: rt_occluded_surfels_device's rules.  d_index[j], j < n, names the entries; NULL is the identity and
+ *   n must equal n_records.  An entry >= n_records is skipped and nothing is written for it; an entry named
+ *   twice is undefined.  d_surfels and d_acc have n_records elements.
+ * Calls.  `params` is a host pointer.  RT_ERR_ARG, before anything is launched, in rt_occluded_surfels_device's
+ *   order: an unknown gather_mode (checked first), a null scene, n < 0, spp <= 0; then, for n > 0, a null
+ *   surfels, params or accumulator pointer, n_records <= 0 or >= 2^32, a null index with n != n_records, params
+ *   that break a rule of the struct, spp > 2^19 (split the call by sample_base).  RT_ERR_STATE on a BVH2 scene.
+ *   n == 0 returns RT_OK and touches nothing.  Always the generic kernels; no camera is needed; the counters of
+ *   rt_scene_get_stats, an armed rt_debug_ray_log, the rt_kernel_times ring and the scene-specialised kernels
+ *   are left as they were.  Asynchronous on `stream`, ordered like the device-resident renders (the per-scene
+ *   scratch rule of the preamble); chunks of max(1, 2^19 / spp) whole list positions (RTCORE_QUERY_CHUNK
+ *   samples), 64 + 48 B of per-scene scratch per sample.
+ *
+ * The rule (rt_obscurance_select_device).  N = samples, n = (double)N.  active(entry), in this order:
+ *   1. N < min_samples: 1.     2. N >= max_samples: 0.     3. N < 2: 1.
+ *   4. u = o2 - (o * o) / n,  d = u / (n - 1.0);  d a NaN: 0.
+ *   5. v = u > (n * 2^-49) * o2 ? d : 0;  se = sqrt(v / n);  active when se > tol.
+ *   tol is absolute: obscurance lies in [0, 1].  With power == 0 the weights are 0 or 1 and se is the binomial
+ *   standard error sqrt(p (1 - p) / (N - 1)).  The guard of step 5 is "adaptive light probes"': u carries up to
+ *   (3 n + 13) 2^-53 o2 of rounding, n 2^-49 o2 is above that for every n, and a difference not above it is
+ *   rounding, not variance.  An entry whose samples all weigh the same therefore has se == 0 exactly and stops
+ *   at min_samples: open sky, an invalid surfel, the centre of a sphere.
+ *   The list is ascending; *d_count is the number of active entries, also when it exceeds cap.  The pass runs on
+ *   the calling thread's current device, asynchronous on `stream`.  RT_ERR_ARG for a null pointer (d_list may be
+ *   NULL with cap == 0), tol NaN or negative, n_records <= 0 or >= 2^32.  rt_debug_obscurance_select is its host
+ *   twin and returns the count (or a negative status).  rt_debug_obscurance_error reports se and mean = o / n as
+ *   step 5 reads them; both a quiet NaN where N < 2.
+ * Not part of it: a host-buffer entry, a per-entry radius, RT_QUERY_EXACT, fusing the fold into the query
+ *   kernel, and any promised relation to rt_occluded_surfels' counts (one-sided culling and ties at the radius
+ *   make a few samples differ).
+ */
+typedef struct rt_obscurance_params {   /* 24 B */
+    double   radius;      /* finite, > 0: a hit at this distance or beyond does not obscure */
+    int32_t  power;       /* 0 .. 8: 0 counts every hit inside the radius as 1; p >= 1: (1 - d / radius)^p */
+    uint32_t reserved[3]; /* 0 */
+} rt_obscurance_params;
+typedef struct rt_obscurance {          /* 48 B per entry, three 16-byte rows; added to */
+    double   o, o2;       /* sum of the samples' weights, and of their squares                 */
+    double   bent[3];     /* sum of (1 - weight) * direction: the unnormalised bent normal     */
+    uint32_t samples;     /* samples taken (an invalid surfel's count too)                     */
+    uint32_t hits;        /* samples with a hit inside the radius                              */
+} rt_obscurance;
+typedef struct rt_obscurance_select_params {   /* 16 B */
+    double   tol;          /* >= 0, not NaN: converged when se <= tol (absolute: obscurance lies in [0, 1]) */
+    uint32_t min_samples, max_samples;
+} rt_obscurance_select_params;
+int rt_obscurance_surfels_device(rt_scene* scene, int32_t gather_mode, const rt_surfel* d_surfels, int64_t n_records,
+                                 const uint32_t* d_index, int64_t n, const rt_obscurance_params* params, int32_t spp,
+                                 uint64_t seed, uint64_t sample_base, uint64_t stream_base, rt_obscurance* d_acc,
+                                 void* stream);
+/* Its fold on the host, no device: rays and hits are n * spp of each, entry i's at [i * spp, (i + 1) * spp). */
+int rt_debug_obscurance_fold(const rt_obscurance_params* params, const rt_ray* rays, const rt_hit* hits, int64_t n,
+                             int32_t spp, rt_obscurance* acc);
+int rt_obscurance_select_device(const rt_obscurance_select_params* params, const rt_obscurance* d_acc, int64_t n_records,
+                                uint32_t* d_list, uint32_t cap, uint32_t* d_count, void* stream);
+int64_t rt_debug_obscurance_select(const rt_obscurance_select_params* params, const rt_obscurance* acc, int64_t n_records,
+                                   uint32_t* list, uint32_t cap);
+int rt_debug_obscurance_error(const rt_obscurance_select_params* params, const rt_obscurance* acc, int64_t n,
+                              double* se_out, double* mean_out);
 
 /* ---------------------------------------------------- indexed radiance queries --- */
 /*

@@ -203,6 +203,32 @@ def probe_depth_params(d_max: float, sharpness: int = 5, var_floor: float = 1e-4
     return rt_probe_depth_params(float(d_max), float(var_floor), int(sharpness), RT_PROBE_DEPTH_WRAP if wrap else 0)
 
 
+class rt_obscurance_params(C.Structure):
+    """The parameters of obscurance at surfels (rt_obscurance_surfels_device), 24 B."""
+    _fields_ = [("radius", C.c_double), ("power", C.c_int32), ("reserved", C.c_uint32 * 3)]
+
+
+class rt_obscurance(C.Structure):
+    """One entry's obscurance accumulators (OBSCURANCE_DTYPE), 48 B."""
+    _fields_ = [("o", C.c_double), ("o2", C.c_double), ("bent", C.c_double * 3), ("samples", C.c_uint32),
+                ("hits", C.c_uint32)]
+
+
+class rt_obscurance_select_params(C.Structure):
+    """The stopping rule of adaptive obscurance (rt_obscurance_select_device), 16 B."""
+    _fields_ = [("tol", C.c_double), ("min_samples", C.c_uint32), ("max_samples", C.c_uint32)]
+
+
+def obscurance_params(radius: float, power: int = 1) -> rt_obscurance_params:
+    """rt_obscurance_params; the library checks the values."""
+    return rt_obscurance_params(float(radius), int(power))
+
+
+def obscurance_select_params(tol: float, min_samples: int, max_samples: int) -> rt_obscurance_select_params:
+    """rt_obscurance_select_params; the library checks the values."""
+    return rt_obscurance_select_params(float(tol), int(min_samples), int(max_samples))
+
+
 class rt_hit(C.Structure):
     """One answer of rt_query_rays (Hit.cs): 48 B, offsets in include/rtcore.h."""
     _fields_ = [
@@ -291,6 +317,8 @@ BEAM_DTYPE = np.dtype([(f, np.float64, (4,)) for f in
                        ("origin", "direction", "origin_du", "origin_dv", "direction_du", "direction_dv")])
 SURFEL_DTYPE = np.dtype([("position", np.float64, (4,)), ("normal", np.float64, (4,))])
 PROBE_MOMENTS_DTYPE = np.dtype([("m", np.float64, (4, 2))])  # rt_probe_moments
+OBSCURANCE_DTYPE = np.dtype([("o", np.float64), ("o2", np.float64), ("bent", np.float64, (3,)), ("samples", np.uint32),
+                             ("hits", np.uint32)])  # rt_obscurance
 HIT_DTYPE = np.dtype([
     ("prim_id", np.int32), ("inside", np.int32), ("distance", np.float64),
     ("position", np.float32, (3,)), ("normal", np.float32, (3,)), ("reserved", np.int32, (2,)),
@@ -307,7 +335,8 @@ _OPTIONAL = ("rt_query_rays", "rt_query_rays_device", "rt_camera_rays", "rt_sele
              "rt_occluded_surfels", "rt_occluded_surfels_device", "rt_render_probes", "rt_render_probes_device",
              "rt_probe_radiance_device", "rt_shade_probes", "rt_shade_probes_device", "rt_render_probe_list_device",
              "rt_probe_select_device", "rt_render_probe_depth_device", "rt_probe_depth_close_device",
-             "rt_shade_probes_depth_device", "rt_debug_launch_overlap", "rt_debug_kernel_times_raw")
+             "rt_shade_probes_depth_device", "rt_obscurance_surfels_device", "rt_obscurance_select_device",
+             "rt_debug_launch_overlap", "rt_debug_kernel_times_raw")
 
 _lib: Optional[C.CDLL] = None
 
@@ -471,6 +500,17 @@ def load_library(path: str = "") -> C.CDLL:
                                                    C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
         "rt_debug_shade_probes_depth": (C.c_int, [P(rt_probe_grid), P(rt_probe_depth_params), C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+        "rt_obscurance_surfels_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                   P(rt_obscurance_params), C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64,
+                                                   C.c_void_p, C.c_void_p]),
+        "rt_debug_obscurance_fold": (C.c_int, [P(rt_obscurance_params), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                               C.c_void_p]),
+        "rt_obscurance_select_device": (C.c_int, [P(rt_obscurance_select_params), C.c_void_p, C.c_int64, C.c_void_p,
+                                                  C.c_uint32, C.c_void_p, C.c_void_p]),
+        "rt_debug_obscurance_select": (C.c_int64, [P(rt_obscurance_select_params), C.c_void_p, C.c_int64, C.c_void_p,
+                                                   C.c_uint32]),
+        "rt_debug_obscurance_error": (C.c_int, [P(rt_obscurance_select_params), C.c_void_p, C.c_int64, C.c_void_p,
+                                                C.c_void_p]),
         "rt_debug_oct_texel_dirs": (C.c_int, [C.c_void_p]),
         "rt_debug_oct_texel": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
         "rt_render_list": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
@@ -1269,6 +1309,89 @@ def ambient_occlusion(occluded, samples) -> np.ndarray:
         return np.where(ns > 0, 1.0 - occ / ns, np.nan)
 
 
+def obscurance_fold_host(params: rt_obscurance_params, rays, hits, out=None) -> np.ndarray:
+    """rt_debug_obscurance_fold (host code, no GPU): obscurance_surfels' accumulation over per-sample results.
+    rays (n, spp) RAY_DTYPE as surfel_rays reports them, hits (n, spp) HIT_DTYPE as query_rays answers for them.
+    Added into out (n,) OBSCURANCE_DTYPE (a new zeroed array without it); returns it."""
+    lib = load_library()
+    if not hasattr(lib, "rt_debug_obscurance_fold"):
+        raise RtError("this build of the library has no rt_debug_obscurance_fold")
+    r, h = np.ascontiguousarray(rays, RAY_DTYPE), np.ascontiguousarray(hits, HIT_DTYPE)
+    if r.ndim != 2 or r.shape != h.shape:
+        raise ValueError("rays and hits must be (n, spp)")
+    n, spp = r.shape
+    if out is None:
+        out = np.zeros(n, OBSCURANCE_DTYPE)
+    if out.dtype != OBSCURANCE_DTYPE or out.shape != (n,) or not out.flags.c_contiguous:
+        raise ValueError("out must be a contiguous (n,) OBSCURANCE_DTYPE array")
+    _check(lib.rt_debug_obscurance_fold(C.byref(params), r.ctypes.data_as(C.c_void_p), h.ctypes.data_as(C.c_void_p), n, spp,
+                                        out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def obscurance_select_device(params: rt_obscurance_select_params, d_acc, n_records: int, d_list, cap: int, d_count,
+                             stream: int = 0) -> None:
+    """rt_obscurance_select_device: from n_records entries' device accumulators (48 B each) the entry numbers of
+    those that still need samples, ascending, into d_list (at most cap), their number into the uint32 at d_count.
+    Works on the current device; asynchronous on `stream`.  The device arrays as torch tensors or as pointers."""
+    lib = load_library()
+    if not hasattr(lib, "rt_obscurance_select_device"):
+        raise RtError("this build of the library has no rt_obscurance_select_device")
+    _check(lib.rt_obscurance_select_device(C.byref(params), C.c_void_p(_ptr(d_acc)), n_records,
+                                           C.c_void_p(0 if d_list is None else _ptr(d_list)), cap, C.c_void_p(_ptr(d_count)),
+                                           C.c_void_p(stream)))
+
+
+def obscurance_select_host(params: rt_obscurance_select_params, acc, cap: Optional[int] = None) -> Tuple[np.ndarray, int]:
+    """rt_debug_obscurance_select, the host twin of obscurance_select_device (no GPU): acc (n,) OBSCURANCE_DTYPE.
+    Returns (the first min(count, cap) list entries, count)."""
+    lib = load_library()
+    if not hasattr(lib, "rt_debug_obscurance_select"):
+        raise RtError("this build of the library has no rt_debug_obscurance_select")
+    a = np.ascontiguousarray(acc, OBSCURANCE_DTYPE).reshape(-1)
+    cap = a.shape[0] if cap is None else int(cap)
+    out = np.zeros(max(cap, 1), np.uint32)
+    k = lib.rt_debug_obscurance_select(C.byref(params), a.ctypes.data_as(C.c_void_p), a.shape[0], out.ctypes.data_as(C.c_void_p), cap)
+    if k < 0:
+        _check(int(k))
+    return out[:min(int(k), cap)].copy(), int(k)
+
+
+def obscurance_error(params: rt_obscurance_select_params, acc) -> Tuple[np.ndarray, np.ndarray]:
+    """rt_debug_obscurance_error (host code, no GPU): (se, mean) per entry as the stopping rule's last step reads
+    them: the estimated standard error of the mean obscurance, and o / samples; NaN where an entry has fewer than
+    two samples."""
+    lib = load_library()
+    if not hasattr(lib, "rt_debug_obscurance_error"):
+        raise RtError("this build of the library has no rt_debug_obscurance_error")
+    a = np.ascontiguousarray(acc, OBSCURANCE_DTYPE).reshape(-1)
+    se, mean = np.zeros(a.shape[0], np.float64), np.zeros(a.shape[0], np.float64)
+    _check(lib.rt_debug_obscurance_error(C.byref(params), a.ctypes.data_as(C.c_void_p), a.shape[0], se.ctypes.data_as(C.c_void_p),
+                                         mean.ctypes.data_as(C.c_void_p)))
+    return se, mean
+
+
+def ambient_access(acc) -> np.ndarray:
+    """1 - o / samples of obscurance accumulators (OBSCURANCE_DTYPE): the share of a point's surroundings that is
+    open, hits weighed by their falloff; 1 where an entry has no sample."""
+    a = np.asarray(acc)
+    o, ns = a["o"].astype(np.float64), a["samples"].astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(ns > 0, 1.0 - o / ns, 1.0)
+
+
+def bent_normals(acc, normals) -> np.ndarray:
+    """The bent normal of obscurance accumulators: acc["bent"] normalised, the mean unoccluded direction; the
+    surfel's own unit normal (normals (n, 3) or wider) where bent is zero or not finite."""
+    b = np.asarray(acc)["bent"].astype(np.float64)
+    nr = np.asarray(normals, np.float64)[..., :3]
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        own = nr / np.linalg.norm(nr, axis=-1, keepdims=True)
+        length = np.linalg.norm(b, axis=-1, keepdims=True)
+        ok = np.isfinite(b).all(axis=-1, keepdims=True) & np.isfinite(length) & (length > 0)
+        return np.where(ok, b / np.where(ok, length, 1.0), own)
+
+
 def _surfel_t_max(t_max, n: int) -> Optional[np.ndarray]:
     """occluded_surfels' t_max (None, a scalar or an array of n) as n contiguous doubles, or None."""
     if t_max is None:
@@ -1971,6 +2094,111 @@ class GpuRaytracer:
                                                    C.c_void_p(0 if d_t_max is None else _ptr(d_t_max)), spp, seed, sample_base,
                                                    stream_base, C.c_void_p(_ptr(d_occluded)), C.c_void_p(_ptr(d_samples)),
                                                    C.c_void_p(stream)))
+
+    def obscurance_surfels_device(self, mode: int, d_surfels, n_records: int, d_index, n: int, params: rt_obscurance_params,
+                                  spp: int, seed: int, sample_base: int, stream_base: int, d_acc, stream: int = 0) -> None:
+        """rt_obscurance_surfels_device: asynchronous falloff obscurance for the n entries listed (uint32 entry
+        numbers at d_index, or None: every entry, n == n_records) of the n_records rt_surfel resident at d_surfels,
+        added into n_records rt_obscurance (48 B each) at d_acc on `stream`.  The device arrays as torch tensors or
+        as pointers (integers)."""
+        if not hasattr(self.lib, "rt_obscurance_surfels_device"):
+            raise RtError("this build of the library has no rt_obscurance_surfels_device")
+        _check(self.lib.rt_obscurance_surfels_device(self.handle, mode, C.c_void_p(_ptr(d_surfels)), n_records,
+                                                     C.c_void_p(0 if d_index is None else _ptr(d_index)), n, C.byref(params),
+                                                     spp, seed, sample_base, stream_base, C.c_void_p(_ptr(d_acc)),
+                                                     C.c_void_p(stream)))
+
+    def obscurance_select_device(self, params: rt_obscurance_select_params, d_acc, n_records: int, d_list, cap: int, d_count,
+                                 stream: int = 0) -> None:
+        """rt_obscurance_select_device on this scene's device (the module's obscurance_select_device)."""
+        import torch
+
+        with torch.cuda.device(self.device):
+            obscurance_select_device(params, d_acc, n_records, d_list, cap, d_count, stream)
+
+    def obscurance_surfels(self, positions, normals, spp: int, seed: int, radius: float, power: int = 1,
+                           mode: int = RT_GATHER_COSINE, index=None, sample_base: int = 0, stream_base: int = 0,
+                           out=None) -> np.ndarray:
+        """Obscurance at surface points (rtcore.h, "obscurance at surfels"): spp samples per point, the rays
+        surfel_rays reports, each weighed by its closest hit: 0 beyond `radius` or on a miss, else
+        (1 - distance / radius)^power (power 0: 1).  Returns an (n,) OBSCURANCE_DTYPE array: o and o2 the sums of
+        the weights and of their squares, bent the sum of (1 - weight) * direction, samples and hits; a new zeroed
+        array, or the caller's `out`, which the call adds into (sample_base continues).  index: the entries to
+        sample (None: all); the others are left as they are.  ambient_access and bent_normals read the result."""
+        import torch
+
+        surfels = _pack_surfels(positions, normals)
+        n = surfels.shape[0]
+        idx = None
+        if index is not None:
+            idx = np.asarray(index).reshape(-1)
+            if idx.size and (idx.min() < 0 or idx.max() >= 1 << 32):
+                raise ValueError("entry numbers must lie in [0, 2^32)")
+            idx = np.ascontiguousarray(idx, np.uint32)
+        if out is None:
+            out = np.zeros(n, OBSCURANCE_DTYPE)
+        if out.dtype != OBSCURANCE_DTYPE or out.shape != (n,) or not out.flags.c_contiguous:
+            raise ValueError("out must be a contiguous (n,) OBSCURANCE_DTYPE array")
+        m = n if idx is None else idx.size
+        if n == 0 or m == 0:
+            return out
+        params = obscurance_params(radius, power)
+        with torch.cuda.device(self.device):
+            dev = torch.device("cuda", self.device)
+            d_surfels = torch.from_numpy(surfels.view(np.uint8).copy()).to(dev)
+            d_acc = torch.from_numpy(out.view(np.uint8).copy()).to(dev)
+            d_idx = torch.from_numpy(idx.view(np.int32).copy()).to(dev) if idx is not None else None
+            torch.cuda.synchronize()
+            self.obscurance_surfels_device(mode, d_surfels, n, d_idx, m, params, spp, seed, sample_base, stream_base, d_acc)
+            torch.cuda.synchronize()
+            out.view(np.uint8)[:] = d_acc.cpu().numpy()
+        return out
+
+    def obscurance_adaptive(self, positions, normals, tol: float, min_spp: int, max_spp: int, batch_spp: int, seed: int = 0,
+                            radius: float = 1.0, power: int = 1, mode: int = RT_GATHER_COSINE, stream_base: int = 0,
+                            sample_base: int = 0):
+        """bake_probes_adaptive's loop for obscurance: sample until the estimated standard error of every point's
+        mean obscurance is at most tol (rtcore.h, "obscurance at surfels", the rule), with the surfels, the
+        accumulators and the list held on this scene's device.  Each iteration: rt_obscurance_select_device builds
+        the ascending list of entries that still need samples; the list's length is read (one 4-byte copy, the
+        loop's only synchronisation); rt_obscurance_surfels_device adds batch_spp samples of the listed entries at
+        sample_base + iteration * batch_spp.  The loop stops when the list is empty.  min_spp and max_spp are
+        rounded up to multiples of batch_spp.
+        Returns a dict: device tensors acc (n, 48) uint8 (view the host copy as OBSCURANCE_DTYPE) and surfels, and
+        counts, lists and params."""
+        import torch
+
+        if batch_spp <= 0 or min_spp <= 0 or max_spp < min_spp:
+            raise ValueError("need batch_spp > 0 and 0 < min_spp <= max_spp")
+        surfels = _pack_surfels(positions, normals)
+        n = surfels.shape[0]
+        if n == 0:
+            raise ValueError("no surfels")
+        up = lambda v: -(-int(v) // batch_spp) * batch_spp  # noqa: E731
+        par = obscurance_select_params(tol, up(min_spp), up(max_spp))
+        fall = obscurance_params(radius, power)
+        dev = torch.device("cuda", self.device)
+        with torch.cuda.device(dev):
+            d_surfels = torch.from_numpy(surfels.view(np.uint8).copy()).to(dev)
+            d_acc = torch.zeros((n, OBSCURANCE_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+            d_count = torch.zeros(1, dtype=torch.int32, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            counts, lists = [], []
+            while True:
+                lst = torch.empty(n if not counts else counts[-1], dtype=torch.int32, device=dev)
+                obscurance_select_device(par, d_acc, n, lst, lst.numel(), d_count, stream=stream)
+                m = int(d_count.item()) & 0xFFFFFFFF
+                if m == 0:
+                    break
+                if m > lst.numel():
+                    raise RtError("obscurance_adaptive: the list of active entries grew")
+                lst = lst[:m]
+                self.obscurance_surfels_device(mode, d_surfels, n, lst, m, fall, batch_spp, seed,
+                                               int(sample_base) + len(counts) * batch_spp, stream_base, d_acc, stream)
+                counts.append(m)
+                lists.append(lst)
+            torch.cuda.synchronize(dev)
+        return {"acc": d_acc, "surfels": d_surfels, "counts": counts, "lists": lists, "params": par}
 
     def render_list(self, kind: int, records, index=None, spp: int = 1, seed: int = 0, mode: int = 0, sample_base: int = 0,
                     stream_base: int = 0, out=None, moments: bool = False):

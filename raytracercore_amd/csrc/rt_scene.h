@@ -1,6 +1,6 @@
 // rt_scene.h -- the scene object behind the C ABI and what the API's translation units share
 // (rtcore_api.hip, scene_upload.hip, api_frame.hip, api_debug.hip, api_query.hip, api_select.hip, api_render_rays.hip,
-// api_render_pixels.hip, api_render_probes.hip, api_shade_probes.hip, api_probe_depth.hip, chunk_pipeline.hip, api_adaptive.hip, api_denoise.hip, api_reproject.hip).
+// api_render_pixels.hip, api_render_probes.hip, api_shade_probes.hip, api_probe_depth.hip, api_obscurance.hip, chunk_pipeline.hip, api_adaptive.hip, api_denoise.hip, api_reproject.hip).
 #pragma once
 #include <algorithm>
 #include <array>
@@ -203,8 +203,8 @@ struct rt_scene {
     DevBuf<double> probe_seg_t_max;
     DevBuf<unsigned char> probe_seg_occluded;
     DevBuf<double> shade_L, shade_out;
-    // rt_render_probe_depth_device: one chunk's sample rays and their closest hits, made and read on the
-    // caller's stream
+    // rt_render_probe_depth_device and rt_obscurance_surfels_device: one chunk's sample rays and their closest
+    // hits, made and read on the caller's stream
     DevBuf<rt_ray> probe_depth_rays;
     DevBuf<rt_hit> probe_depth_hits;
     DevBuf<rt_surfel> shade_points;
@@ -460,7 +460,8 @@ int fill_query(rt_scene* s, int kernel, int blocks_per_cu, const rt_ray* d_rays,
 int launch_segments(rt_scene* s, int32_t mode, const rt_ray* d_rays, const double* d_t_max, unsigned n, unsigned char* d_out,
                     hipStream_t st);
 // rt_query_rays' launch over n <= kQueryLaunchMax rays on `st`, after the stream ordering is settled;
-// rt_render_probe_depth_device (api_probe_depth.hip) runs it over the sample rays it makes.
+// rt_render_probe_depth_device (api_probe_depth.hip) and rt_obscurance_surfels_device (api_obscurance.hip) run it
+// over the sample rays they make.
 int launch_rays(rt_scene* s, int32_t mode, const rt_ray* d_rays, unsigned n, rt_hit* d_hits, hipStream_t st);
 // api_render_surfels.hip: rt_debug_surfel_rays_device's launch for total = n x spp samples on `st`.
 int launch_surfel_rays(int32_t mode, const rt_surfel* d_surfels, unsigned long long total, unsigned spp, uint64_t seed,

@@ -3,6 +3,7 @@ cosine-distributed directions about the hit's normal along which nothing lies wi
 
 usage: python tools/bake_ao.py SCENE [--width W] [--rays K] [--radius R] [--seed S]
                                [--traversal MODE] [--device] [--out PREFIX]
+                               [--falloff P] [--bent] [--tol T --min A --max B --batch C]
 
 SCENE is a scene file (or the name of one shipped in tests/golden/scenes).  The steps: camera_rays (the
 rays rt_primary_ids traces), query_rays (RT_QUERY_FAST) for the hits, K directions per hit from a
@@ -13,6 +14,13 @@ triangle), get AO 1.  The image keeps the scene's aspect ratio at width W.  Writ
 float32 [H, W]) and PREFIX.ppm (binary P6, grey).
 --device: the K directions are drawn on the device instead (bake_ao_device): one surfel per hit through
 occluded_surfels (rt_occluded_surfels) in RT_GATHER_COSINE mode, 72 B up and 4 B down per hit for any K.
+--falloff P: falloff obscurance instead of a count (bake_obscurance): a hit at distance d < R weighs
+(1 - d / R)^P (P = 0: 1), through obscurance_surfels (rt_obscurance_surfels_device, a closest-hit query); the
+image is 1 - the mean weight.  --bent also writes the bent normal, the mean unoccluded direction, as
+PREFIX_bent.npy (float32 [H, W, 3]) and PREFIX_bent.ppm (0.5 + 0.5 n; a primary miss is black).  --tol T with
+--min A --max B --batch C samples each pixel until the standard error of its obscurance is at most T
+(obscurance_adaptive), between A and B samples in steps of C, and also writes the samples-per-pixel map
+PREFIX_spp.npy; --bent and --tol imply --falloff 1 unless it is given.  Without these options nothing changes.
 """
 from __future__ import annotations
 
@@ -106,6 +114,40 @@ def bake_ao_device(gpu, k: int, radius: float, seed: int = 0) -> np.ndarray:
     return np.ascontiguousarray(ao.T)
 
 
+def bake_obscurance(gpu, k: int, radius: float, seed: int = 0, power: int = 1, adaptive=None):
+    """bake_ao_device with falloff obscurance (--falloff): the same surfels through obscurance_surfels, or with
+    adaptive = (tol, min, max, batch) through obscurance_adaptive.  Returns (ao float32 [H, W], bent float32
+    [H, W, 3] with zeros at a primary miss, spp int32 [H, W])."""
+    import raytracercore_amd as rc
+
+    hits = gpu.query_rays(gpu.camera_rays())  # [x, y]
+    mask, pos, nrm = ao_surfels(hits)
+    ao = np.ones(hits.shape, np.float32)
+    bent = np.zeros(hits.shape + (3,), np.float32)
+    spp = np.zeros(hits.shape, np.int32)
+    if len(pos):
+        if adaptive is None:
+            acc = gpu.obscurance_surfels(pos, nrm, k, seed, float(radius), power, rc.RT_GATHER_COSINE)
+        else:
+            tol, lo, hi, batch = adaptive
+            out = gpu.obscurance_adaptive(pos, nrm, tol, lo, hi, batch, seed=seed, radius=float(radius), power=power,
+                                          mode=rc.RT_GATHER_COSINE)
+            acc = out["acc"].cpu().numpy().reshape(-1).view(rc.OBSCURANCE_DTYPE)
+        ao[mask] = rc.ambient_access(acc).astype(np.float32)
+        bent[mask] = rc.bent_normals(acc, nrm).astype(np.float32)
+        spp[mask] = acc["samples"].astype(np.int32)
+    return np.ascontiguousarray(ao.T), np.ascontiguousarray(bent.transpose(1, 0, 2)), np.ascontiguousarray(spp.T)
+
+
+def write_normals_ppm(path: str, normals: np.ndarray) -> None:
+    """Unit vectors [H, W, 3] as a binary PPM of 0.5 + 0.5 n; a zero vector is black."""
+    lit = np.any(normals != 0, axis=-1, keepdims=True)
+    g = np.where(lit, np.clip(np.rint((0.5 + 0.5 * normals) * 255.0), 0, 255), 0).astype(np.uint8)
+    with open(path, "wb") as f:
+        f.write(f"P6\n{normals.shape[1]} {normals.shape[0]}\n255\n".encode())
+        f.write(np.ascontiguousarray(g).tobytes())
+
+
 def write_ppm(path: str, ao: np.ndarray) -> None:
     """AO [H, W] in [0, 1] as a grey binary PPM."""
     g = np.clip(np.rint(ao * 255.0), 0, 255).astype(np.uint8)
@@ -124,9 +166,20 @@ def main(argv=None) -> int:
     ap.add_argument("--traversal", default="AUTO", choices=["AUTO", "BRUTE", "GROUPED", "BVH"])
     ap.add_argument("--device", action="store_true", help="draw the directions on the device (rt_occluded_surfels)")
     ap.add_argument("--out", default="ao")
+    ap.add_argument("--falloff", type=int, default=None, metavar="P", help="falloff obscurance (1 - d / radius)^P, 0 .. 8")
+    ap.add_argument("--bent", action="store_true", help="also write the bent-normal image")
+    ap.add_argument("--tol", type=float, default=None, help="adaptive: stop a pixel at this standard error")
+    ap.add_argument("--min", type=int, default=16, dest="min_spp", help="adaptive: fewest samples of a pixel")
+    ap.add_argument("--max", type=int, default=256, dest="max_spp", help="adaptive: most samples of a pixel")
+    ap.add_argument("--batch", type=int, default=16, help="adaptive: samples added per iteration")
     a = ap.parse_args(argv)
     if a.width < 1 or a.rays < 1 or not a.radius > 0:
         ap.error("--width and --rays must be >= 1, --radius > 0")
+    falloff = a.falloff if a.falloff is not None else 1 if (a.bent or a.tol is not None) else None
+    if falloff is not None and not 0 <= falloff <= 8:
+        ap.error("--falloff must lie in 0 .. 8")
+    if a.tol is not None and (not a.tol >= 0 or a.batch < 1 or a.min_spp < 1 or a.max_spp < a.min_spp):
+        ap.error("--tol must be >= 0, --batch and --min >= 1, --max >= --min")
 
     import raytracercore_amd as rc
 
@@ -135,11 +188,27 @@ def main(argv=None) -> int:
     height = max(1, round(a.width * scene.params.height / max(1, scene.params.width)))
     gpu = rc.GpuRaytracer(scene, 0, size=(a.width, height), traversal=getattr(rc, "RT_TRAVERSAL_" + a.traversal))
     try:
-        ao = (bake_ao_device if a.device else bake_ao)(gpu, a.rays, a.radius, a.seed)
+        if falloff is not None:
+            adaptive = None if a.tol is None else (a.tol, a.min_spp, a.max_spp, a.batch)
+            ao, bent, spp = bake_obscurance(gpu, a.rays, a.radius, a.seed, falloff, adaptive)
+        else:
+            ao = (bake_ao_device if a.device else bake_ao)(gpu, a.rays, a.radius, a.seed)
     finally:
         gpu.close()
     np.save(a.out + ".npy", ao)
     write_ppm(a.out + ".ppm", ao)
+    if falloff is not None:
+        if a.bent:
+            np.save(a.out + "_bent.npy", bent)
+            write_normals_ppm(a.out + "_bent.ppm", bent)
+        if a.tol is not None:
+            np.save(a.out + "_spp.npy", spp)
+        lit = spp > 0
+        print(f"{os.path.basename(path)} obscurance {a.width}x{height}: falloff {falloff}, radius {a.radius}, "
+              f"{int(spp.sum())} samples over {int(lit.sum())} hits (mean {float(spp[lit].mean()) if lit.any() else 0.0:.1f} per hit), "
+              f"mean {float(ao.mean()):.4f} -> {a.out}.npy, {a.out}.ppm"
+              + (f", {a.out}_bent.npy, {a.out}_bent.ppm" if a.bent else "") + (f", {a.out}_spp.npy" if a.tol is not None else ""))
+        return 0
     print(f"{os.path.basename(path)} AO {a.width}x{height}: {a.rays} rays of radius {a.radius} per hit, "
           f"mean {float(ao.mean()):.4f}, {int((ao < 1).sum())} pixels occluded -> {a.out}.npy, {a.out}.ppm")
     return 0
