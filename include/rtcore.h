@@ -64,7 +64,13 @@ extern "C" {
                                    rt_probe_select_device, rt_debug_probe_moments, rt_debug_probe_select and
                                    rt_debug_probe_error, and rt_obscurance, rt_obscurance_surfels_device,
                                    rt_obscurance_select_device, rt_debug_obscurance_fold,
-                                   rt_debug_obscurance_select and rt_debug_obscurance_error */
+                                   rt_debug_obscurance_select and rt_debug_obscurance_error, and
+                                   rt_probe_relocate_params, rt_probe_relocation, rt_probe_positions_device,
+                                   rt_debug_probe_positions, rt_relocate_probes_device, rt_debug_probe_relocate,
+                                   rt_shade_probes_placed, rt_shade_probes_placed_device,
+                                   rt_debug_probe_segments_placed, rt_debug_probe_segments_placed_device,
+                                   rt_debug_shade_probes_placed, rt_shade_probes_depth_placed_device and
+                                   rt_debug_shade_probes_depth_placed */
 
 typedef enum rt_status {
     RT_OK = 0,
@@ -1232,8 +1238,8 @@ int rt_debug_shade_probes(const rt_probe_grid* grid, const double* L, const rt_s
  * n < 0, then for n > 0 a null L, D, points or irradiance pointer; n == 0 returns RT_OK and touches nothing.
  * The close: RT_ERR_ARG for n < 0, n >= 2^25 or a null pointer with n > 0.  Outputs are written, not added to;
  * d_weight may be NULL.
- * Not part of it: a host-buffer bake; bilinear lookup across the octahedral seams; probe relocation (the
- * backface share only enables it); fusing the fold into rt_render_probes' launch.
+ * Not part of it: a host-buffer bake; bilinear lookup across the octahedral seams; fusing the fold into
+ * rt_render_probes' launch.  (Relocation, which the backface share drives, is "probe relocation" below.)
  */
 #define RT_PROBE_DEPTH_WRAP 1u
 typedef struct rt_probe_depth_params {   /* 32 B */
@@ -1263,6 +1269,143 @@ int rt_debug_shade_probes_depth(const rt_probe_grid* grid, const rt_probe_depth_
    each; -1 for one that is zero or not finite). */
 int rt_debug_oct_texel_dirs(double* dirs_out);
 int rt_debug_oct_texel(const double* vectors_xyz, int64_t n, int32_t* texels_out);
+
+/*
+ * Probe relocation: per-probe offsets that move a grid's probes off nearby geometry, a device pass that
+ * derives them from the hit distances of a probe's own sample directions and classifies the probe (DDGI's
+ * relocation and classification), and shading entries that honour the offsets and states.  A grid alone can
+ * place a probe only at origin + i * step; a probe next to a wall sees it under a wide range of distances
+ * inside one texel of its depth map, and the Chebyshev test then hides little ("probe depth maps").
+ *
+ * Everything below is normative and fp64 as "probe grids" is: every operation rounded on its own, nothing
+ * contracted, IEEE division and square root, no library function.  A comparison with a NaN is false.
+ *
+ * Placement.  Offsets: n_probes x 3 doubles in world units, indexed like L; a NULL pointer means all zero.
+ * State: n_probes uint32, bits RT_PROBE_INSIDE and RT_PROBE_IDLE; a NULL pointer means all 0.  The position of
+ * probe (i_x, i_y, i_z) is  q_a = (origin_a + (double)i_a * step_a) + offset_a:  the grid term is "probe
+ * grids"', the offset is added last (also a zero offset, for a NULL pointer +0.0).  An offset is valid when its
+ * three components are finite; a probe with a non-finite offset is ABSENT everywhere below.
+ * rt_probe_positions_device writes one rt_surfel per grid probe, in index order: position (q, 1), normal
+ * (0, 0, 1, 0); for a non-finite offset the position is four quiet NaNs, an invalid surfel for every entry.
+ * This is the array rt_render_probes_device, rt_render_probe_list_device and rt_render_probe_depth_device take,
+ * so the three bakes work at relocated positions unchanged.
+ *
+ * One relocation step (rt_relocate_probes_device).  Sample k of probe i is sample k of surfel i of
+ * rt_probe_positions_device's array in RT_GATHER_SPHERE mode, keyed (seed, stream_base + i, sample_base + k):
+ * the ray rt_debug_surfel_rays_device reports; its hit is rt_query_rays_device(RT_QUERY_FAST)'s answer on this
+ * scene in its traversal mode: the directions and the query of the depth bake.  d is rt_hit.distance.
+ * The fold, per probe, over k = 0 .. spp - 1, from (d_near, k_near) = (+inf, -1), (d_back, k_back) = (+inf, -1),
+ * (d_far, k_far) = (-inf, -1) and all counts 0:
+ *   a direction of all zeros:      skipped += 1;
+ *   a miss (prim_id < 0):          misses += 1;
+ *   a hit with inside != 0:        back += 1;   d < d_back:  (d_back, k_back) = (d, k);
+ *   any other hit:                 front += 1;  d < d_near:  (d_near, k_near) = (d, k);
+ *                                               d > d_far:   (d_far, k_far) = (d, k).
+ * Ties therefore keep the lowest k, and a NaN distance is counted and never chosen.
+ * The rule.  o is the offset read, D_k the reported direction of sample k (fp32 values in doubles; (0, 0, 0)
+ * for k = -1), hits = back + front, s the grid's step.
+ *   (a) hits > 0 and (double)back > back_share * (double)hits:
+ *         m = d_back + min_front * 0.5,   c_a = o_a + D_kback,a * m;   state bit RT_PROBE_INSIDE.
+ *   (b) else front > 0 and d_near < min_front:
+ *         p = (Dn_x * Df_x + Dn_y * Df_y) + Dn_z * Df_z  with Dn = D_knear, Df = D_kfar;
+ *         p > 0:  c = o  (moving toward the far surface would also approach the near one);
+ *         else    h = d_far * 0.5,  t = h < min_front ? h : min_front,  c_a = o_a + Df_a * t  (the probe never
+ *                 passes the far surface).
+ *   (c) else (nothing near: move home):
+ *         len = sqrt((o_x * o_x + o_y * o_y) + o_z * o_z);   len not > 0:  c = o;
+ *         else  room = (front > 0 ? d_near : +inf) - min_front,  m = room < len ? room : len;
+ *               m == len:  c = (+0.0, +0.0, +0.0);   else  c_a = o_a - (o_a / len) * m.
+ *   Accept:  e_a = c_a / s_a.  c becomes the offset when its three components are finite and
+ *         (e_x * e_x + e_y * e_y) + e_z * e_z < max_offset * max_offset;  otherwise the offset stays o.
+ *   State bit RT_PROBE_IDLE:  front == 0, or d_near > sqrt((s_x * s_x + s_y * s_y) + s_z * s_z): no front face
+ *         within the cell's diagonal, so no surface is there to shade from this probe.  It is information for the
+ *         baker, who feeds the other probes to rt_render_probe_list_device; shading does not act on it.
+ *   A probe whose samples were all skipped (an invalid position):  the offset stays, state = RT_PROBE_INSIDE |
+ *         RT_PROBE_IDLE, moved = 0.
+ * rt_probe_relocation, per probe: the state, the counts, the three winners, and moved = 1 when the bits of the
+ * offset the rule gives differ from those of o.  With RT_PROBE_RELOCATE_CLASSIFY_ONLY the record is the same
+ * (moved reports what a step would do) and the offsets are read, never written.
+ * What is promised:
+ *   1. The device result (offsets and records) equals rt_debug_probe_relocate over the reported rays and the
+ *      query's answers, bit for bit.  (The device folds a probe's samples across the lanes of a wave and reduces
+ *      (d, k) pairs in the lexicographic order "smaller d, then smaller k" (far: larger d, then smaller k), which
+ *      is what the sequential fold with strict comparisons selects.)
+ *   2. A probe's result depends on its grid position, its offset, the params, (seed, stream_base + i, the sample
+ *      indices) and the traversal mode only: not on chunking or on the stream.
+ *   3. With RT_PROBE_RELOCATE_CLASSIFY_ONLY, d_offsets is bit-identical afterwards.
+ * Calls.  grid and params are host pointers; the grid's flags and bias play no part.  RT_ERR_ARG, before
+ * anything is launched, for a null scene, grid or params, a grid or params that break a rule of their struct,
+ * spp <= 0, spp > 2^19 (take several steps), a null d_offsets or d_info.  RT_ERR_STATE on a BVH2 scene.  Always
+ * the generic kernels; no camera is needed; the counters of rt_scene_get_stats, an armed rt_debug_ray_log,
+ * rt_kernel_times and the scene-specialised kernels are left as they were.  Asynchronous on `stream`, ordered
+ * like the device-resident renders; chunks of max(1, 2^19 / spp) whole probes (RTCORE_QUERY_CHUNK samples),
+ * 64 + 48 B of per-scene scratch per sample (the depth bake's) and 64 B per probe of a chunk.
+ *
+ * Shading that honours the placement.  The _placed entries take offsets and state after the grid and are
+ * otherwise their unplaced entries, word for word: cell, corners and t_c stay the grid's (the trilinear weights
+ * belong to the lattice, as in DDGI); only q changes, so the segments' ends, and the depth shading's v, r and
+ * texel, change with it.  A probe with state & RT_PROBE_INSIDE, or with a non-finite offset, is ABSENT: it is
+ * not blended, and its segment is the empty one.
+ * What is promised:
+ *   1. Device equals twin, bit for bit, as for the unplaced entries.
+ *   2. With NULL offsets and NULL state, and with all-zero arrays, every placed entry's result equals its
+ *      unplaced entry's, bit for bit.  (x + 0.0 is exact but -0.0 + 0.0 is +0.0: only the bits of q can differ
+ *      there, and only in the sign of a zero.  The grid term is in fact never -0.0: (double)i_a * step_a is +0.0
+ *      or above 0, and a sum is -0.0 only when both terms are; so the results agree in every bit.)
+ * Calls.  As the unplaced entries; offsets and state are device pointers in the _device entries and host
+ * pointers in the others, each may be NULL.  rt_shade_probes_placed uploads them once, with L.
+ * Not part of it: moving the cell or the trilinear weights with the probes; acting on RT_PROBE_IDLE in the
+ * shading; a relocation over host buffers.
+ */
+#define RT_PROBE_INSIDE 1u                 /* state: the probe sits inside geometry; absent in the shading */
+#define RT_PROBE_IDLE 2u                   /* state: no front face within the cell's diagonal              */
+#define RT_PROBE_RELOCATE_CLASSIFY_ONLY 1u /* params.flags: offsets are read, never written                */
+typedef struct rt_probe_relocate_params {   /* 32 B */
+    double   back_share;  /* finite, in [0, 1): the share of back-face hits above which a probe is inside (DDGI: 0.25) */
+    double   min_front;   /* finite, > 0, world units: the clearance a probe keeps from a front face                  */
+    double   max_offset;  /* finite, in (0, 0.5): the offset's bound, in steps, an ellipsoid (DDGI: 0.45)             */
+    uint32_t flags;       /* RT_PROBE_RELOCATE_CLASSIFY_ONLY or 0 */
+    uint32_t reserved;    /* 0 */
+} rt_probe_relocate_params;
+typedef struct rt_probe_relocation {   /* 64 B */
+    uint32_t state, moved, front, back, misses, skipped;
+    int32_t  k_near, k_back, k_far, reserved;   /* -1: none; reserved 0 */
+    double   d_near, d_back, d_far;             /* +inf, +inf, -inf: none */
+} rt_probe_relocation;
+/* On the calling thread's current device (as rt_probe_radiance_device), asynchronous on `stream`; d_offsets may
+   be NULL.  RT_ERR_ARG for a grid that breaks a rule of its struct or a null output. */
+int rt_probe_positions_device(const rt_probe_grid* grid, const double* d_offsets, rt_surfel* d_probes_out, void* stream);
+/* Its host twin: host only, no device. */
+int rt_debug_probe_positions(const rt_probe_grid* grid, const double* offsets, rt_surfel* probes_out);
+/* One step over every probe of the grid: d_offsets (n_probes x 3 doubles) is read and written, d_info (n_probes
+   records) is written; neither may be NULL. */
+int rt_relocate_probes_device(rt_scene* scene, const rt_probe_grid* grid, const rt_probe_relocate_params* params,
+                              int32_t spp, uint64_t seed, uint64_t sample_base, uint64_t stream_base,
+                              double* d_offsets, rt_probe_relocation* d_info, void* stream);
+/* The fold and the rule on the host, no device: rays and hits are n_probes * spp of each, probe i's at
+   [i * spp, (i + 1) * spp); offsets in/out, info written.  RT_ERR_ARG as above, and for a null rays or hits. */
+int rt_debug_probe_relocate(const rt_probe_grid* grid, const rt_probe_relocate_params* params, const rt_ray* rays,
+                            const rt_hit* hits, int32_t spp, double* offsets, rt_probe_relocation* info);
+int rt_shade_probes_placed_device(rt_scene* scene, const rt_probe_grid* grid, const double* d_offsets,
+                                  const uint32_t* d_state, const double* d_L, const rt_surfel* d_points, int64_t n,
+                                  rt_color* d_irradiance, double* d_weight, void* stream);
+int rt_shade_probes_placed(rt_scene* scene, const rt_probe_grid* grid, const double* offsets, const uint32_t* state,
+                           const double* L, const rt_surfel* points, int64_t n, rt_color* irradiance, double* weight);
+int rt_debug_probe_segments_placed_device(const rt_probe_grid* grid, const double* d_offsets, const uint32_t* d_state,
+                                          const rt_surfel* d_points, int64_t n, rt_ray* d_rays_out, double* d_t_max_out,
+                                          void* stream);
+int rt_debug_probe_segments_placed(const rt_probe_grid* grid, const double* offsets, const uint32_t* state,
+                                   const rt_surfel* points, int64_t n, rt_ray* rays_out, double* t_max_out);
+int rt_debug_shade_probes_placed(const rt_probe_grid* grid, const double* offsets, const uint32_t* state, const double* L,
+                                 const rt_surfel* points, int64_t n, const uint8_t* occluded, rt_color* irradiance,
+                                 double* weight);
+int rt_shade_probes_depth_placed_device(const rt_probe_grid* grid, const double* d_offsets, const uint32_t* d_state,
+                                        const rt_probe_depth_params* params, const double* d_L, const double* d_D,
+                                        const rt_surfel* d_points, int64_t n, rt_color* d_irradiance, double* d_weight,
+                                        void* stream);
+int rt_debug_shade_probes_depth_placed(const rt_probe_grid* grid, const double* offsets, const uint32_t* state,
+                                       const rt_probe_depth_params* params, const double* L, const double* D,
+                                       const rt_surfel* points, int64_t n, rt_color* irradiance, double* weight);
 
 /*
  * Obscurance at surfels: occlusion that fades with distance, the bent normal, and the loop that adapts the

@@ -203,6 +203,31 @@ def probe_depth_params(d_max: float, sharpness: int = 5, var_floor: float = 1e-4
     return rt_probe_depth_params(float(d_max), float(var_floor), int(sharpness), RT_PROBE_DEPTH_WRAP if wrap else 0)
 
 
+RT_PROBE_INSIDE = 1  # probe state: inside geometry; absent in the placed shading
+RT_PROBE_IDLE = 2  # probe state: no front face within the cell's diagonal
+RT_PROBE_RELOCATE_CLASSIFY_ONLY = 1  # rt_probe_relocate_params.flags: offsets are read, never written
+
+
+class rt_probe_relocate_params(C.Structure):
+    """The parameters of probe relocation (rt_relocate_probes_device), 32 B."""
+    _fields_ = [("back_share", C.c_double), ("min_front", C.c_double), ("max_offset", C.c_double), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+def probe_relocate_params(min_front: float, back_share: float = 0.25, max_offset: float = 0.45,
+                          classify_only: bool = False) -> rt_probe_relocate_params:
+    """rt_probe_relocate_params (DDGI's defaults for the two shares); the library checks the values."""
+    return rt_probe_relocate_params(float(back_share), float(min_front), float(max_offset),
+                                    RT_PROBE_RELOCATE_CLASSIFY_ONLY if classify_only else 0, 0)
+
+
+# rt_probe_relocation, 64 B per probe
+RELOCATION_DTYPE = np.dtype([("state", "<u4"), ("moved", "<u4"), ("front", "<u4"), ("back", "<u4"), ("misses", "<u4"),
+                             ("skipped", "<u4"), ("k_near", "<i4"), ("k_back", "<i4"), ("k_far", "<i4"), ("reserved", "<i4"),
+                             ("d_near", "<f8"), ("d_back", "<f8"), ("d_far", "<f8")])
+assert RELOCATION_DTYPE.itemsize == 64
+
+
 class rt_obscurance_params(C.Structure):
     """The parameters of obscurance at surfels (rt_obscurance_surfels_device), 24 B."""
     _fields_ = [("radius", C.c_double), ("power", C.c_int32), ("reserved", C.c_uint32 * 3)]
@@ -336,7 +361,9 @@ _OPTIONAL = ("rt_query_rays", "rt_query_rays_device", "rt_camera_rays", "rt_sele
              "rt_probe_radiance_device", "rt_shade_probes", "rt_shade_probes_device", "rt_render_probe_list_device",
              "rt_probe_select_device", "rt_render_probe_depth_device", "rt_probe_depth_close_device",
              "rt_shade_probes_depth_device", "rt_obscurance_surfels_device", "rt_obscurance_select_device",
-             "rt_debug_launch_overlap", "rt_debug_kernel_times_raw")
+             "rt_debug_launch_overlap", "rt_debug_kernel_times_raw", "rt_probe_positions_device",
+             "rt_relocate_probes_device", "rt_shade_probes_placed", "rt_shade_probes_placed_device",
+             "rt_shade_probes_depth_placed_device")
 
 _lib: Optional[C.CDLL] = None
 
@@ -500,6 +527,25 @@ def load_library(path: str = "") -> C.CDLL:
                                                    C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
         "rt_debug_shade_probes_depth": (C.c_int, [P(rt_probe_grid), P(rt_probe_depth_params), C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+        "rt_probe_positions_device": (C.c_int, [P(rt_probe_grid), C.c_void_p, C.c_void_p, C.c_void_p]),
+        "rt_debug_probe_positions": (C.c_int, [P(rt_probe_grid), C.c_void_p, C.c_void_p]),
+        "rt_relocate_probes_device": (C.c_int, [C.c_void_p, P(rt_probe_grid), P(rt_probe_relocate_params), C.c_int32, C.c_uint64,
+                                                C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "rt_debug_probe_relocate": (C.c_int, [P(rt_probe_grid), P(rt_probe_relocate_params), C.c_void_p, C.c_void_p, C.c_int32,
+                                              C.c_void_p, C.c_void_p]),
+        "rt_shade_probes_placed_device": (C.c_int, [C.c_void_p, P(rt_probe_grid)] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p]),
+        "rt_shade_probes_placed": (C.c_int, [C.c_void_p, P(rt_probe_grid)] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p,
+                                             C.c_void_p]),
+        "rt_debug_probe_segments_placed_device": (C.c_int, [P(rt_probe_grid)] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p,
+                                                            C.c_void_p, C.c_void_p]),
+        "rt_debug_probe_segments_placed": (C.c_int, [P(rt_probe_grid)] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_void_p]),
+        "rt_debug_shade_probes_placed": (C.c_int, [P(rt_probe_grid)] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p]),
+        "rt_shade_probes_depth_placed_device": (C.c_int, [P(rt_probe_grid), C.c_void_p, C.c_void_p, P(rt_probe_depth_params)] +
+                                                [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "rt_debug_shade_probes_depth_placed": (C.c_int, [P(rt_probe_grid), C.c_void_p, C.c_void_p, P(rt_probe_depth_params)] +
+                                               [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_void_p]),
         "rt_obscurance_surfels_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                                    P(rt_obscurance_params), C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64,
                                                    C.c_void_p, C.c_void_p]),
@@ -1292,6 +1338,139 @@ def shade_probes_depth_device(grid: rt_probe_grid, params: rt_probe_depth_params
                                             C.c_void_p(_ptr(d_weight)), C.c_void_p(stream)))
 
 
+def _grid_n(grid: rt_probe_grid) -> int:
+    return int(grid.dims[0]) * int(grid.dims[1]) * int(grid.dims[2])
+
+
+def _grid_placement(grid: rt_probe_grid, offsets, state):
+    """A grid's placement as contiguous ((n_probes, 3) f64 or None, (n_probes,) u32 or None), checked against dims."""
+    n = _grid_n(grid)
+    o = s = None
+    if offsets is not None:
+        o = np.ascontiguousarray(offsets, np.float64)
+        if o.size != n * 3 or o.shape[-1:] != (3,):
+            raise ValueError("offsets must hold nx * ny * nz probes of 3 doubles")
+        o = o.reshape(n, 3)
+    if state is not None:
+        s = np.ascontiguousarray(state, np.uint32).reshape(-1)
+        if s.size != n:
+            raise ValueError("state must hold nx * ny * nz uint32")
+    return o, s
+
+
+def _np_ptr(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def probe_positions_host(grid: rt_probe_grid, offsets=None) -> np.ndarray:
+    """rt_debug_probe_positions (host code, no GPU): the grid's probes as (n_probes,) SURFEL_DTYPE, position
+    (origin + i * step) + offset and normal (0, 0, 1); a probe with a non-finite offset is four NaNs."""
+    lib = load_library()
+    if not hasattr(lib, "rt_debug_probe_positions"):
+        raise RtError("this build of the library has no rt_debug_probe_positions")
+    o, _ = _grid_placement(grid, offsets, None)
+    out = np.zeros(_grid_n(grid), SURFEL_DTYPE)
+    _check(lib.rt_debug_probe_positions(C.byref(grid), _np_ptr(o), _np_ptr(out)))
+    return out
+
+
+def probe_positions_device(grid: rt_probe_grid, d_offsets, d_probes_out, stream: int = 0) -> None:
+    """rt_probe_positions_device: n_probes rt_surfel (64 B each) at d_probes_out from the grid and the offsets at
+    d_offsets (0: none), on the current device, asynchronous on `stream`."""
+    lib = load_library()
+    if not hasattr(lib, "rt_probe_positions_device"):
+        raise RtError("this build of the library has no rt_probe_positions_device")
+    _check(lib.rt_probe_positions_device(C.byref(grid), C.c_void_p(_optr(d_offsets)), C.c_void_p(_ptr(d_probes_out)),
+                                         C.c_void_p(stream)))
+
+
+def probe_relocate_host(grid: rt_probe_grid, params: rt_probe_relocate_params, rays, hits, offsets=None):
+    """rt_debug_probe_relocate (host code, no GPU): one relocation step's fold and rule over per-sample results.
+    rays (n_probes, spp) RAY_DTYPE as surfel_rays reports them in RT_GATHER_SPHERE mode at probe_positions, hits
+    (n_probes, spp) HIT_DTYPE as query_rays answers for them, offsets (n_probes, 3) or None for zeros.  Returns
+    (offsets after the step, info (n_probes,) RELOCATION_DTYPE); the argument is not changed."""
+    lib = load_library()
+    if not hasattr(lib, "rt_debug_probe_relocate"):
+        raise RtError("this build of the library has no rt_debug_probe_relocate")
+    r, h = np.ascontiguousarray(rays, RAY_DTYPE), np.ascontiguousarray(hits, HIT_DTYPE)
+    n = _grid_n(grid)
+    if r.ndim != 2 or r.shape != h.shape or r.shape[0] != n:
+        raise ValueError("rays and hits must be (n_probes, spp)")
+    o, _ = _grid_placement(grid, np.zeros((n, 3)) if offsets is None else offsets, None)
+    o = o.copy()
+    info = np.zeros(n, RELOCATION_DTYPE)
+    _check(lib.rt_debug_probe_relocate(C.byref(grid), C.byref(params), _np_ptr(r), _np_ptr(h), r.shape[1], _np_ptr(o),
+                                       _np_ptr(info)))
+    return o, info
+
+
+def probe_segments_placed_host(grid: rt_probe_grid, offsets, state, positions, normals) -> Tuple[np.ndarray, np.ndarray]:
+    """rt_debug_probe_segments_placed (host code, no GPU): probe_segments_host for probes at their placed
+    positions; the empty segment also for a probe that is RT_PROBE_INSIDE or has a non-finite offset."""
+    lib = load_library()
+    if not hasattr(lib, "rt_debug_probe_segments_placed"):
+        raise RtError("this build of the library has no rt_debug_probe_segments_placed")
+    pts = _pack_surfels(positions, normals)
+    n = pts.shape[0]
+    o, s = _grid_placement(grid, offsets, state)
+    rays, t_max = np.zeros((n, 8), RAY_DTYPE), np.zeros((n, 8), np.float64)
+    _check(lib.rt_debug_probe_segments_placed(C.byref(grid), _np_ptr(o), _np_ptr(s), _np_ptr(pts), n, _np_ptr(rays),
+                                              _np_ptr(t_max)))
+    return rays, t_max
+
+
+def shade_probes_placed_host(grid: rt_probe_grid, offsets, state, L, positions, normals,
+                             occluded=None) -> Tuple[np.ndarray, np.ndarray]:
+    """rt_debug_shade_probes_placed (host code, no GPU): shade_probes_host without the probes the placement makes
+    absent; occluded as there, for probe_segments_placed_host's segments."""
+    lib = load_library()
+    if not hasattr(lib, "rt_debug_shade_probes_placed"):
+        raise RtError("this build of the library has no rt_debug_shade_probes_placed")
+    pts = _pack_surfels(positions, normals)
+    n = pts.shape[0]
+    coeffs = _grid_L(grid, L)
+    o, s = _grid_placement(grid, offsets, state)
+    occ = None
+    if occluded is not None:
+        occ = np.ascontiguousarray(np.asarray(occluded) != 0, np.uint8)
+        if occ.shape != (n, 8):
+            raise ValueError("occluded must be (n, 8)")
+    irr, w = np.zeros((n, 3), np.float64), np.zeros(n, np.float64)
+    _check(lib.rt_debug_shade_probes_placed(C.byref(grid), _np_ptr(o), _np_ptr(s), _np_ptr(coeffs), _np_ptr(pts), n, _np_ptr(occ),
+                                            _np_ptr(irr), _np_ptr(w)))
+    return irr, w
+
+
+def shade_probes_depth_placed_host(grid: rt_probe_grid, offsets, state, L, D, params: rt_probe_depth_params, positions,
+                                   normals) -> Tuple[np.ndarray, np.ndarray]:
+    """rt_debug_shade_probes_depth_placed (host code, no GPU): shade_probes_depth_host with the distances and
+    texels taken from the placed positions and without the absent probes."""
+    lib = load_library()
+    if not hasattr(lib, "rt_debug_shade_probes_depth_placed"):
+        raise RtError("this build of the library has no rt_debug_shade_probes_depth_placed")
+    pts = _pack_surfels(positions, normals)
+    n = pts.shape[0]
+    coeffs, moments = _grid_L(grid, L), _grid_D(grid, D)
+    o, s = _grid_placement(grid, offsets, state)
+    irr, w = np.zeros((n, 3), np.float64), np.zeros(n, np.float64)
+    _check(lib.rt_debug_shade_probes_depth_placed(C.byref(grid), _np_ptr(o), _np_ptr(s), C.byref(params), _np_ptr(coeffs),
+                                                  _np_ptr(moments), _np_ptr(pts), n, _np_ptr(irr), _np_ptr(w)))
+    return irr, w
+
+
+def shade_probes_depth_placed_device(grid: rt_probe_grid, d_offsets, d_state, params: rt_probe_depth_params, d_L, d_D, d_points,
+                                     n: int, d_irradiance, d_weight=0, stream: int = 0) -> None:
+    """rt_shade_probes_depth_placed_device: shade_probes_depth_device with n_probes x 3 doubles at d_offsets and
+    n_probes uint32 at d_state (0: none)."""
+    lib = load_library()
+    if not hasattr(lib, "rt_shade_probes_depth_placed_device"):
+        raise RtError("this build of the library has no rt_shade_probes_depth_placed_device")
+    _check(lib.rt_shade_probes_depth_placed_device(C.byref(grid), C.c_void_p(_optr(d_offsets)), C.c_void_p(_optr(d_state)),
+                                                   C.byref(params), C.c_void_p(_ptr(d_L)), C.c_void_p(_ptr(d_D)),
+                                                   C.c_void_p(_ptr(d_points)), n, C.c_void_p(_ptr(d_irradiance)),
+                                                   C.c_void_p(_ptr(d_weight)), C.c_void_p(stream)))
+
+
 def probe_backface_share(counts) -> np.ndarray:
     """Inside hits divided by hits of the depth bake's counts (..., 4) = (hits, inside hits, misses, skipped):
     the share of a probe's hits that met a back face; near 1 for a probe inside geometry.  NaN without a hit."""
@@ -1426,6 +1605,16 @@ def prim_surfels(prim: rt_prim, width: int, height: int, offset: float, flip: bo
 def _ptr(a) -> int:
     """A device pointer as an integer: a torch tensor's data_ptr(), or the integer itself."""
     return int(a.data_ptr()) if hasattr(a, "data_ptr") else int(a)
+
+
+def _optr(a) -> int:
+    """_ptr with None for a null pointer."""
+    return 0 if a is None else _ptr(a)
+
+
+def _to_numpy(a):
+    """A device tensor brought to the host; None and host arrays as they are."""
+    return a.cpu().numpy() if hasattr(a, "data_ptr") else a
 
 
 def _pack_items(items) -> np.ndarray:
@@ -1916,19 +2105,28 @@ class GpuRaytracer:
         acc.update(counts=counts, lists=lists, rays=int(d_rays.item()), params=par)
         return acc
 
-    def shade_probes(self, grid: rt_probe_grid, L, positions, normals) -> Tuple[np.ndarray, np.ndarray]:
+    def shade_probes(self, grid: rt_probe_grid, L, positions, normals, offsets=None,
+                     state=None) -> Tuple[np.ndarray, np.ndarray]:
         """rt_shade_probes: the irradiance a grid of light probes (probe_grid; L (n_probes, 9, 3) as
         probe_radiance_sh returns it, x fastest) gives at surface points: the trilinear blend of the cell's
         eight probes, without those an any-hit query from the point cannot reach (grid.flags) or that hold a
         NaN, then the nine-term dot product for the point's normal.  positions and normals as render_surfels
         takes them.  Returns (irradiance (n, 3), weight (n,)): weight is the share of the trilinear weight that
-        contributed; 0 (and irradiance 0) where no probe did."""
-        if not hasattr(self.lib, "rt_shade_probes"):
-            raise RtError("this build of the library has no rt_shade_probes")
+        contributed; 0 (and irradiance 0) where no probe did.  With offsets (n_probes, 3) or state (n_probes,)
+        given (relocate_probes), rt_shade_probes_placed: the probes sit at their placed positions and those that
+        are RT_PROBE_INSIDE or have a non-finite offset are left out."""
+        placed = offsets is not None or state is not None
+        if not hasattr(self.lib, "rt_shade_probes_placed" if placed else "rt_shade_probes"):
+            raise RtError("this build of the library has no rt_shade_probes" + ("_placed" if placed else ""))
         pts = _pack_surfels(positions, normals)
         n = pts.shape[0]
         coeffs = _grid_L(grid, L)
         irr, w = np.zeros((n, 3), np.float64), np.zeros(n, np.float64)
+        if placed:
+            o, s = _grid_placement(grid, _to_numpy(offsets), _to_numpy(state))
+            _check(self.lib.rt_shade_probes_placed(self.handle, C.byref(grid), _np_ptr(o), _np_ptr(s), _np_ptr(coeffs),
+                                                   _np_ptr(pts), n, _np_ptr(irr), _np_ptr(w)))
+            return irr, w
         _check(self.lib.rt_shade_probes(self.handle, C.byref(grid), coeffs.ctypes.data_as(C.POINTER(C.c_double)),
                                         pts.ctypes.data_as(C.c_void_p), n, irr.ctypes.data_as(C.POINTER(rt_color)),
                                         w.ctypes.data_as(C.POINTER(C.c_double))))
@@ -1987,8 +2185,114 @@ class GpuRaytracer:
             torch.cuda.synchronize()
         return acc
 
+    def _device_placement(self, grid: rt_probe_grid, offsets, state, dev):
+        """offsets and state as contiguous device tensors (f64 (n_probes, 3), int32 (n_probes,)) or None."""
+        import torch
+
+        n = _grid_n(grid)
+        d_o = d_s = None
+        if offsets is not None:
+            d_o = (offsets if hasattr(offsets, "data_ptr") else torch.from_numpy(_grid_placement(grid, offsets, None)[0].copy()).to(dev))
+            if d_o.numel() != n * 3 or d_o.dtype != torch.float64:
+                raise ValueError("offsets must hold nx * ny * nz probes of 3 doubles")
+            d_o = d_o.contiguous()
+        if state is not None:
+            d_s = (state if hasattr(state, "data_ptr")
+                   else torch.from_numpy(_grid_placement(grid, None, state)[1].view(np.int32).copy()).to(dev))
+            if d_s.numel() != n or d_s.dtype != torch.int32:
+                raise ValueError("state must hold nx * ny * nz 32-bit words")
+            d_s = d_s.contiguous()
+        return d_o, d_s
+
+    def probe_positions(self, grid: rt_probe_grid, offsets=None):
+        """rt_probe_positions_device on this scene's device: the grid's probes at their placed positions as a
+        device tensor (n_probes, 64) uint8 of rt_surfel records, the array the probe bakes take (render_probes_device,
+        render_probe_list_device, render_probe_depth_device).  offsets: (n_probes, 3) doubles, host or device, or None."""
+        import torch
+
+        with torch.cuda.device(self.device):
+            dev = torch.device("cuda", self.device)
+            d_o, _ = self._device_placement(grid, offsets, None, dev)
+            out = torch.empty((_grid_n(grid), 64), dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize()
+            probe_positions_device(grid, d_o, out)
+            torch.cuda.synchronize()
+        return out
+
+    def relocate_probes_device(self, grid: rt_probe_grid, params: rt_probe_relocate_params, spp: int, seed: int,
+                               sample_base: int, stream_base: int, d_offsets, d_info, stream: int = 0) -> None:
+        """rt_relocate_probes_device: one asynchronous relocation step of the grid's probes: n_probes x 3 doubles
+        at d_offsets (in/out) and n_probes rt_probe_relocation (64 B each) at d_info (written) on `stream`."""
+        if not hasattr(self.lib, "rt_relocate_probes_device"):
+            raise RtError("this build of the library has no rt_relocate_probes_device")
+        _check(self.lib.rt_relocate_probes_device(self.handle, C.byref(grid), C.byref(params), spp, seed, sample_base, stream_base,
+                                                  C.c_void_p(_optr(d_offsets)), C.c_void_p(_optr(d_info)), C.c_void_p(stream)))
+
+    def relocate_probes(self, grid: rt_probe_grid, params: rt_probe_relocate_params, spp: int, steps: int, seed: int,
+                        sample_base: int = 0, offsets=None):
+        """Probe relocation (rtcore.h, "probe relocation"): `steps` steps on the device, step j with the samples
+        sample_base + j * spp .. + spp - 1 of every probe, then one RT_PROBE_RELOCATE_CLASSIFY_ONLY pass with the
+        samples after them.  Starts from offsets (n_probes, 3; None: zeros).  Returns (offsets (n_probes, 3) f64,
+        state (n_probes,) int32 holding the uint32 bits, info (n_probes, 64) uint8 of rt_probe_relocation records
+        -- .cpu().numpy().view(RELOCATION_DTYPE) -- all device tensors, and the list of probes moved per step)."""
+        import torch
+
+        n = _grid_n(grid)
+        with torch.cuda.device(self.device):
+            dev = torch.device("cuda", self.device)
+            d_o, _ = self._device_placement(grid, np.zeros((n, 3)) if offsets is None else offsets, None, dev)
+            d_o = d_o.clone().reshape(n, 3)
+            d_info = torch.zeros((n, 64), dtype=torch.uint8, device=dev)
+            moved = []
+            torch.cuda.synchronize()
+            for j in range(int(steps)):
+                self.relocate_probes_device(grid, params, spp, seed, int(sample_base) + j * spp, 0, d_o, d_info)
+                moved.append(int(d_info.view(torch.int32)[:, 1].sum().item()))
+            last = rt_probe_relocate_params.from_buffer_copy(params)
+            last.flags |= RT_PROBE_RELOCATE_CLASSIFY_ONLY
+            self.relocate_probes_device(grid, last, spp, seed, int(sample_base) + int(steps) * spp, 0, d_o, d_info)
+            torch.cuda.synchronize()
+            state = d_info.view(torch.int32)[:, 0].contiguous()
+        return d_o, state, d_info, moved
+
+    def shade_probes_placed_device(self, grid: rt_probe_grid, d_offsets, d_state, d_L, d_points, n: int, d_irradiance, d_weight=0,
+                                   stream: int = 0) -> None:
+        """rt_shade_probes_placed_device: shade_probes_device with n_probes x 3 doubles at d_offsets and n_probes
+        uint32 at d_state (None or 0: none)."""
+        if not hasattr(self.lib, "rt_shade_probes_placed_device"):
+            raise RtError("this build of the library has no rt_shade_probes_placed_device")
+        _check(self.lib.rt_shade_probes_placed_device(self.handle, C.byref(grid), C.c_void_p(_optr(d_offsets)),
+                                                      C.c_void_p(_optr(d_state)), C.c_void_p(_ptr(d_L)), C.c_void_p(_ptr(d_points)), n,
+                                                      C.c_void_p(_ptr(d_irradiance)), C.c_void_p(_optr(d_weight)), C.c_void_p(stream)))
+
+    def probe_segments_placed_device(self, grid: rt_probe_grid, offsets, state, positions, normals) -> Tuple[np.ndarray, np.ndarray]:
+        """rt_debug_probe_segments_placed_device on this scene's device: probe_segments_placed_host's (rays, t_max)
+        as the device pass makes them, bit for bit the same."""
+        import torch
+
+        if not hasattr(self.lib, "rt_debug_probe_segments_placed_device"):
+            raise RtError("this build of the library has no rt_debug_probe_segments_placed_device")
+        pts = _pack_surfels(positions, normals)
+        n = pts.shape[0]
+        rays, t_max = np.zeros((n, 8), RAY_DTYPE), np.zeros((n, 8), np.float64)
+        with torch.cuda.device(self.device):
+            dev = torch.device("cuda", self.device)
+            d_o, d_s = self._device_placement(grid, offsets, state, dev)
+            d_in = torch.from_numpy(pts.view(np.uint8).copy()).to(dev)
+            d_rays = torch.zeros(max(rays.nbytes, 1), dtype=torch.uint8, device=dev)
+            d_t = torch.zeros(max(n * 8, 1), dtype=torch.float64, device=dev)
+            torch.cuda.synchronize()
+            _check(self.lib.rt_debug_probe_segments_placed_device(C.byref(grid), C.c_void_p(_optr(d_o)), C.c_void_p(_optr(d_s)),
+                                                                  C.c_void_p(d_in.data_ptr() if n else 0), n,
+                                                                  C.c_void_p(d_rays.data_ptr()), C.c_void_p(d_t.data_ptr()), None))
+            torch.cuda.synchronize()
+            if n:
+                rays.view(np.uint8).reshape(-1)[:] = d_rays.cpu().numpy()[:rays.nbytes]
+                t_max.reshape(-1)[:] = d_t.cpu().numpy()[:n * 8]
+        return rays, t_max
+
     def shade_probes_depth(self, grid: rt_probe_grid, L, D, params: rt_probe_depth_params, positions,
-                           normals) -> Tuple[np.ndarray, np.ndarray]:
+                           normals, offsets=None, state=None) -> Tuple[np.ndarray, np.ndarray]:
         """rt_shade_probes_depth_device on this scene's device: shade_probes without a ray, each corner weighed by
         a Chebyshev test of the point's distance against the probe's depth map D (and by the wrap weight with
         RT_PROBE_DEPTH_WRAP).  grid with flags 0 (probe_grid(..., visibility=False)); L (n_probes, 9, 3) and D
@@ -2007,8 +2311,12 @@ class GpuRaytracer:
             d_pts = torch.from_numpy(pts.view(np.uint8).copy()).to(dev)
             d_irr = torch.zeros((n, 3), dtype=torch.float64, device=dev)
             d_w = torch.zeros(n, dtype=torch.float64, device=dev)
+            d_o, d_s = self._device_placement(grid, offsets, state, dev)
             torch.cuda.synchronize()
-            shade_probes_depth_device(grid, params, d_L.contiguous(), d_D.contiguous(), d_pts, n, d_irr, d_w)
+            if d_o is not None or d_s is not None:  # the probes at their placed positions, the absent ones left out
+                shade_probes_depth_placed_device(grid, d_o, d_s, params, d_L.contiguous(), d_D.contiguous(), d_pts, n, d_irr, d_w)
+            else:
+                shade_probes_depth_device(grid, params, d_L.contiguous(), d_D.contiguous(), d_pts, n, d_irr, d_w)
             torch.cuda.synchronize()
             return d_irr.cpu().numpy(), d_w.cpu().numpy()
 

@@ -1,6 +1,6 @@
 // rt_scene.h -- the scene object behind the C ABI and what the API's translation units share
 // (rtcore_api.hip, scene_upload.hip, api_frame.hip, api_debug.hip, api_query.hip, api_select.hip, api_render_rays.hip,
-// api_render_pixels.hip, api_render_probes.hip, api_shade_probes.hip, api_probe_depth.hip, api_obscurance.hip, chunk_pipeline.hip, api_adaptive.hip, api_denoise.hip, api_reproject.hip).
+// api_render_pixels.hip, api_render_probes.hip, api_shade_probes.hip, api_probe_depth.hip, api_probe_relocate.hip, api_obscurance.hip, chunk_pipeline.hip, api_adaptive.hip, api_denoise.hip, api_reproject.hip).
 #pragma once
 #include <algorithm>
 #include <array>
@@ -203,11 +203,11 @@ struct rt_scene {
     DevBuf<double> probe_seg_t_max;
     DevBuf<unsigned char> probe_seg_occluded;
     DevBuf<double> shade_L, shade_out;
-    // rt_render_probe_depth_device and rt_obscurance_surfels_device: one chunk's sample rays and their closest
-    // hits, made and read on the caller's stream
+    // rt_render_probe_depth_device, rt_relocate_probes_device and rt_obscurance_surfels_device: one chunk's sample
+    // rays and their closest hits, made and read on the caller's stream
     DevBuf<rt_ray> probe_depth_rays;
     DevBuf<rt_hit> probe_depth_hits;
-    DevBuf<rt_surfel> shade_points;
+    DevBuf<rt_surfel> shade_points; // (rt_relocate_probes_device: also a chunk's probe records)
     // run_items: the blocks per CU of each ItemSource's instance of `items_variant`
     int items_variant[ITEMS_SURFELS + 1] = {-1, -1, -1, -1, -1}, items_blocks_per_cu[ITEMS_SURFELS + 1] = {1, 1, 1, 1, 1};
     // the selection pass (api_select.hip): the caller's item list on the device, and the host-buffer

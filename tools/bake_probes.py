@@ -2,7 +2,7 @@
 
 usage: python tools/bake_probes.py SCENE --grid NX NY NZ [--bounds X0 Y0 Z0 X1 Y1 Z1] --spp N [--seed S]
                                    [--traversal MODE] [--show K] [--out probes.npz]
-                                   [--tol T [--min A] [--max B] [--batch C]]
+                                   [--tol T [--min A] [--max B] [--batch C]] [--relocate STEPS [--min-front X]]
 
 SCENE is a scene file (or the name of one shipped in tests/golden/scenes).  The probes are the cell centres of
 an NX x NY x NZ grid over --bounds (default: the box of the scene's primitives without the planes,
@@ -16,6 +16,11 @@ samples [n], misses [n] and the grid to the .npz.
 standard error of its band-0/1 irradiance is at most T of its mean luminance.  The .npz then also holds the
 samples each probe took (spp [n]), and the total is printed against n x B.  A probe whose samples so far all came
 back black has an estimated error of zero and stops at A: choose --min so that a probe finds the scene's lights.
+
+--relocate STEPS first moves the probes off nearby geometry (rtcore.h, "probe relocation";
+GpuRaytracer.relocate_probes: STEPS steps of N samples each, min_front X, default a fifth of the smallest cell
+side, then a classification) and bakes at the relocated positions.  The .npz then also holds offsets [n, 3] and
+state [n] (RT_PROBE_INSIDE, RT_PROBE_IDLE), which shade_probes takes; positions are the relocated ones.
 
 For the first K probes (--show, default 3) and the six axis normals it prints sh_irradiance(L, normal) beside
 pi x gather_mean of a COSINE render_surfels of the same N samples at the same point: the irradiance by its
@@ -78,9 +83,11 @@ def main(argv=None) -> int:
     ap.add_argument("--min", type=int, default=64, dest="min_spp")
     ap.add_argument("--max", type=int, dest="max_spp", help="default: --spp")
     ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--relocate", type=int, default=0, metavar="STEPS")
+    ap.add_argument("--min-front", type=float, default=None, metavar="X")
     a = ap.parse_args(argv)
-    if min(a.grid) < 1 or a.spp < 1:
-        ap.error("--grid and --spp must be >= 1")
+    if min(a.grid) < 1 or a.spp < 1 or a.relocate < 0:
+        ap.error("--grid and --spp must be >= 1, --relocate >= 0")
     max_spp = a.max_spp if a.max_spp is not None else a.spp
     if a.tol is not None and (a.tol < 0 or a.batch < 1 or a.min_spp < 1 or max_spp < a.min_spp):
         ap.error("--tol needs T >= 0, --batch >= 1 and 1 <= --min <= --max")
@@ -100,7 +107,19 @@ def main(argv=None) -> int:
     positions = probe_grid(bounds, a.grid)
     amb = scene.params.ambient
     gpu = rc.GpuRaytracer(scene, 0, traversal=getattr(rc, "RT_TRAVERSAL_" + a.traversal))
+    placement = {}
     try:
+        if a.relocate:
+            step = (np.array(bounds[3:]) - np.array(bounds[:3])) / np.array(a.grid)
+            grid = rc.probe_grid(positions[0], step, a.grid, False)
+            min_front = a.min_front if a.min_front is not None else 0.2 * float(step.min())
+            d_o, d_state, _, moved = gpu.relocate_probes(grid, rc.probe_relocate_params(min_front), a.spp, a.relocate, a.seed)
+            placement = {"offsets": d_o.cpu().numpy(), "state": d_state.cpu().numpy().view(np.uint32)}
+            placed = gpu.probe_positions(grid, d_o).cpu().numpy().view(rc.SURFEL_DTYPE).reshape(-1)
+            positions = placed["position"][:, :3].copy()  # (NaN for a probe without a valid offset: none comes from a step)
+            st = placement["state"]
+            print(f"relocation: min_front {min_front:.4g}, moved per step {moved}, {int((st & rc.RT_PROBE_INSIDE != 0).sum())} probes "
+                  f"inside, {int((st & rc.RT_PROBE_IDLE != 0).sum())} idle")
         if a.tol is None:
             L, ns, ms, rays = bake_probes(gpu, positions, a.spp, amb, a.seed)
             taken = None
@@ -114,7 +133,7 @@ def main(argv=None) -> int:
             rows.append((rc.sh_irradiance(L[i], AXES), np.pi * rc.gather_mean(s, cn, cm, amb)))
     finally:
         gpu.close()
-    extra = {} if taken is None else {"spp": taken}
+    extra = dict(placement, **({} if taken is None else {"spp": taken}))
     np.savez(a.out, positions=positions, L=L, samples=ns, misses=ms, grid=np.array(a.grid), bounds=np.array(bounds), **extra)
     if taken is None:
         how = f"{a.spp} spp"

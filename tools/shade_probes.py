@@ -2,6 +2,7 @@
 
 usage: python tools/shade_probes.py SCENE --grid NX NY NZ --spp N [--prim P] --size W H [--offset E] [--flip]
                                     [--seed S] [--traversal MODE] [--out PREFIX] [--depth]
+                                    [--relocate STEPS [--min-front X]]
        python tools/shade_probes.py --mesh --grid ...
 
 SCENE is a scene file (or the name of one shipped in tests/golden/scenes; --mesh: the procedural 1 M-triangle
@@ -24,6 +25,14 @@ twice the grid's diagonal step, sharpness 5) and shades the texels a third way, 
 PREFIX_depth.npy / PREFIX_depth_weight.npy; prints its difference to the gather as for the other two, and how the
 depth test agrees with the rays over the (texel, corner) pairs that have a segment: the share of ray-hidden
 corners whose Chebyshev weight c is below 0.5, and the share of ray-visible corners with c >= 0.5.
+
+--relocate STEPS [--min-front X] (implies --depth): probe relocation (rtcore.h, "probe relocation").  STEPS steps of
+N samples each and a classification (relocate_probes; min_front X, default a fifth of the smallest step), then the
+radiance and the depth maps are baked again at the relocated positions (probe_positions) and the texels shaded
+through the placed entries, with rays (rt_shade_probes_placed_device) and with the maps
+(rt_shade_probes_depth_placed_device), into PREFIX_relocated.npy / PREFIX_relocated_weight.npy.  Prints both
+differences to the gather, the probes moved per step, the state counts, and the agreement table above before and
+after relocation (after: the segments end at the relocated probes).
 """
 from __future__ import annotations
 
@@ -131,9 +140,12 @@ def main(argv=None) -> int:
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--traversal", default="AUTO", choices=["AUTO", "BRUTE", "GROUPED", "BVH"])
     ap.add_argument("--out", default="shade_probes")
+    ap.add_argument("--relocate", type=int, default=0, metavar="STEPS")
+    ap.add_argument("--min-front", type=float, default=None, metavar="X")
     a = ap.parse_args(argv)
-    if min(a.grid) < 1 or a.spp < 1 or min(a.size) < 1:
-        ap.error("--grid, --spp and --size must be >= 1")
+    if min(a.grid) < 1 or a.spp < 1 or min(a.size) < 1 or a.relocate < 0:
+        ap.error("--grid, --spp and --size must be >= 1, --relocate >= 0")
+    a.depth = a.depth or a.relocate > 0
 
     import torch
 
@@ -180,6 +192,25 @@ def main(argv=None) -> int:
             occ = np.asarray(gpu.occluded_rays(seg.reshape(-1), None, t_max.reshape(-1))).reshape(n, 8) != 0
             cheb = corner_chebyshev(rc, grid, acc["D"].cpu().numpy(), seg, t_max, d_max, P.var_floor)
             counts = acc["counts"].cpu().numpy().view(np.uint32).astype(np.int64)
+        if a.relocate:
+            min_front = a.min_front if a.min_front is not None else 0.2 * float(min(flat.step))
+            R = rc.probe_relocate_params(min_front)
+            d_o, d_state, d_info, moved = gpu.relocate_probes(flat, R, a.spp, a.relocate, a.seed)
+            placed = gpu.probe_positions(flat, d_o).cpu().numpy().view(rc.SURFEL_DTYPE).reshape(-1)
+            d_Lr, _ = bake_grid_device(rc, torch, gpu, placed["position"][:, :3], a.spp, a.seed, amb)
+            acc_r = gpu.render_probe_depth(placed, a.spp, a.seed, d_max, sharpness=5)
+            d_Er, d_Ev = (torch.empty((n, 3), dtype=torch.float64, device="cuda") for _ in range(2))
+            d_Wr, d_Wv = (torch.empty(n, dtype=torch.float64, device="cuda") for _ in range(2))
+            rc.shade_probes_depth_placed_device(flat, d_o, d_state, P, d_Lr, acc_r["D"], d_pts, n, d_Er, d_Wr)
+            gpu.shade_probes_placed_device(grid, d_o, d_state, d_Lr, d_pts, n, d_Ev, d_Wv)
+            torch.cuda.synchronize()
+            Er, Wr, Ev, Wv = d_Er.cpu().numpy(), d_Wr.cpu().numpy(), d_Ev.cpu().numpy(), d_Wv.cpu().numpy()
+            seg_r, t_max_r = gpu.probe_segments_placed_device(grid, d_o, d_state, pos.reshape(-1, 3), nrm.reshape(-1, 3))
+            occ_r = np.asarray(gpu.occluded_rays(seg_r.reshape(-1), None, t_max_r.reshape(-1))).reshape(n, 8) != 0
+            cheb_r = corner_chebyshev(rc, grid, acc_r["D"].cpu().numpy(), seg_r, t_max_r, d_max, P.var_floor)
+            counts_r = acc_r["counts"].cpu().numpy().view(np.uint32).astype(np.int64)
+            state = d_state.cpu().numpy().view(np.uint32)
+            offsets = d_o.cpu().numpy()
     finally:
         gpu.close()
 
@@ -200,16 +231,33 @@ def main(argv=None) -> int:
         ways.append(("depth maps", Ed, Wd > 0))
         np.save(a.out + "_depth.npy", image(Ed))
         np.save(a.out + "_depth_weight.npy", image(Wd)[..., 0])
+    if a.relocate:
+        ways += [("relocated, rays", Ev, Wv > 0), ("relocated, maps", Er, Wr > 0)]
+        np.save(a.out + "_relocated.npy", image(Er))
+        np.save(a.out + "_relocated_weight.npy", image(Wr)[..., 0])
     for label, e, lit in ways:
         d = np.abs(e @ LUM - ref)[lit] / scale
         print(f"  {label:14s} mean |difference| {float(np.nanmean(d)) if d.size else float('nan'):.4f}, max "
               f"{float(np.nanmax(d)) if d.size else float('nan'):.4f} of that mean, over {int(lit.sum())} texels with a probe")
     print(f"  weight < 1 at {float((Wt < 1 - 1e-12).mean()):.4f} of the texels, weight 0 at {float((Wt == 0).mean()):.4f}"
           f" -> {a.out}.npy, {a.out}_flat.npy, {a.out}_weight.npy, {a.out}.ppm, {a.out}_flat.ppm")
+    share = lambda sel, ok: float((ok & sel).sum()) / max(int(sel.sum()), 1)  # noqa: E731
+    if a.relocate:
+        steps = np.linalg.norm(offsets / np.array(flat.step), axis=1)
+        print(f"  relocation: min_front {min_front:.4g}, {a.relocate} steps of {a.spp} spp moved {moved} probes; states: "
+              f"{int((state == 0).sum())} plain, {int((state & rc.RT_PROBE_INSIDE != 0).sum())} inside, "
+              f"{int((state & rc.RT_PROBE_IDLE != 0).sum())} idle; offsets up to {float(np.nanmax(steps)):.3f} steps, "
+              f"{int((steps > 0).sum())} of {len(steps)} probes off their grid position")
+        for label, tm, oc, ch, cn in (("before", t_max, occ, cheb, counts), ("after", t_max_r, occ_r, cheb_r, counts_r)):
+            has = tm > 0
+            hidden, visible = has & oc, has & ~oc
+            print(f"  {label:6s} relocation: {int(has.sum())} (texel, corner) pairs, {int(hidden.sum())} ray-hidden, of them c < 0.5 at "
+                  f"{share(hidden, ch < 0.5):.4f}; {int(visible.sum())} ray-visible, of them c >= 0.5 at {share(visible, ch >= 0.5):.4f}; "
+                  f"inside hits {int(cn[:, 1].sum())} of {int(cn[:, 0].sum())}, "
+                  f"{int((rc.probe_backface_share(cn) > 0.5).sum())} probes with a backface share above 0.5")
     if a.depth:
         has = t_max > 0
         hidden, visible = has & occ, has & ~occ
-        share = lambda sel, ok: float((ok & sel).sum()) / max(int(sel.sum()), 1)
         print(f"  depth against rays over {int(has.sum())} (texel, corner) pairs: {int(hidden.sum())} ray-hidden, of them c < 0.5 at "
               f"{share(hidden, cheb < 0.5):.4f}; {int(visible.sum())} ray-visible, of them c >= 0.5 at {share(visible, cheb >= 0.5):.4f}; "
               f"depth weight < 1 at {float((Wd < 1 - 1e-12).mean()):.4f} of the texels, 0 at {float((Wd == 0).mean()):.4f}; "
